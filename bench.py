@@ -586,6 +586,22 @@ def config5_workload(args, ffi, dist, rank, world, gpu, ring, gulp_bytes, pin, i
     }
 
 
+DUMP_SAMPLE = 1 << 21       # visibilities per plane that --dump-outputs writes
+
+
+def dump_outputs(path, vis, rank, world):
+    """--dump-outputs: the dump of the last timed step as its caller receives it, int32[2][nchan][per_chan] (planar re|im,
+    xGPU register-tile order), is 191 MB at config 2.  Written: the same DUMP_SAMPLE positions of every run (fixed seed,
+    ascending) as visibilities_index.npy and both planes there as visibilities.npy [2][DUMP_SAMPLE], float64 (exact for
+    every int32): 48 MB.  Ranks of an N-GPU run (their own channels) add _rank<r> to the names."""
+    vis = vis.reshape(2, -1)
+    idx = np.sort(np.random.RandomState(0x5eed).permutation(vis.shape[1])[:DUMP_SAMPLE])
+    sfx = "_rank%d" % rank if world > 1 else ""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "visibilities_index%s.npy" % sfx), idx.astype(np.float64))
+    np.save(os.path.join(path, "visibilities%s.npy" % sfx), vis[:, idx].astype(np.float64))
+
+
 def _leg(name):
     """XENG_BENCH_TRACE=1: names each leg on stderr as it starts (a fault under a profiler then says where it was)"""
     if os.environ.get("XENG_BENCH_TRACE"):
@@ -627,7 +643,13 @@ def main():
     ap.add_argument("--selftest-spawn", action="store_true",
                     help="testing only (no GPU): ranks skip the X-engine work and report a fixed fake time, so that the "
                          "N-rank launch, the process group, the max-over-ranks and the JSON line can be checked on CPU")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the visibilities of the last timed step to DIR/*.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "correlator":
+        ap.error("--dump-outputs: only the correlator workload")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under torch.distributed.run: be the launcher.  Nothing in this process has touched the GPU yet.
@@ -782,6 +804,9 @@ def main():
     ffi.call("xengDeviceSynchronize")
     el = time.perf_counter() - t0
     ffi.call("xengXgpuGetTimes", tm, cn)
+    if args.dump_outputs:
+        # (before the legs below reuse the output spans)
+        dump_outputs(args.dump_outputs, outs[(si[0] - 1) % nout].download(np.int32), rank, world)
     _leg('one-launch-at-a-time')
     # outside the timed region: the same kernels launched one integration at a time (no overlap between
     # launches), to document the stand-alone duration of each kernel next to the streaming one

@@ -28,7 +28,8 @@ BAD_PK = re.compile(VOP3P + r".*\bop_sel:\[0,1[,\]]")
 def code_objects(lib, tmp):
     """gfx950 code objects of a HIP shared library: the .hip_fatbin section is a sequence of clang offload bundles."""
     fat = os.path.join(tmp, "fat.bin")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, lib])
+    # (an output file of its own: without one llvm-objcopy rewrites the library in place)
+    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, lib, os.path.join(tmp, "lib.out")])
     data = open(fat, "rb").read()
     magic = b"__CLANG_OFFLOAD_BUNDLE__"
     out, pos = [], data.find(magic)

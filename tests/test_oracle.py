@@ -272,3 +272,20 @@ def test_vectorised_cpu_baseline_equals_the_scalar_oracle():
         assert np.array_equal(a, b), (T, C, S)
         assert np.array_equal(orc.xgpu_correlate(v[T:], S, C, a), orc.xgpu_correlate_fast(v[T:], S, C, b)), (T, C, S)
     assert orc.fast_lib().fast_isa() in (0, 1, 2) and orc.fast_lib().fast_num_threads() >= 1
+
+
+def test_vectorised_cpu_baseline_builds_in_a_checkout_it_cannot_write(monkeypatch):
+    """A checkout built by another account, read-only to the user who runs bench.py, with no library for this host in it:
+    the library is built for this process alone, in a temporary directory removed once it is loaded; oracle/ is left alone."""
+    real_access, real_exists, real_mkdtemp = os.access, os.path.exists, orc.tempfile.mkdtemp
+    made = []
+    monkeypatch.setattr(orc, "_FAST", None)
+    monkeypatch.setattr(os, "access", lambda p, mode: False if p == orc.HERE else real_access(p, mode))
+    monkeypatch.setattr(os.path, "exists", lambda p: False if os.path.dirname(p) == orc.HERE and
+                        os.path.basename(p).startswith("libxeng_cpu_fast_") else real_exists(p))
+    monkeypatch.setattr(orc.tempfile, "mkdtemp", lambda **kw: made.append(real_mkdtemp(**kw)) or made[-1])
+    before = sorted(os.listdir(orc.HERE))
+    v = np.random.default_rng(5).integers(0, 256, (8, 4, 16, 2), dtype=np.uint8)
+    assert np.array_equal(orc.xgpu_correlate_fast(v, 16, 4), orc.xgpu_correlate(v, 16, 4))
+    assert len(made) == 1 and not real_exists(made[0])
+    assert sorted(os.listdir(orc.HERE)) == before
