@@ -212,6 +212,13 @@ class HipBackend:
         # (bfBeamformIntegrate reads only the two data pointers from its structs: the raw entry point, no structs built per gulp)
         return self._x.beam_integrate(_dev(in_arr), _dev(out_arr), int(ntime_sum))
 
+    def beam_packetize_voltages(self, in_arr, out_arr, nchan, nbeam, ntime, beam0, nbeam_pkt, pkt_stride, server, gbe, nbeam_hdr, nserver,
+                                chan0, seq0):
+        """BeamformVlbiOutput's gulp -> "ibeam" packets on the beamformer's stream (include/xeng.h xengBeamformPacketizeVoltages;
+        beamform_vlbi_output_block.py:258-276 does it on the host).  Enqueue only: beam_mark / beam_wait cover it."""
+        return self._enq.xengBeamformPacketizeVoltages(in_arr.ptr, out_arr.ptr, int(nchan), int(nbeam), int(ntime), int(beam0), int(nbeam_pkt),
+                                                       int(pkt_stride), int(server), int(gbe), int(nbeam_hdr), int(nserver), int(chan0), int(seq0))
+
     def last_error(self):
         return self._lib.xengGetLastError().decode()
 

@@ -6,6 +6,7 @@
 #include <mutex>
 
 #include "beamform_kernels.h"
+#include "beam_vlbi_kernels.h"
 #include <algorithm>
 #include <vector>
 
@@ -477,6 +478,44 @@ int xengBeamformIntegrateSingleBeam(const void* in_dev, void* out_dev, int ntime
     if (beam_id < 0 || beam_id >= x.nbeam / 2) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "IntegrateSingleBeam: beam %d out of range", beam_id);
     XENG_HIP(hipSetDevice(x.gpu));
     return integrate_locked(in_dev, out_dev, ntime_sum, beam_id, 1);
+}
+
+// beamform_vlbi_output_block.py:258-276 on the device (beam_vlbi_kernels.h).  Every argument is checked before the context is
+// looked at, so that a bad call is told apart from a missing context (and is refused without launching anything).
+int xengBeamformPacketizeVoltages(const void* in_dev, void* out_dev, int nchan, int nbeam, int ntime, int beam0, int nbeam_pkt,
+                                  size_t pkt_stride, int server, int gbe, int nbeam_hdr, int nserver, int chan0, uint64_t seq0) {
+    if (!in_dev || !out_dev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "PacketizeVoltages: null buffer");
+    if ((uintptr_t)in_dev % 8) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "PacketizeVoltages: input %p not 8-byte aligned (cf32)", in_dev);
+    if ((uintptr_t)out_dev % 16) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "PacketizeVoltages: output %p not 16-byte aligned", out_dev);
+    if (nchan <= 0 || nbeam <= 0 || ntime <= 0 || nbeam_pkt <= 0)
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "PacketizeVoltages: bad sizes nchan=%d nbeam=%d ntime=%d nbeam_pkt=%d", nchan, nbeam, ntime, nbeam_pkt);
+    if (beam0 < 0 || beam0 >= nbeam || nbeam_pkt > nbeam - beam0)
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "PacketizeVoltages: beams [%d, %d) outside [0, %d)", beam0, beam0 + nbeam_pkt, nbeam);
+    if (nchan > 255 || nbeam_hdr < 0 || nbeam_hdr > 255 || nserver < 0 || nserver > 255 || server < 0 || server > 255 || gbe < 0 || gbe > 255)
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "PacketizeVoltages: header field out of uint8 range (nchan=%d nbeam=%d nserver=%d server=%d gbe=%d)",
+                  nchan, nbeam_hdr, nserver, server, gbe);
+    if (chan0 < 0 || chan0 > 65535) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "PacketizeVoltages: chan0 %d out of uint16 range", chan0);
+    const size_t nrow = (size_t)nchan * nbeam_pkt;
+    if (nrow > (1u << 24) || ntime > 65535 * VLBI_TIMES)
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "PacketizeVoltages: %zu beams x channels or %d samples is more than one launch takes", nrow, ntime);
+    if (pkt_stride % 16 || pkt_stride < VLBI_HDR + 8 * nrow)
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "PacketizeVoltages: packet stride %zu not a multiple of 16 of at least %zu bytes", pkt_stride,
+                  (size_t)VLBI_HDR + 8 * nrow);
+    std::lock_guard<std::mutex> lk(g_bmu);
+    BeamContext& x = g_b;
+    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Beamform: not initialized (the Beamform block initializes the shared context)");
+    XENG_HIP(hipSetDevice(x.gpu));
+    const VlbiHeader h{(uint8_t)server, (uint8_t)gbe, (uint8_t)nchan, (uint8_t)nbeam_hdr, (uint8_t)nserver, (uint16_t)chan0, seq0};
+    const dim3 grid((unsigned)((nrow + VLBI_ROWS - 1) / VLBI_ROWS), (unsigned)((ntime + VLBI_TIMES - 1) / VLBI_TIMES));
+    if (ntime % 2 == 0 && (uintptr_t)in_dev % 16 == 0)
+        hipLaunchKernelGGL(beam_vlbi_packetize_kernel<true>, grid, dim3(256), 0, x.stream, (const uint2*)in_dev, (uint8_t*)out_dev,
+                           nbeam, ntime, beam0, nbeam_pkt, (int)nrow, pkt_stride, h);
+    else
+        hipLaunchKernelGGL(beam_vlbi_packetize_kernel<false>, grid, dim3(256), 0, x.stream, (const uint2*)in_dev, (uint8_t*)out_dev,
+                           nbeam, ntime, beam0, nbeam_pkt, (int)nrow, pkt_stride, h);
+    stream_tick(STREAM_BEAM);
+    XENG_HIP(hipGetLastError());
+    return XENG_STATUS_SUCCESS;
 }
 
 int xengBeamformSync(void) {

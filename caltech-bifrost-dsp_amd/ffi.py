@@ -86,6 +86,7 @@ SYMBOLS = {
     "xengBeamformRunSlabs": [_vp, _i, _i, _vp, _i, _sz, ctypes.c_uint64, _i, _vp, _vp, ctypes.c_longlong], "xengBeamformTryRunSlabs": [_vp, _i, _i, _vp, _i, _sz, ctypes.c_uint64, _i, _vp, _vp, ctypes.c_longlong], "xengBeamformGetSlabFallbacks": [_pi], "xengBeamformGetSlabStats": [_pi, _pi],
     "xengBeamformIntegrate": [_vp, _vp, _i],
     "xengBeamformIntegrateSingleBeam": [_vp, _vp, _i, _i], "xengBeamformMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengBeamformWait": [ctypes.c_ulonglong], "xengBeamformTicketDone": [ctypes.c_ulonglong, _pi], "xengBeamformSync": [],
+    "xengBeamformPacketizeVoltages": [_vp, _vp, _i, _i, _i, _i, _i, _sz, _i, _i, _i, _i, _i, ctypes.c_uint64],
     "xengBeamformSetProfiling": [_i], "xengBeamformGetTimes": [ctypes.POINTER(ctypes.c_double), _pi],
     "xengBeamformGetRouteInfo": [_pi, _pi, _pi],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
@@ -128,7 +129,7 @@ def lib():
 # XENG_STATUS_WOULD_BLOCK instead, and the caller gives the lock up to wait; xengSnap2UnpackAsync shares a mutex with the
 # synchronous call, which polls: it is made on the releasing handle.)
 ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xengBeamformTryRunVersioned", "xengBeamformTryRunParts", "xengBeamformTryRunSlabs",
-                "xengBeamformIntegrate", "xengBeamformIntegrateSingleBeam", "xengBeamformMark", "xengMapAssignI32",
+                "xengBeamformIntegrate", "xengBeamformIntegrateSingleBeam", "xengBeamformPacketizeVoltages", "xengBeamformMark", "xengMapAssignI32",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

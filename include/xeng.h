@@ -386,6 +386,22 @@ int xengBeamformIntegrate(const void *in_dev, void *out_dev, int ntime_sum);
 
 /* beamform_sum_single_beam_block.py:114: one dual-pol beam -> f32[ntime/ntime_sum][nchan][4]. */
 int xengBeamformIntegrateSingleBeam(const void *in_dev, void *out_dev, int ntime_sum, int beam_id);
+/* beamform_vlbi_output_block.py:258-276 (BeamformVlbiOutput): the voltage beams of one gulp -> ntime "ibeam" packets, built on
+ * the beamformer's stream (xengBeamformMark / Wait / TicketDone cover it; a live context is required, INVALID_STATE otherwise,
+ * but every size comes from the arguments).  in_dev cf32[nchan][nbeam][ntime] (the Beamform output span, 8-byte aligned; never
+ * written).  Packet t lives in slot t at out_dev + t*pkt_stride (out_dev 16-byte aligned, pkt_stride a multiple of 16 and at
+ * least 16 + 8*nchan*nbeam_pkt) and is the byte range [1, 16 + 8*nchan*nbeam_pkt) of its slot:
+ *   bytes [1,16)  header, the packed 15-byte `struct ibeam` of the reference docstring (:141-149):
+ *                 u8 server, gbe, nchan, nbeam (= nbeam_hdr), nserver; u16 chan0; u64 seq = seq0 + t; multi-byte fields big-endian
+ *   bytes [16,..) payload cf32[nchan][nbeam_pkt] = beams [beam0, beam0+nbeam_pkt) at sample t, bits copied unchanged, native
+ *                 byte order (bifrost sends the numpy payload as it lies)
+ * so a sender passes slot[1 : 16 + payload] as one contiguous buffer.  Byte 0 and the bytes after the packet are left as they were.
+ * The layout is UNPINNED: the docstring also says "32 byte header" (:137) and a uint32 chan0 (:174), and bifrost's ibeam writer
+ * is an empty submodule in the reference tree; this follows its struct.  Rejected without a launch: null or misaligned
+ * pointers, beams outside [0, nbeam), nchan / nbeam_hdr / nserver / server / gbe above 255, chan0 above 65535, a stride too
+ * small for header and payload. */
+int xengBeamformPacketizeVoltages(const void *in_dev, void *out_dev, int nchan, int nbeam, int ntime, int beam0, int nbeam_pkt,
+                                  size_t pkt_stride, int server, int gbe, int nbeam_hdr, int nserver, int chan0, uint64_t seq0);
 int xengBeamformSync(void);
 /* Completion tickets on the beamformer's stream: Mark returns a ticket for everything enqueued so far (Run, Integrate,
  * by any thread), Wait blocks until that point has been reached.  They let the Beamform / BeamformSumBeams blocks keep
