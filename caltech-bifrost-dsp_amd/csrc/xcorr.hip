@@ -36,8 +36,6 @@ struct XgpuContext {
     WorkList work_pairs;                       // the same items with neighbouring channels per XCD and round (packet-slab launches: xcorr_tiling.h build_work)
     size_t gulp_bytes = 0;
     const uint8_t* gulp_ptr[XC_MAX_GULPS] = {};
-    bool fp6 = false;          // -DXENG_EXPERIMENTS builds, XENG_MFMA=fp6: E3M2 codes + block-scaled FP6 MFMA (exact)
-    int ghk = 0;               // fp6: 32-sample half-tiles per gulp; cap_kt then counts 64-sample K steps
     int64_t per_chan = 0, matlen = 0;
     // Two staging areas (raw gulp copies of the synchronous calls, or corner-turned fragments on the two-pass
     // path): filled on `stream` while the contraction of the previous flush reads the other one.
@@ -140,72 +138,31 @@ static int destroy_locked() {
     return XENG_STATUS_SUCCESS;
 }
 
-template <int ABL>
-static void launch_abl(const XcorrParams& p, hipStream_t s) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_mfma_kernel<ABL>), dim3(p.nchan * p.nwg), dim3(256), 0, s, p);
-}
 static void launch_xcorr(const XcorrParams& p, hipStream_t s, bool raw, int grid_size, bool kloop16) {
     if (raw) {
         const dim3 grid(grid_size);
-#ifdef XENG_DIAGNOSTICS
-        const int fabl = getenv("XENG_ABLATE") ? atoi(getenv("XENG_ABLATE")) : 0;     // (diagnostic build: read per launch, so one process can alternate)
-        if (kloop16 && fabl == 16 && !p.gdesc && !p.acc2_mode) { hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused16_kernel<16>), grid, dim3(512), 0, s, p); return; }
-        switch (fabl) {
-            case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<1>), grid, dim3(256), 0, s, p); return;
-            case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<2>), grid, dim3(256), 0, s, p); return;
-            case 4: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<4>), grid, dim3(256), 0, s, p); return;
-            case 8: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<8>), grid, dim3(256), 0, s, p); return;
-            case 9: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<9>), grid, dim3(256), 0, s, p); return;
-            case 15: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<15>), grid, dim3(256), 0, s, p); return;
-            case 16: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<16>), grid, dim3(256), 0, s, p); return;
-            case 32: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<32>), grid, dim3(256), 0, s, p); return;
-            case 48: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<48>), grid, dim3(256), 0, s, p); return;
-            case 5: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<5>), grid, dim3(256), 0, s, p); return;
-            case 17: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<17>), grid, dim3(256), 0, s, p); return;
-            case 31: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<31>), grid, dim3(256), 0, s, p); return;
-            case 64: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<64>), grid, dim3(256), 0, s, p); return;
-            case 128: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<128>), grid, dim3(256), 0, s, p); return;   // diagonal cells at 3/4 of their MFMAs
-            case 256: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<256>), grid, dim3(256), 0, s, p); return;   // offset-binary operands
-            case 384: hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<384>), grid, dim3(256), 0, s, p); return;
-            default: break;
-        }
-#endif
         // the eight-wave 16x16x64 kernel (xcorr_fused16.h) for gulps by pointer without a long accumulator; the four-wave kernel otherwise
         // (round 5: and for gulps through their offset tables -- those are laid out for the four-wave kernel's pieces)
         if (kloop16 && !p.acc2_mode && !(p.gdesc && p.by_table)) {
-            if (p.gdesc) hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused16_kernel<0, true>), grid, dim3(512), 0, s, p);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused16_kernel<0>), grid, dim3(512), 0, s, p);
+            if (p.gdesc) hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused16_kernel<true>), grid, dim3(512), 0, s, p);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused16_kernel<>), grid, dim3(512), 0, s, p);
             return;
         }
         if (p.gdesc && p.by_table) {          // gulps by descriptor, every one through its offset table (packet slabs on a lossy link)
-            if (p.acc2_mode) hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<0, true, true, true>), grid, dim3(256), 0, s, p);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<0, false, true, true>), grid, dim3(256), 0, s, p);
+            if (p.acc2_mode) hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<true, true, true>), grid, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<false, true, true>), grid, dim3(256), 0, s, p);
             return;
         }
         if (p.gdesc) {          // gulps by descriptor, by strides (packet slabs)
-            if (p.acc2_mode) hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<0, true, true>), grid, dim3(256), 0, s, p);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<0, false, true>), grid, dim3(256), 0, s, p);
+            if (p.acc2_mode) hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<true, true>), grid, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<false, true>), grid, dim3(256), 0, s, p);
             return;
         }
-        if (p.acc2_mode) hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<0, true>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<0>), grid, dim3(256), 0, s, p);
+        if (p.acc2_mode) hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(xcorr_fused_kernel<>), grid, dim3(256), 0, s, p);
         return;
     }
-#ifdef XENG_DIAGNOSTICS
-    // timing-only ablations of the K loop (results are wrong): build with -DXENG_DIAGNOSTICS, select with
-    // XENG_ABLATE = 1 (no LDS-DMA) | 2 (no unpack) | 4 (no LDS reads) | 8 (no barrier); see profiles/r01/README.md
-    const int abl = getenv("XENG_ABLATE") ? atoi(getenv("XENG_ABLATE")) : 0;
-    switch (abl) {
-        case 1: launch_abl<1>(p, s); return;
-        case 2: launch_abl<2>(p, s); return;
-        case 4: launch_abl<4>(p, s); return;
-        case 8: launch_abl<8>(p, s); return;
-        case 9: launch_abl<9>(p, s); return;
-        case 15: launch_abl<15>(p, s); return;
-        default: break;
-    }
-#endif
-    launch_abl<0>(p, s);
+    hipLaunchKernelGGL(xcorr_mfma_kernel, dim3(p.nchan * p.nwg), dim3(256), 0, s, p);
 }
 
 // completion event of launch number `seq`, or null when that launch is known to have completed (its slot was taken over)
@@ -235,17 +192,7 @@ static int flush_locked(void* out, bool dump, void* acc = nullptr, int acc_mode 
                   "xgpu: output buffer changed inside one integration (partial sums live in %p, got %p)",
                   x.acc_out, out);
     int nkt = x.nfilled * x.gkt;
-#ifdef XENG_EXPERIMENTS
-    if (x.fp6) {
-        const int nhk = x.nfilled * x.ghk;
-        if (nhk & 1)   // the last 64-sample K step is half filled: its second half must hold the value 0
-            hipLaunchKernelGGL(fp6_zero_half_kernel, dim3(x.cfg.nchan * x.nblk64), dim3(64), 0, x.stream,
-                               x.stash[x.cur], x.nblk64, x.cap_kt, nhk >> 1);
-        stream_tick(STREAM_XGPU);
-        nkt = (nhk + 1) >> 1;
-    }
-#endif
-    const int rem = (x.fp6 || x.raw) ? 0 : nkt % x.kt_stage;
+    const int rem = x.raw ? 0 : nkt % x.kt_stage;
     if (rem) {  // zero-fill the K padding of every (channel, block) row of the stash
         const int padk = x.kt_stage - rem;
         XENG_HIP(hipMemset2DAsync(x.stash[x.cur] + (size_t)nkt * KT_BYTES, (size_t)x.cap_kt * KT_BYTES, 0,
@@ -329,10 +276,6 @@ static int flush_locked(void* out, bool dump, void* acc = nullptr, int acc_mode 
         x.writers[buf] = XgpuContext::Writer{seq, si};
     }
     int slot = x.timer.begin(smm, 1);
-#ifdef XENG_EXPERIMENTS
-    if (x.fp6) hipLaunchKernelGGL(xcorr_fp6_kernel, dim3(p.nchan * p.nwg), dim3(256), 0, smm, p);
-    else
-#endif
     launch_xcorr(p, smm, x.raw, fused_grid(x.cfg.nchan, x.nfg, x.ncu), x.kloop16);
     x.timer.end(smm, slot);
     XENG_HIP(hipGetLastError());
@@ -406,14 +349,6 @@ static int kernel_locked(const void* in_dev, void* out_dev, int doDump, bool syn
         } else {
             x.gulp_ptr[x.nfilled] = (const uint8_t*)in_dev;
         }
-#ifdef XENG_EXPERIMENTS
-    } else if (x.fp6) {
-        slot = x.timer.begin(x.stream, 0);
-        const size_t l6 = (((size_t)32 * x.ninput + 1023) & ~(size_t)1023) + (size_t)x.nblk64 * 2 * F6_FRAG;
-        hipLaunchKernelGGL(corner_turn_fp6_kernel, dim3(x.cfg.nchan, x.ghk), dim3(192), l6, x.stream,
-                           (const uint8_t*)in_dev, stash, x.cfg.ntime_gulp, x.cfg.nchan, x.ninput, x.nblk64,
-                           x.cap_kt, x.nfilled * x.ghk);
-#endif
     } else if (x.ct_pitch > 0) {
         slot = x.timer.begin(x.stream, 0);
         const size_t l8 = (((size_t)16 * x.ct_pitch + 1023) & ~(size_t)1023);
@@ -567,13 +502,8 @@ static int initialize_locked(int gpu) {
         // default: fused corner turn whenever the shape allows it (whole 16-byte input chunks, gulps made
         // of whole 96-sample stages); XENG_RAW=0 keeps the two-pass path
         const char* r = getenv("XENG_RAW");
-#ifdef XENG_EXPERIMENTS
-        const char* m = getenv("XENG_MFMA");
-#else
-        const char* m = nullptr;
-#endif
         x.gulp_bytes = (size_t)x.cfg.ntime_gulp * x.cfg.nchan * x.ninput;
-        x.raw = !(m && !strcmp(m, "fp6")) && !(r && !strcmp(r, "0")) && x.ninput % 16 == 0 &&
+        x.raw = !(r && !strcmp(r, "0")) && x.ninput % 16 == 0 &&
                 x.cfg.ntime_gulp % (XC_KT * 32) == 0 && x.gulp_bytes + (size_t)16 * x.cfg.nchan * x.ninput < (1ull << 32) &&
                 // (the kernel's per-lane LDS-DMA offsets subtract the instruction's immediate, up to 3072 bytes, from
                 // n * 8 rows: they stay non-negative -- the VGPR offset is unsigned -- only for rows of at least 128 bytes)
@@ -602,18 +532,6 @@ static int initialize_locked(int gpu) {
         while (((pitch / 4) & 63) != 8) pitch += 16;
         if ((size_t)16 * pitch + 1024 <= 64 * 1024) x.ct_pitch = pitch;
     }
-#ifdef XENG_EXPERIMENTS
-    {
-        const char* m = getenv("XENG_MFMA");
-        const size_t l6 = (((size_t)32 * x.ninput + 1023) & ~(size_t)1023) + (size_t)x.nblk64 * 2 * F6_FRAG;
-        x.fp6 = m && !strcmp(m, "fp6") && x.ninput % 16 == 0 && l6 <= 64 * 1024;
-        if (x.fp6) {
-            x.ghk = (x.cfg.ntime_gulp + 31) / 32;
-            x.cap_kt = (cap * x.ghk + 1) / 2;                       // 64-sample K steps
-            x.stash_bytes = (size_t)x.cfg.nchan * x.nblk64 * x.cap_kt * F6_KT_BYTES;
-        }
-    }
-#endif
     if (x.raw) x.stash_bytes = (size_t)cap * x.gulp_bytes;   // raw copies of synchronously handed gulps
 
     for (int b = 0; b < 2; b++) {
@@ -1099,7 +1017,7 @@ int xengXgpuGetPath(int* fused_corner_turn, int* fp6) {
     XgpuContext& x = g_ctx;
     if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "xgpu: not initialized");
     if (fused_corner_turn) *fused_corner_turn = x.raw ? 1 : 0;
-    if (fp6) *fp6 = x.fp6 ? 1 : 0;
+    if (fp6) *fp6 = 0;                     // (the FP6 route was removed)
     return XENG_STATUS_SUCCESS;
 }
 

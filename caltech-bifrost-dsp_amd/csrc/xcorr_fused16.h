@@ -29,13 +29,6 @@
 // Not covered here (the four-wave kernel stays for it): the long accumulator in the epilogue (CorrAcc's opt-in fused mode).
 #pragma once
 
-#ifndef XF16_SCHED
-#define XF16_SCHED 1          // 1: 2-2-2-3 VALU pinned behind the MFMAs; 2: the compiler's order; 3: reads, MFMA burst, then the unpack (A/B builds)
-#endif
-#ifndef XF16_PRIO
-#define XF16_PRIO 0           // 1: the wave raises its issue priority for the MFMAs of a K-tile (A/B builds)
-#endif
-
 // sub-cell accumulators (i, j) -> idx 2 i + j of one 32x32 cell, 16x16 MFMA layout (column = lane & 15, row = 4 (lane >> 4) + reg)
 // into the 32x32 MFMA layout (column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)): register 4 k + r of lane
 // (C, h) is row 8 k + 4 h + r -- sub-cell (k >> 1, C >> 4), lane group 2 (k & 1) + h, register r.  With A, B = register r of
@@ -58,7 +51,7 @@ __device__ __forceinline__ v16i xcorr_sub16_to_cell32(const v4i (&sub)[4]) {
 
 // DESC: gulps by descriptor (GulpDesc in device memory, slab.h: a gulp may be a slab of F-engine packets read where it lies) -- base
 // and strides per gulp, read with scalar loads when the gulp's first stage is set up.
-template <int ABL, bool DESC = false>
+template <bool DESC = false>
 __global__ __launch_bounds__(512, 1) void xcorr_fused16_kernel(XcorrParams p) {
     constexpr int SLOT_BYTES = XC_KT * KT_BYTES;       // 96 rows x 64 B: one 64-input block of a stage
     constexpr int STAGE_BYTES = XC_NSLOT * SLOT_BYTES; // 24 KiB
@@ -236,9 +229,6 @@ __global__ __launch_bounds__(512, 1) void xcorr_fused16_kernel(XcorrParams p) {
         // the 32 MFMAs of one K-tile: per sub-cell R += xr*yr + xi*yi, P += xi*yr, Q += xr*yi (no negated operand: -(-8) x 16 overflows)
         auto mfma_tile = [&](const Ops& o, auto patc) {
             constexpr int PAT = decltype(patc)::value;
-#if XF16_PRIO
-            __builtin_amdgcn_s_setprio(2);
-#endif
             constexpr int RA[3][2] = {{0, 0}, {0, 1}, {0, 0}}, CB[3][2] = {{1, 2}, {0, 2}, {1, 0}};      // fragment of the cell's rows / columns
 #pragma unroll
             for (int cc = 0; cc < 2; cc++)
@@ -252,12 +242,8 @@ __global__ __launch_bounds__(512, 1) void xcorr_fused16_kernel(XcorrParams p) {
                         accQ[q] = __builtin_amdgcn_mfma_i32_16x16x64_i8(o.r[x], o.i[y], accQ[q], 0, 0, 0);
                         accR[q] = __builtin_amdgcn_mfma_i32_16x16x64_i8(o.i[x], o.i[y], accR[q], 0, 0, 0);
                     }
-#if XF16_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
         };
         auto pin = [&]() {
-#if XF16_SCHED == 1
 #pragma unroll
             for (int i = 0; i < 32; i++) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                   // MFMA
@@ -265,11 +251,6 @@ __global__ __launch_bounds__(512, 1) void xcorr_fused16_kernel(XcorrParams p) {
                 if ((i & 3) == 3) __builtin_amdgcn_sched_group_barrier(0x002, 3, 0); // VALU 2-2-2-3
                 else __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
             }
-#elif XF16_SCHED == 3
-            __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);                      // the reads of the next K-tile
-            __builtin_amdgcn_sched_group_barrier(0x008, 32, 0);                      // this K-tile's MFMAs back to back (the SIMD's other wave unpacks meanwhile)
-            __builtin_amdgcn_sched_group_barrier(0x002, 80, 0);                      // then the unpack
-#endif
         };
 
         auto kloop = [&](auto patc) {
@@ -348,27 +329,21 @@ __global__ __launch_bounds__(512, 1) void xcorr_fused16_kernel(XcorrParams p) {
 #pragma unroll
         for (int q = 0; q < 2; q++) fast = fast && row[q] > col[q] && row[q] * 32 + 32 <= 2 * p.nstand;
         fast = __builtin_amdgcn_readfirstlane((int)fast) != 0;
-        if (ABL & 16) {       // timing only: no epilogue (keep the accumulators live)
+        v16i eR[2][2], eP[2][2], eQ[2][2];
 #pragma unroll
-            for (int q = 0; q < 8; q++) asm volatile("" :: "v"(accR[q][0]), "v"(accP[q][1]), "v"(accQ[q][2]));
-            stores_in_flight = 0;
-        } else {
-            v16i eR[2][2], eP[2][2], eQ[2][2];
-#pragma unroll
-            for (int n = 0; n < 2; n++) {
-                const v4i sr[4] = {accR[4 * n], accR[4 * n + 1], accR[4 * n + 2], accR[4 * n + 3]};
-                const v4i sp[4] = {accP[4 * n], accP[4 * n + 1], accP[4 * n + 2], accP[4 * n + 3]};
-                const v4i sq[4] = {accQ[4 * n], accQ[4 * n + 1], accQ[4 * n + 2], accQ[4 * n + 3]};
-                eR[0][n] = xcorr_sub16_to_cell32(sr);
-                eP[0][n] = xcorr_sub16_to_cell32(sp);
-                eQ[0][n] = xcorr_sub16_to_cell32(sq);
-                eR[1][n] = eP[1][n] = eQ[1][n] = (v16i)(0);
-            }
-            int lane_e = lane;                  // (laundered: the epilogue's per-lane constants are not to be hoisted into the K loop's registers)
-            asm volatile("" : "+v"(lane_e));
-            xcorr_store_cells<false, 1>(p, c, row, col, live, fast, p.accumulate != 0, lane_e, eR, eP, eQ);
-            stores_in_flight = fast ? 1 : 0;
+        for (int n = 0; n < 2; n++) {
+            const v4i sr[4] = {accR[4 * n], accR[4 * n + 1], accR[4 * n + 2], accR[4 * n + 3]};
+            const v4i sp[4] = {accP[4 * n], accP[4 * n + 1], accP[4 * n + 2], accP[4 * n + 3]};
+            const v4i sq[4] = {accQ[4 * n], accQ[4 * n + 1], accQ[4 * n + 2], accQ[4 * n + 3]};
+            eR[0][n] = xcorr_sub16_to_cell32(sr);
+            eP[0][n] = xcorr_sub16_to_cell32(sp);
+            eQ[0][n] = xcorr_sub16_to_cell32(sq);
+            eR[1][n] = eP[1][n] = eQ[1][n] = (v16i)(0);
         }
+        int lane_e = lane;                  // (laundered: the epilogue's per-lane constants are not to be hoisted into the K loop's registers)
+        asm volatile("" : "+v"(lane_e));
+        xcorr_store_cells<false, 1>(p, c, row, col, live, fast, p.accumulate != 0, lane_e, eR, eP, eQ);
+        stores_in_flight = fast ? 1 : 0;
         if (p.stamps && lane == 0 && m == 0) p.stamps[((size_t)(c * p.nwg + wg) * 4 + (wave >> 1)) * 8 + 5] = __builtin_amdgcn_s_memrealtime();
     }
     wait_vmcnt<0>();   // no LDS-DMA may still be in flight when the wave ends

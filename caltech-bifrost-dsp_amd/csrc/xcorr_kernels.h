@@ -21,7 +21,6 @@
 //          v_mfma_i32_32x32x32_i8, so the contraction kernel moves it HBM -> LDS with
 //          linear global_load_lds_dwordx4 and LDS -> VGPR with conflict-free ds_read_b128.
 //            xcorr_mfma_kernel      (int8 MFMA, one work-group per (channel, tile group))
-//          (also: xcorr_fp6_kernel + corner_turn_fp6_kernel, the opt-in FP6 experiment)
 //
 // Common to the contraction kernels:
 //     Nibbles are sign-extended "for free": (x & 0xF0F0F0F0) is 16*re as int8,
@@ -228,31 +227,9 @@ __device__ __forceinline__ Frags unpack_frags(const RawFrags& r) {
     return u;
 }
 
-// A/B (diagnostic builds, ABL & 256; results are wrong): operands as an offset-binary decode would supply them -- x ^ 0x88 read as
-// unsigned nibbles 0..15, same two VALU ops per operand dword -- to measure what smaller, sign-free operands are worth at the
-// power cap before anybody builds the row-sum corrections they would need (round-3 review, item 3)
-__device__ __forceinline__ Frags unpack_frags_offset_binary(const RawFrags& r) {
-    const v4i M = (v4i)(0x0F0F0F0F), X = (v4i)(0x88888888u);
-    Frags u;
-#pragma unroll
-    for (int m = 0; m < 2; m++) {
-        const v4i a = r.a[m] ^ X, b = r.b[m] ^ X;     // (one more VALU op than the real thing would need: the XOR could be folded into the ingest)
-        u.ar[m] = (a >> 4) & M;
-        u.ai[m] = a & M;
-        u.br[m] = (b >> 4) & M;
-        u.bi[m] = b & M;
-    }
-    return u;
-}
-
 constexpr int XC_KT = 3;      // K-tiles (32 samples each) per LDS stage
 constexpr int XC_RING = 4;    // LDS ring depth (stages), two-pass kernel
-#ifndef XF_NO_RELAX
-#define XF_NO_RELAX 0         // 1: A/B build without the relaxed first-stage wait behind an epilogue
-#endif
-#ifndef XF_DEPTH
-#define XF_DEPTH 3            // fused kernel: stages of LDS-DMA in flight ahead of the MFMAs (ring = XF_DEPTH+1 stages of 24 KiB; 3, 4, 5 measure the same)
-#endif
+constexpr int XF_DEPTH = 3;   // fused kernel: stages of LDS-DMA in flight ahead of the MFMAs (ring = XF_DEPTH+1 stages of 24 KiB; 3, 4, 5 measured the same)
 
 // ---- epilogue shared by both contraction kernels: D[i][j] = sum x_i conj(x_j), lane = column j,
 // register = row i.  MFMA C/D map (32x32): col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
@@ -393,10 +370,7 @@ __device__ __forceinline__ void xcorr_mfma_tile(const Frags& u, bool skip01, v16
 // =======================================================================================
 // Two-pass path, pass 2: operands come from the fragment-major staging area written by the corner turn.
 // One work-group per (channel, tile group).
-// ABL: timing-only ablation bits (results are wrong unless ABL == 0): 1 no LDS-DMA in the loop,
-// 2 no nibble unpack, 4 no LDS reads in the loop, 8 no barrier/vmcnt wait in the loop.
 // =======================================================================================
-template <int ABL>
 __global__ __launch_bounds__(256, 1) void xcorr_mfma_kernel(XcorrParams p) {
     constexpr int KT_STAGE = XC_KT;
     constexpr int SLOT_BYTES = KT_STAGE * KT_BYTES;
@@ -498,21 +472,13 @@ __global__ __launch_bounds__(256, 1) void xcorr_mfma_kernel(XcorrParams p) {
     for (int s = 0; s < nstage; s++) {
 #pragma unroll
         for (int j = 0; j < KT_STAGE; j++) {
-            if (!(ABL & 1)) {
-                issue_piece(s + 3, 2 * j);
-                issue_piece(s + 3, 2 * j + 1);
-            }
+            issue_piece(s + 3, 2 * j);
+            issue_piece(s + 3, 2 * j + 1);
             xcorr_mfma_tile(cur, skip01, accR, accP, accQ);
-            if (ABL & 2) {
-#pragma unroll
-                for (int m = 0; m < 2; m++) { cur.ar[m] = raw.a[m]; cur.ai[m] = raw.a[m]; cur.br[m] = raw.b[m]; cur.bi[m] = raw.b[m]; }
-            } else {
-                cur = unpack_frags(raw);
-            }
+            cur = unpack_frags(raw);
             // K-tile g+2: same stage for j < KT_STAGE-2, else the next stage (already visible; past the
             // end of K the read lands in a valid ring buffer and is never used)
-            if (!(ABL & 4)) raw = (j + 2 < KT_STAGE) ? load_raw(s, j + 2) : load_raw(s + 1, j + 2 - KT_STAGE);
-            else { asm volatile("" : "+v"(raw.a[0]), "+v"(raw.a[1]), "+v"(raw.b[0]), "+v"(raw.b[1])); }
+            raw = (j + 2 < KT_STAGE) ? load_raw(s, j + 2) : load_raw(s + 1, j + 2 - KT_STAGE);
             // pin the interleave: 1 MFMA : 3 VALU (the 48 mask/shift ops of the next K-tile hide under
             // the 16 MFMAs of this one), the two DMA pieces early, the four LDS reads in the second half
 #pragma unroll
@@ -523,10 +489,8 @@ __global__ __launch_bounds__(256, 1) void xcorr_mfma_kernel(XcorrParams p) {
                 if (i >= 8 && i < 12) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
             }
         }
-        if (!(ABL & 8)) {
-            if (!(ABL & 1)) wait_vmcnt<NLOAD>();
-            __builtin_amdgcn_s_barrier();
-        }
+        wait_vmcnt<NLOAD>();
+        __builtin_amdgcn_s_barrier();
     }
     wait_vmcnt<0>();   // no LDS-DMA may still be in flight when the wave ends
     if (p.stamps) {
@@ -576,12 +540,9 @@ __global__ __launch_bounds__(256, 1) void xcorr_mfma_kernel(XcorrParams p) {
 // the 16 (12 when cell 1 is dead) int8 MFMAs of one K-tile: for every cell R += xr*yr + xi*yi, P += xi*yr, Q += xr*yi.
 // Operands: u.a = fragments 0, 1; u.b = fragments 2, 3 of the wave (FragGroup).  Unpacked fragments are the same thing
 // whether they enter as A or B operand, so the Z wiring multiplies a diagonal fragment with itself.
-// skipdiag (diagnostic builds, ABL & 128; results are wrong): the two diagonal cells of a Z wave sit this K-tile out.  Done on every
-// fourth K-tile it takes away a quarter of their MFMA work -- what 16x16x64 MFMAs on the three needed sub-cells would save --
-// without building that data path: an upper bound of the lever (round-3 review, item 3).
 template <bool Z>
 __device__ __forceinline__ void xcorr_mfma_cells(const Frags& u, bool skip1, v16i (&accR)[2][2], v16i (&accP)[2][2],
-                                                 v16i (&accQ)[2][2], bool skipdiag = false) {
+                                                 v16i (&accQ)[2][2]) {
     auto cell = [&](int m, int n, const v4i& xr, const v4i& xi, const v4i& yr, const v4i& yi) {
         accR[m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xr, yr, accR[m][n], 0, 0, 0);
         accP[m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xi, yr, accP[m][n], 0, 0, 0);
@@ -589,10 +550,10 @@ __device__ __forceinline__ void xcorr_mfma_cells(const Frags& u, bool skip1, v16
         accR[m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xi, yi, accR[m][n], 0, 0, 0);
     };
     if (Z) {
-        if (!skipdiag) cell(0, 0, u.ar[0], u.ai[0], u.ar[0], u.ai[0]);  // (d0, d0)
+        cell(0, 0, u.ar[0], u.ai[0], u.ar[0], u.ai[0]);                 // (d0, d0)
         if (!skip1) cell(0, 1, u.br[0], u.bi[0], u.br[1], u.bi[1]);     // the free cell (r, c)
         cell(1, 0, u.ar[1], u.ai[1], u.ar[0], u.ai[0]);                 // (d1, d0)
-        if (!skipdiag) cell(1, 1, u.ar[1], u.ai[1], u.ar[1], u.ai[1]);  // (d1, d1)
+        cell(1, 1, u.ar[1], u.ai[1], u.ar[1], u.ai[1]);                 // (d1, d1)
     } else {
         cell(0, 0, u.ar[0], u.ai[0], u.br[0], u.bi[0]);
         if (!skip1) cell(0, 1, u.ar[0], u.ai[0], u.br[1], u.bi[1]);
@@ -604,7 +565,7 @@ __device__ __forceinline__ void xcorr_mfma_cells(const Frags& u, bool skip1, v16
 // Epilogue of the fragment-tiled kernel: accumulator (m, n) is cell p = 2m + n with rows = inputs 32*row[p].., columns =
 // inputs 32*col[p].. (wave-uniform).  Same register-tile order, lane regrouping and masks as xcorr_store_tile.
 // fast: all four cells live, strictly below the diagonal, no padded inputs, nothing to add to -- exactly 32 stores.
-// MR: accumulator rows m in use (2: all four cells; 1: cells 0 and 1 only -- the two-cell wave tiles of experiments/xcorr_fused16.h)
+// MR: accumulator rows m in use (2: all four cells; 1: cells 0 and 1 only -- the two-cell wave tiles of xcorr_fused16.h)
 template <bool LACC, int MR = 2>
 __device__ __forceinline__ void xcorr_store_cells(const XcorrParams& p, int c, const int (&row)[4], const int (&col)[4],
                                                   int live, bool fast, bool accumulate, int lane, const v16i (&accR)[2][2],
@@ -705,9 +666,6 @@ __device__ __forceinline__ void xcorr_store_cells(const XcorrParams& p, int c, c
         }
 }
 
-// ABL: timing-only ablation bits as for xcorr_mfma_kernel (diagnostic builds; results are wrong unless 0);
-// 16: no epilogue, 32: every channel reads a 1 MB window of gulp 0 that stays in L2, 64: half-item skew between the two
-// channels of a round (an experiment: results stay right).
 // DESC: gulps by descriptor (GulpDesc above) instead of by pointer: strides are per gulp and read with scalar loads; the default
 // instantiation is untouched.
 // TAB (round 5; a third instantiation, the DESC one is what it was): every gulp of the launch is read through its offset TABLE
@@ -719,17 +677,13 @@ __device__ __forceinline__ void xcorr_store_cells(const XcorrParams& p, int c, c
 //   * when the pieces of a stage have landed, lanes whose sample nobody carries overwrite their 16 bytes with zeros (a flag word in
 //     the same row, read when the stage begins; a wave-uniform branch per stage when nothing is missing).
 // Every stage costs NVM = 7 operations on the vmcnt counter instead of 6.
-template <int ABL, bool LACC = false, bool DESC = false, bool TAB = false>
+template <bool LACC = false, bool DESC = false, bool TAB = false>
 __global__ __launch_bounds__(256, 1) void xcorr_fused_kernel(XcorrParams p) {
     constexpr int KT_STAGE = XC_KT;
     constexpr int SLOT_BYTES = KT_STAGE * KT_BYTES;
     constexpr int STAGE_BYTES = XC_NSLOT * SLOT_BYTES;
     constexpr int NLOAD = 2 * KT_STAGE;  // 1 KiB LDS-DMA pieces per wave per stage
-#ifndef XT_EXPERIMENT
-#define XT_EXPERIMENT 0       // timing-only A/B builds of the TAB path (results wrong): 1 no hole flags / fix, 2 no table fetch in the loop, 3 both
-                              // (profiles/r05/slab_tables_ablation.txt: the fetch costs ~3 %, the flags ~1-2 %, everything else nothing)
-#endif
-    constexpr int NVM = NLOAD + ((TAB && !(XT_EXPERIMENT & 2)) ? 1 : 0);    // vector-memory operations per wave and stage (TAB: + the table rows)
+    constexpr int NVM = NLOAD + (TAB ? 1 : 0);    // vector-memory operations per wave and stage (TAB: + the table rows)
     constexpr int DEPTH = XF_DEPTH;          // the LDS-DMA of stage S+DEPTH is issued while stage S is contracted
     constexpr int RING = DEPTH + 1;          // LDS ring (stages)
     static_assert(!TAB || (DESC && DEPTH == 3), "the table ring (flags of S+2, offsets of S+3 and S+4, S+5 landed, S+6 in flight) assumes DEPTH 3");
@@ -828,11 +782,9 @@ __global__ __launch_bounds__(256, 1) void xcorr_fused_kernel(XcorrParams p) {
             // the previous gulp's last stage was, whose pieces are still to be issued with the old offsets)
             if (is_sl == 0 && is_g > 0) load_desc(is_g);
             is_stage = d_base + (size_t)(is_sl * (KT_STAGE * 32)) * d_t + (size_t)is_c * d_c;
+        } else {
+            is_stage = p.gulps[is_g] + ((size_t)(is_sl * (KT_STAGE * 32)) * p.nchan + is_c) * (size_t)p.ninput;
         }
-        else if (ABL & 32)   // timing only: every channel reads channel (c & 7)'s first stage of gulp 0 (a 1 MB window that stays in L2)
-            is_stage = p.gulps[0] + (size_t)(is_c & 7) * (size_t)p.ninput;
-        else
-        is_stage = p.gulps[is_g] + ((size_t)(is_sl * (KT_STAGE * 32)) * p.nchan + is_c) * (size_t)p.ninput;
         is_issued++;
         if (++is_sl == p.spg) { is_sl = 0; is_g++; }
     };
@@ -897,13 +849,6 @@ __global__ __launch_bounds__(256, 1) void xcorr_fused_kernel(XcorrParams p) {
 
     Item it;
     if (!item(0, it)) return;                // (the host never launches work-groups without work)
-    if (ABL & 64) {   // timing only: the second channel of every round (work-groups 16-31 of an XCD) starts half an item late,
-                      // so that the two channels' epilogue bursts do not coincide
-        if ((blockIdx.x >> 3) & 16) {
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            while (__builtin_amdgcn_s_memrealtime() - t0 < 1500ull) __builtin_amdgcn_s_sleep(32);     // 15 us at 100 MHz
-        }
-    }
     is_setup(it);
     if (TAB) {
         // table rows of stages 0-5, then the pieces of stages 0-2 from them
@@ -951,8 +896,8 @@ __global__ __launch_bounds__(256, 1) void xcorr_fused_kernel(XcorrParams p) {
         next_stage();
         if (TAB) {
             sb_q2 = nx_sb;
-            if (!(ABL & 1) && !(XT_EXPERIMENT & 2)) issue_table((q + 6) & 7);
-            if (!(XT_EXPERIMENT & 1)) load_flags((q + 2) & 7);
+            issue_table((q + 6) & 7);
+            load_flags((q + 2) & 7);
         }
     };
     // TAB, once the last piece of the stage has been issued: the offsets of the pieces that the NEXT stage issues (their rows landed
@@ -962,18 +907,16 @@ __global__ __launch_bounds__(256, 1) void xcorr_fused_kernel(XcorrParams p) {
     };
     // ... and ends with: this wave's pieces of stage S+2 (and everything older) have landed; TAB: zeros for its missing samples; one barrier
     auto stage_end = [&](bool relaxed) {
-        if (!(ABL & 8)) {
-            // (first stage behind a straight-line epilogue: the 32 tile stores of that epilogue sit between the DMA of
-            // stage S+2, which this wait is for, and the pieces just issued; vmcnt retires in issue order, so
-            // allowing them to stay in flight does not let stage S+2 slip -- and the wave does not stall for the
-            // write acknowledgements of the previous item)
-            if (!(ABL & 1)) { if (relaxed && !XF_NO_RELAX) wait_vmcnt<(DEPTH - 2) * NVM + 32>(); else wait_vmcnt<(DEPTH - 2) * NVM>(); }
-            if (TAB) {
-                if (!(XT_EXPERIMENT & 1)) fix_holes(rs1 + 1 == RING ? 0 : rs1 + 1);
-                q = (q + 1) & 7;
-            }
-            __builtin_amdgcn_s_barrier();
+        // (first stage behind a straight-line epilogue: the 32 tile stores of that epilogue sit between the DMA of
+        // stage S+2, which this wait is for, and the pieces just issued; vmcnt retires in issue order, so
+        // allowing them to stay in flight does not let stage S+2 slip -- and the wave does not stall for the
+        // write acknowledgements of the previous item)
+        if (relaxed) wait_vmcnt<(DEPTH - 2) * NVM + 32>(); else wait_vmcnt<(DEPTH - 2) * NVM>();
+        if (TAB) {
+            fix_holes(rs1 + 1 == RING ? 0 : rs1 + 1);
+            q = (q + 1) & 7;
         }
+        __builtin_amdgcn_s_barrier();
         bump(rs); bump(rs1); bump(rf);
     };
     bool stores_in_flight = false;            // the previous item of this wave ended with the 32-store epilogue
@@ -986,10 +929,8 @@ __global__ __launch_bounds__(256, 1) void xcorr_fused_kernel(XcorrParams p) {
             // kernel is power-limited).  Nothing is live across this branch.
             for (int s = 0; s < p.nstage; s++) {
                 stage_begin();
-                if (!(ABL & 1)) {
 #pragma unroll
-                    for (int n = 0; n < NLOAD; n++) issue_piece(rf, n);
-                }
+                for (int n = 0; n < NLOAD; n++) issue_piece(rf, n);
                 stage_offsets();
                 stage_end(false);
             }
@@ -1059,24 +1000,14 @@ __global__ __launch_bounds__(256, 1) void xcorr_fused_kernel(XcorrParams p) {
                 stage_begin();
 #pragma unroll
                 for (int j = 0; j < KT_STAGE; j++) {
-                    if (!(ABL & 1)) {
-                        issue_piece(rf, 2 * j);
-                        issue_piece(rf, 2 * j + 1);
-                    }
+                    issue_piece(rf, 2 * j);
+                    issue_piece(rf, 2 * j + 1);
                     if (j == KT_STAGE - 1) stage_offsets();
-                    xcorr_mfma_cells<Z>(cur, skip1, accR, accP, accQ, (ABL & 128) && Z && ((s * KT_STAGE + j) & 3) == 3);
-                    if (ABL & 256) {
-                        cur = unpack_frags_offset_binary(raw);
-                    } else if (ABL & 2) {
-#pragma unroll
-                        for (int m = 0; m < 2; m++) { cur.ar[m] = raw.a[m]; cur.ai[m] = raw.a[m]; cur.br[m] = raw.b[m]; cur.bi[m] = raw.b[m]; }
-                    } else {
-                        cur = unpack_frags(raw);
-                    }
+                    xcorr_mfma_cells<Z>(cur, skip1, accR, accP, accQ);
+                    cur = unpack_frags(raw);
                     // K-tile g+2: same stage for j < KT_STAGE-2, else the next stage (already visible; at the end
                     // of an item the read lands in a valid ring buffer and is not used)
-                    if (!(ABL & 4)) raw = (j + 2 < KT_STAGE) ? load_raw(rs, j + 2) : load_raw(rs1, j + 2 - KT_STAGE);
-                    else { asm volatile("" : "+v"(raw.a[0]), "+v"(raw.a[1]), "+v"(raw.b[0]), "+v"(raw.b[1])); }
+                    raw = (j + 2 < KT_STAGE) ? load_raw(rs, j + 2) : load_raw(rs1, j + 2 - KT_STAGE);
                     // pin the interleave: 1 MFMA : 3 VALU (the 48 mask/shift ops of the next K-tile hide under the
                     // 16 MFMAs of this one), the eight transposing LDS reads in the second half
 #pragma unroll
@@ -1104,13 +1035,7 @@ __global__ __launch_bounds__(256, 1) void xcorr_fused_kernel(XcorrParams p) {
 #pragma unroll
         for (int q = 0; q < 4; q++) fast = fast && row[q] > col[q] && row[q] * 32 + 32 <= 2 * p.nstand;
         fast = __builtin_amdgcn_readfirstlane((int)fast) != 0;
-        stores_in_flight = !(ABL & 16) && !LACC && fast;
-        if (ABL & 16) {   // timing only: no epilogue (keep the accumulators live)
-#pragma unroll
-            for (int m = 0; m < 2; m++)
-#pragma unroll
-                for (int n = 0; n < 2; n++) asm volatile("" :: "v"(accR[m][n][0]), "v"(accP[m][n][5]), "v"(accQ[m][n][9]));
-        } else
+        stores_in_flight = !LACC && fast;
         xcorr_store_cells<LACC>(p, c, row, col, live, fast, p.accumulate != 0, lane, accR, accP, accQ);
         if (p.stamps && lane == 0) p.stamps[((size_t)(c * p.nwg + wg) * 4 + wave) * 8 + 5] = __builtin_amdgcn_s_memrealtime();
     }
@@ -1248,9 +1173,5 @@ __global__ __launch_bounds__(256) void packetize_kernel(const int32_t* __restric
 }
 
 #include "xcorr_fused16.h"
-
-#ifdef XENG_EXPERIMENTS
-#include "experiments/xcorr_fp6.h"
-#endif
 
 }  // namespace xeng

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# XENG_LIB: load another build of the same library (the -DXENG_DIAGNOSTICS build used by profiles/: timing-only ablations)
+# XENG_LIB: load another build of the same library (the -DXENG_DIAGNOSTICS build used by profiles/: host-side diagnostic switches)
 LIB_PATH = os.environ.get("XENG_LIB") or os.path.join(_HERE, "libxeng.so")
 
 STATUS_SUCCESS = 0

@@ -280,7 +280,7 @@ int xengXgpuGetInfo(int *nstand, int *npol, int *nchan, int *ntime_gulp, int64_t
 
 /* which contraction path the current context runs: fused_corner_turn = 1 when gulps are read in place
  * (ninput % 16 == 0, ntime_gulp % 96 == 0, not disabled with XENG_RAW=0), else the two-pass path
- * (corner turn into a fragment-major staging area); fp6 = 1 for the opt-in XENG_MFMA=fp6 experiment. */
+ * (corner turn into a fragment-major staging area); fp6 is always 0 (the FP6 route was removed). */
 int xengXgpuGetPath(int *fused_corner_turn, int *fp6);
 /* the contraction kernel plain and slab launches of the current context take: 4 waves per work-group on v_mfma_i32_32x32x32_i8
  * (mfma_k 32: the default, the two-pass path, and always for dumps that feed a long accumulator) or, with XENG_KLOOP=16, 8 waves

@@ -1,6 +1,6 @@
 #!/bin/bash
-# builds profiles/_ab/libxeng_diag.so: the library with -DXENG_DIAGNOSTICS (the XENG_ABLATE / XENG_SLAB_* / XENG_MM_STREAMS
-# switches that the shipped build compiles out).  usage: bash profiles/build_diag.sh
+# builds profiles/_ab/libxeng_diag.so: the library with -DXENG_DIAGNOSTICS (the host-side XENG_GRID / XENG_MM_STREAMS / XENG_ITEM_ORDER /
+# XENG_DBG_STAMPS ... switches that the shipped build compiles out).  usage: bash profiles/build_diag.sh
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 B=${TMPDIR:-/tmp}/diagbuild

@@ -28,10 +28,10 @@ res = {"xcorr_sources_sha256": h.hexdigest(), "xcorr_sources": srcs,
                      "WRITE_SIZE exact for 16-B-per-lane stores; separate --pmc passes (profiles/pmc_run.sh)"}
 for k, d in agg.items():
     if ("xcorr_" in k or "fused_kernel<" in k) and "FETCH_SIZE" in d and "WRITE_SIZE" in d:
-        if "fused_kernel<" in k:      # template arguments <ABL, LACC, DESC, TAB>: long accumulation in the epilogue; gulps by descriptor (packet slabs); through offset tables
+        if "fused_kernel<" in k:      # template arguments <LACC, DESC, TAB>: long accumulation in the epilogue; gulps by descriptor (packet slabs); through offset tables
             targs = [a.strip() for a in k[k.index("<") + 1:k.rindex(">")].split(",")]
-            name = ("xcorr_fused_kernel" + ("_lacc" if targs[1] == "true" else "") + ("_slabs" if len(targs) > 2 and targs[2] == "true" else "") +
-                    ("_tables" if len(targs) > 3 and targs[3] == "true" else ""))
+            name = ("xcorr_fused_kernel" + ("_lacc" if targs[0] == "true" else "") + ("_slabs" if len(targs) > 1 and targs[1] == "true" else "") +
+                    ("_tables" if len(targs) > 2 and targs[2] == "true" else ""))
         else:
             name = k.strip()
         f, w = d["FETCH_SIZE"][0] / d["FETCH_SIZE"][1], d["WRITE_SIZE"][0] / d["WRITE_SIZE"][1]
