@@ -219,6 +219,34 @@ class HipBackend:
         return self._enq.xengBeamformPacketizeVoltages(in_arr.ptr, out_arr.ptr, int(nchan), int(nbeam), int(ntime), int(beam0), int(nbeam_pkt),
                                                        int(pkt_stride), int(server), int(gbe), int(nbeam_hdr), int(nserver), int(chan0), int(seq0))
 
+    # ---- upchannelising beamformer (UpchanBeamform; include/xeng.h "Upchannelising beamformer"): a context of its own, its
+    # kernel on the beamformer's stream
+    def upchan_initialize(self, gpu, ninput, nchan, ntime, nupchan, nbeam, nframe_sum):
+        return self._lib.xengUpchanInitialize(int(gpu), int(ninput), int(nchan), int(ntime), int(nupchan), int(nbeam), int(nframe_sum))
+
+    def upchan_run(self, in_arr, out_arr, weights, version=0):
+        """Enqueue only: upchan_mark / upchan_wait cover it."""
+        return self._enq.xengUpchanRun(in_arr.ptr, out_arr.ptr, weights.ptr, int(version))
+
+    def upchan_run_parts(self, part0, ntime0, part1, out_arr, weights, version=0):
+        """One gulp out of two consecutive spans of the input ring (samples [0, ntime0) in part0), one launch, no gathered copy."""
+        return self._enq.xengUpchanRunParts(part0.ptr, int(ntime0), part1.ptr, out_arr.ptr, weights.ptr, int(version))
+
+    def upchan_mark(self):
+        t = ctypes.c_ulonglong()
+        ffi.check("xengUpchanMark", self._enq.xengUpchanMark(ctypes.byref(t)))
+        return t.value
+
+    def upchan_wait(self, ticket):
+        # ask first, without giving up the interpreter lock; only a ticket the GPU has not reached yet is worth a blocking call
+        d = ctypes.c_int()
+        ffi.check("xengUpchanTicketDone", self._enq.xengUpchanTicketDone(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
+        if not d.value:
+            ffi.call("xengUpchanWait", ctypes.c_ulonglong(ticket))
+
+    def upchan_sync(self):
+        ffi.call("xengUpchanSync")
+
     def last_error(self):
         return self._lib.xengGetLastError().decode()
 

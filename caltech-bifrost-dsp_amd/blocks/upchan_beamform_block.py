@@ -1,0 +1,246 @@
+"""UpchanBeamform: fine-channel beams from 4+4-bit F-engine data, FFT and beamforming fused in one HIP kernel.
+
+Counterpart of the reference's upchannelising beamformer, pipeline/scripts/lwa352-upchan-bf.py:94-113 with
+pipeline/lwa352_pipeline/blocks/beamform_offline_block.py (weights :110-138, per-gulp work :211-245): each coarse channel is
+split into `nupchan` fine channels by an FFT over `nupchan` consecutive samples (one "frame"), weighted per fine channel and
+summed over inputs (xengUpchanRun, csrc/upchan_kernels.h; the channelised data never reaches device memory).
+
+Where it differs from the reference: the block takes Beamform's `coeffs` commands (delays in ns, amplitudes,
+timed `load_sample`) instead of pointing from RA/Dec, with calibration at fine resolution; the amplitude multiplies the
+weight (the reference scales the delay by it, :137); every beam is formed (the reference's TODO at :214-215); the power mode
+writes |v|^2 summed over frames (the reference's output writes np.abs(v)).
+
+Input: u8 [ntime_gulp][nchan][ninput] spans (the Beamform input).  Output per gulp:
+  nframe_sum = 0: cf32 [nframe][nbeam][nchan][nupchan]          (nframe = ntime_gulp / nupchan)
+  nframe_sum > 0: f32  [nframe / nframe_sum][nbeam][nchan][nupchan]
+Fine channel j of coarse channel c is centred at sfreq + c*d + (j - nupchan/2)*d/nupchan, d = bw_hz / nchan.
+"""
+import collections
+import json
+import time
+
+import numpy as np
+
+from ..backend import default_backend
+from ..ndarray import XArray
+from ..proclog import cpu_affinity
+from .block_base import Block, COMMAND_INVALID, COMMAND_OK, declare_streams
+
+
+class UpchanBeamform(Block):
+    STREAM_DEPTH = 4        # gulps whose kernels may be in flight behind the one being enqueued (in-repo rings)
+
+    def __init__(self, log, iring, oring, nchan=256, nbeam=1, ninput=352 * 2, ntime_gulp=2500, nupchan=32, nframe_sum=0,
+                 guarantee=True, core=-1, gpu=-1, etcd_client=None, backend=None):
+        super(UpchanBeamform, self).__init__(log, iring, oring, guarantee, core, etcd_client=etcd_client)
+        self._bf = backend if backend is not None else default_backend()
+        self.nchan, self.nbeam, self.ninput, self.ntime_gulp = nchan, nbeam, ninput, ntime_gulp
+        self.nupchan, self.nframe_sum, self.gpu = nupchan, nframe_sum, gpu
+        if ntime_gulp % nupchan or (nframe_sum and (ntime_gulp // nupchan) % nframe_sum):
+            raise ValueError("UPCHAN: gulps of %d samples are not whole frames of %d (or windows of %d frames)" % (ntime_gulp, nupchan, nframe_sum))
+        self.nframe = ntime_gulp // nupchan
+        declare_streams(iring, 'beam')          # (the kernel runs on the beamformer's stream)
+        declare_streams(oring, 'beam')
+        if self.gpu != -1:
+            self._bf.set_device(self.gpu)
+        self.freqs = np.zeros((nchan, nupchan))  # fine-channel centres, set from each sequence header
+        shape = (nchan, nupchan, nbeam, ninput)
+        # weights: latest commanded (new) -> active on the host (cpu) -> on the device (gpu), per beam at its load sample
+        self.cal_gains = np.ones(shape, dtype=np.complex64)
+        self.weights_new = np.zeros(shape, dtype=np.complex64)
+        self.weights_cpu = np.zeros(shape, dtype=np.complex64)
+        self.weights_gpu = XArray(shape=shape, dtype=np.complex64, space=self._bf.space_in)
+        self.weights_load_sample = np.zeros(nbeam)
+        self._weights_version = 0
+        self.define_command_key('coeffs', type=dict, initial_val={})
+        for b in range(nbeam):
+            self.update_stats({'cal_gains%d' % b: [False, ] * ninput})
+        rv = self._bf.upchan_initialize(self.gpu, ninput, nchan, ntime_gulp, nupchan, nbeam, nframe_sum)
+        if rv != self._bf.BF_STATUS_SUCCESS:
+            raise RuntimeError("xengUpchanInitialize returned %d: %s" % (rv, self._bf.last_error()))
+
+    def _etcd_callback(self, watchresponse):
+        """Every command is enacted as it arrives (all share the `coeffs` key, as Beamform's do)."""
+        cpu_affinity.set_core(self.core)
+        self.acquire_control_lock()
+        try:
+            for event in watchresponse.events:
+                try:
+                    seq_id, kwargs = self._parse_event(event)
+                except ValueError:
+                    self.log.exception("UPCHAN >> Failed to JSON-decode event %s" % str(event.value))
+                    self._send_command_response("0", False, "JSON-decode failed!")
+                    continue
+                if kwargs is None:
+                    continue
+                try:
+                    proc_ok = self._process_commands(kwargs, set_pending_flag=False)
+                except Exception:
+                    proc_ok = COMMAND_INVALID
+                self.update_stats({'last_cmd_response': proc_ok})
+                self.update_command_vals()
+                self._send_command_response(seq_id, proc_ok == COMMAND_OK, str(proc_ok))
+        finally:
+            self.release_control_lock()
+
+    def update_command_vals(self):
+        """`calgains`: 2 * nchan * nupchan floats (re, im interleaved, channel-major) per (beam, input).  `beamcoeffs`: the weight
+        amps * exp(2 pi i f tau 1e-9) * cal at every fine frequency f (Beamform's formula, beamform_block.py:340-342), active from
+        its `load_sample` on (-1 or absent: the next gulp)."""
+        cpu_affinity.set_core(self.core)
+        self.command_vals.update(self._pending_command_vals)
+        update_beam_cal_state = False
+        for k, v in self._pending_command_vals.items():
+            try:
+                if not v:
+                    continue
+                if v['type'] == 'calgains':
+                    i, b = v['input_id'], v['beam_id']
+                    data = np.asarray(v['data'], dtype=np.float64)
+                    if data.size != 2 * self.nchan * self.nupchan:
+                        self.log.error("UPCHAN >> calgains need %d values, got %d" % (2 * self.nchan * self.nupchan, data.size))
+                        continue
+                    self.cal_gains[:, :, b, i] = (data[0::2] + 1j * data[1::2]).reshape(self.nchan, self.nupchan)
+                    self.stats['cal_gains%d' % b][i] = True
+                    update_beam_cal_state = True
+                if v['type'] == 'beamcoeffs':
+                    b = v['beam_id']
+                    delays_ns = np.asarray(v['data']['delays'], dtype=np.float64)
+                    amps = np.asarray(v['data']['amps'], dtype=np.float64)
+                    phases = np.exp(2j * np.pi * self.freqs[:, :, None] * delays_ns[None, None, :] * 1e-9)     # chan x fine x input
+                    self.weights_new[:, :, b, :] = amps * phases * self.cal_gains[:, :, b, :]
+                    self.weights_load_sample[b] = v.get('load_sample', -1)
+                    self.update_pending = True
+            except KeyError:
+                self.log.error("UPCHAN >> Failed to parse command")
+        self.update_stats(self.command_vals)
+        if update_beam_cal_state:
+            self.update_stats({'cal_gains%d' % b: self.stats['cal_gains%d' % b] for b in range(self.nbeam)})
+
+    def _load_pending_weights(self, this_gulp_time):
+        """Weights whose load sample has come move from `new` to `cpu`; True when the device copy has to be rewritten."""
+        copy_pending = False
+        self.acquire_control_lock()
+        for b in range(self.nbeam):
+            if self.weights_load_sample[b] == 0:    # 0 = nothing pending for this beam
+                continue
+            if this_gulp_time >= self.weights_load_sample[b]:
+                self.weights_cpu[:, :, b, :] = self.weights_new[:, :, b, :]
+                self.weights_load_sample[b] = 0
+                copy_pending = True
+        if self.weights_load_sample.sum() == 0:
+            self.update_pending = False
+        self.stats['update_pending'] = self.update_pending
+        self.stats['last_cmd_proc_time'] = time.time()
+        self.release_control_lock()
+        return copy_pending
+
+    def output_header(self, ihdr):
+        chan_bw = ihdr['bw_hz'] / self.nchan
+        ohdr = ihdr.copy()
+        ohdr.update(nstand=self.nbeam, nbeam=self.nbeam, nupchan=self.nupchan, nframe_sum=self.nframe_sum, nbit=32, npol=1,
+                    fine_bw_hz=chan_bw / self.nupchan, fine_sfreq=ihdr['sfreq'] - chan_bw / 2)
+        if self.nframe_sum:
+            ohdr.pop('complex', None)
+        else:
+            ohdr['complex'] = True
+        return ohdr
+
+    def main(self):
+        cpu_affinity.set_core(self.core)
+        if self.gpu != -1:
+            self._bf.set_device(self.gpu)
+        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
+        nout = self.nframe // self.nframe_sum if self.nframe_sum else self.nframe
+        ogulp_size = nout * self.nbeam * self.nchan * self.nupchan * (4 if self.nframe_sum else 8)
+        self.oring.resize(ogulp_size)
+        # In-repo rings keep a span's memory alive while it is referenced: several gulps in flight, each output span committed
+        # when ITS kernel has completed (tickets).  A bifrost ring: wait for the kernel after every gulp.
+        streaming = (getattr(self.iring, 'span_memory_outlives_release', False) and getattr(self.oring, 'span_memory_outlives_release', False))
+        pending = collections.deque()           # (ticket, output span, input kept alive)
+
+        def retire(keep):
+            while len(pending) > keep:
+                ticket, osp, _ = pending.popleft()
+                self._bf.upchan_wait(ticket)
+                osp.close()
+        try:
+            with self.oring.begin_writing() as oring:
+                for iseq in self.iring.read(guarantee=self.guarantee):
+                    self._sequence(iseq, oring, ogulp_size, streaming, pending, retire)
+        finally:
+            if pending:         # (nothing a kernel in flight still touches is let go before the stream is idle)
+                try:
+                    self._bf.upchan_sync()
+                except Exception:
+                    pass
+                pending.clear()
+
+    def _sequence(self, iseq, oring, ogulp_size, streaming, pending, retire):
+        self.update_pending = True
+        ihdr = json.loads(iseq.header.tostring())
+        self.sequence_proclog.update(ihdr)
+        if ihdr['nchan'] != self.nchan or ihdr['nstand'] * ihdr['npol'] != self.ninput:
+            raise ValueError("UPCHAN: %d channels x %d inputs in the header, %d x %d configured" % (ihdr['nchan'], ihdr['nstand'] * ihdr['npol'],
+                                                                                                  self.nchan, self.ninput))
+        chan_bw = ihdr['bw_hz'] / self.nchan
+        self.freqs = (ihdr['sfreq'] + chan_bw * np.arange(self.nchan)[:, None]
+                      + (np.arange(self.nupchan)[None, :] - self.nupchan // 2) * chan_bw / self.nupchan)
+        seq0 = ihdr['seq0']
+        row = self.nchan * self.ninput
+        igulp_size = self.ntime_gulp * row
+        read_parts = getattr(iseq, 'read_parts', None)
+        copy_pending = True
+        this_gulp_time = seq0
+        with oring.begin_sequence(time_tag=iseq.time_tag, header=json.dumps(self.output_header(ihdr))) as oseq:
+            prev_time = time.time()
+            for ispan in (read_parts(igulp_size) if read_parts is not None else iseq.read(igulp_size)):
+                if ispan.size < igulp_size:
+                    continue                    # a short final gulp is skipped (as the reference's gulp_nframe reader does)
+                # the gulp's first sample from its place in the sequence: right after a reader skipped gulps as well
+                offset = getattr(ispan, 'offset', None)
+                if offset is not None:
+                    this_gulp_time = seq0 + (offset // igulp_size) * self.ntime_gulp
+                elif getattr(ispan, 'skipped', 0):
+                    this_gulp_time += (ispan.skipped // igulp_size) * self.ntime_gulp
+                self.update_stats({'curr_sample': this_gulp_time})
+                if self.update_pending:
+                    copy_pending = self._load_pending_weights(this_gulp_time) or copy_pending
+                if copy_pending:
+                    retire(0)                   # (kernels in flight may still read the device copy of the weights)
+                    self.weights_gpu[...] = self.weights_cpu
+                    self._weights_version += 1
+                    copy_pending = False
+                curr_time = time.time()
+                acquire_time = curr_time - prev_time
+                prev_time = curr_time
+                ospan = oseq.reserve(ogulp_size)
+                try:
+                    parts = getattr(ispan, 'parts', None)
+                    if parts is not None and len(parts) == 2:
+                        ntime0 = parts[0].nbytes // row
+                        if ntime0 % self.nupchan:
+                            raise RuntimeError("UPCHAN: a gulp split after %d samples is not whole frames of %d" % (ntime0, self.nupchan))
+                        held = parts
+                        rv = self._bf.upchan_run_parts(parts[0], ntime0, parts[1], ospan.data, self.weights_gpu, self._weights_version)
+                    else:
+                        held = ispan.data
+                        rv = self._bf.upchan_run(held, ospan.data, self.weights_gpu, self._weights_version)
+                    if rv != self._bf.BF_STATUS_SUCCESS:
+                        raise RuntimeError("xengUpchanRun returned %d: %s" % (rv, self._bf.last_error()))
+                    if streaming:
+                        pending.append((self._bf.upchan_mark(), ospan, held))
+                        ospan = None
+                        retire(self.STREAM_DEPTH)
+                    else:
+                        self._bf.upchan_sync()
+                finally:
+                    if ospan is not None:
+                        ospan.close()
+                self.update_stats({'last_end_sample': this_gulp_time})
+                this_gulp_time += self.ntime_gulp
+                curr_time = time.time()
+                process_time = curr_time - prev_time
+                prev_time = curr_time
+                self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
+            retire(0)                           # the sequence ends: every gulp in flight is committed first

@@ -1,0 +1,192 @@
+// Host side of the upchannelising beamformer (UpchanBeamform; upchan_kernels.h): a process-global context of its own, beside
+// (not inside) the Beamform context, whose kernels run on the beamformer's stream (STREAM_BEAM) and tick its clock, so that
+// rings declared 'beam' and their span stamps cover them unchanged.
+#include <mutex>
+
+#include "upchan_kernels.h"
+#include "xeng_common.h"
+
+namespace xeng {
+
+struct UpchanContext {
+    bool live = false;
+    int gpu = 0, ninput = 0, nchan = 0, ntime = 0, nupchan = 0, nbeam = 0, nframe_sum = 0;
+    hipStream_t stream = nullptr;
+    // completion tickets (as xengBeamformMark): ticket n -> marks[(n - 1) % NMARK]
+    static constexpr int NMARK = 64;
+    hipEvent_t marks[NMARK] = {};
+    unsigned long long nmarks = 0;
+};
+static std::mutex g_umu;
+static UpchanContext g_u;
+
+static int upchan_destroy_locked() {
+    if (!g_u.live) return XENG_STATUS_SUCCESS;
+    (void)hipSetDevice(g_u.gpu);
+    if (g_u.stream) (void)hipStreamSynchronize(g_u.stream);
+    stream_clocks_forget(g_u.gpu, STREAM_BEAM);          // (the mark events lent to the stream clock go away below)
+    for (int k = 0; k < UpchanContext::NMARK; k++)
+        if (g_u.marks[k]) (void)hipEventDestroy(g_u.marks[k]);
+    g_u = UpchanContext();
+    return XENG_STATUS_SUCCESS;
+}
+
+// frames per work-group: UC_FT in voltage mode; in power mode whole windows (as many as fit in UC_FT frames, or one longer one)
+static int upchan_run_frames(int nframe_sum) {
+    if (nframe_sum == 0) return UC_FT;
+    return nframe_sum <= UC_FT ? nframe_sum * (UC_FT / nframe_sum) : nframe_sum;
+}
+
+static int upchan_threads(int nbeam, int nupchan) {
+    const int units = nbeam * nupchan;
+    return units >= 256 ? 256 : (units + 63) / 64 * 64;
+}
+
+template <int N>
+static void upchan_launch_n(int ppt, dim3 grid, dim3 block, hipStream_t s, const uint8_t* in0, const uint8_t* in1, int ntime0,
+                            const float2* w, float* out, const UpchanContext& x, int nframe, int run) {
+    switch (ppt) {
+    case 1: hipLaunchKernelGGL((upchan_beamform_kernel<N, 1>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run); break;
+    case 2: hipLaunchKernelGGL((upchan_beamform_kernel<N, 2>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run); break;
+    default: hipLaunchKernelGGL((upchan_beamform_kernel<N, 4>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run); break;
+    }
+}
+
+// Every argument is checked before the context is looked at where it can be (a bad call is told apart from a missing
+// context, and nothing is launched); what depends on the context's sizes is checked right after.
+static int upchan_run(const void* in0_dev, int ntime0, const void* in1_dev, void* out_dev, const void* weights_dev) {
+    if (!in0_dev || !out_dev || !weights_dev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: null buffer");
+    if ((uintptr_t)weights_dev % 16 || (uintptr_t)out_dev % 16)
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: weights %p / output %p not 16-byte aligned", weights_dev, out_dev);
+    if (in1_dev && ntime0 <= 0) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: first part of %d samples", ntime0);
+    std::lock_guard<std::mutex> lk(g_umu);
+    UpchanContext& x = g_u;
+    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized (call xengUpchanInitialize)");
+    if (!in1_dev) { in1_dev = in0_dev; ntime0 = x.ntime; }
+    else if (ntime0 >= x.ntime || ntime0 % x.nupchan)
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: parts of %d + %d samples: both must be positive multiples of nupchan %d", ntime0,
+                  x.ntime - ntime0, x.nupchan);
+    XENG_HIP(hipSetDevice(x.gpu));
+    const int nframe = x.ntime / x.nupchan, run = upchan_run_frames(x.nframe_sum);
+    const int nthr = upchan_threads(x.nbeam, x.nupchan);
+    const int ppt = (x.nbeam * x.nupchan + nthr - 1) / nthr;
+    const dim3 grid((unsigned)(x.nchan * ((nframe + run - 1) / run))), block((unsigned)nthr);
+    const uint8_t* a = (const uint8_t*)in0_dev;
+    const uint8_t* b = (const uint8_t*)in1_dev;
+    const float2* w = (const float2*)weights_dev;
+    float* o = (float*)out_dev;
+    switch (x.nupchan) {
+    case 8: upchan_launch_n<8>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
+    case 16: upchan_launch_n<16>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
+    case 32: upchan_launch_n<32>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
+    default: upchan_launch_n<64>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
+    }
+    stream_tick(STREAM_BEAM);
+    XENG_HIP(hipGetLastError());
+    return XENG_STATUS_SUCCESS;
+}
+
+}  // namespace xeng
+
+using namespace xeng;
+
+extern "C" {
+
+int xengUpchanInitialize(int gpu, int ninput, int nchan, int ntime, int nupchan, int nbeam, int nframe_sum) {
+    if (ninput <= 0 || ninput % 4 || nchan <= 0 || ntime <= 0 || nbeam <= 0 || nframe_sum < 0)
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: bad sizes ninput=%d nchan=%d ntime=%d nbeam=%d nframe_sum=%d (inputs a multiple of 4)",
+                  ninput, nchan, ntime, nbeam, nframe_sum);
+    if (nupchan != 8 && nupchan != 16 && nupchan != 32 && nupchan != 64)
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: nupchan %d not one of 8, 16, 32, 64", nupchan);
+    if (ntime % nupchan) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: ntime %d not a multiple of nupchan %d", ntime, nupchan);
+    const int nframe = ntime / nupchan;
+    if (nframe_sum > 0 && nframe % nframe_sum)
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: nframe_sum %d does not divide the %d frames of a gulp", nframe_sum, nframe);
+    if ((long long)nbeam * nupchan > UC_MAXB)
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: nbeam %d x nupchan %d above %d", nbeam, nupchan, UC_MAXB);
+    if ((long long)nchan * nframe > 0x7FFFFFFFLL || (long long)ninput * nchan > 0x7FFFFFFFLL)
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: %d channels x %d inputs x %d frames is more than one launch takes", nchan, ninput, nframe);
+    std::lock_guard<std::mutex> lk(g_umu);
+    upchan_destroy_locked();
+    UpchanContext& x = g_u;
+    x.gpu = gpu < 0 ? 0 : gpu;
+    XENG_HIP(hipSetDevice(x.gpu));
+    int rc = get_stream(STREAM_BEAM, &x.stream);
+    if (rc) return rc;
+    x.ninput = ninput; x.nchan = nchan; x.ntime = ntime; x.nupchan = nupchan; x.nbeam = nbeam; x.nframe_sum = nframe_sum;
+    x.live = true;
+    return XENG_STATUS_SUCCESS;
+}
+
+// weights_version: the kernel reads the fp32 weights as they are (no prepared copy), so any version means "as they are now"
+int xengUpchanRun(const void* in_dev, void* out_dev, const void* weights_dev, long long weights_version) {
+    (void)weights_version;
+    return upchan_run(in_dev, 0, nullptr, out_dev, weights_dev);
+}
+
+int xengUpchanRunParts(const void* in0_dev, int ntime0, const void* in1_dev, void* out_dev, const void* weights_dev, long long weights_version) {
+    (void)weights_version;
+    if (!in1_dev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: null second part");
+    return upchan_run(in0_dev, ntime0, in1_dev, out_dev, weights_dev);
+}
+
+int xengUpchanMark(unsigned long long* ticket) {
+    if (!ticket) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanMark: null ticket");
+    std::lock_guard<std::mutex> lk(g_umu);
+    UpchanContext& x = g_u;
+    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized");
+    XENG_HIP(hipSetDevice(x.gpu));
+    hipEvent_t& ev = x.marks[x.nmarks % UpchanContext::NMARK];
+    if (!ev) XENG_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    const unsigned long long upto = stream_clock_now(STREAM_BEAM);      // (read BEFORE the record: everything counted precedes it)
+    XENG_HIP(hipEventRecord(ev, x.stream));
+    stream_clock_external_mark(STREAM_BEAM, ev, upto);
+    *ticket = ++x.nmarks;
+    return XENG_STATUS_SUCCESS;
+}
+
+int xengUpchanWait(unsigned long long ticket) {
+    hipEvent_t ev = nullptr;
+    int gpu = 0;
+    {
+        std::lock_guard<std::mutex> lk(g_umu);
+        UpchanContext& x = g_u;
+        if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized");
+        if (ticket == 0 || ticket > x.nmarks) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanWait: unknown ticket %llu", ticket);
+        gpu = x.gpu;
+        ev = x.marks[(ticket - 1) % UpchanContext::NMARK];      // (a re-recorded slot completes later on the same stream)
+    }
+    XENG_HIP(hipSetDevice(gpu));
+    XENG_HIP(hipEventSynchronize(ev));          // (outside the lock)
+    return XENG_STATUS_SUCCESS;
+}
+
+int xengUpchanTicketDone(unsigned long long ticket, int* done) {
+    if (!done) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanTicketDone: null result");
+    std::lock_guard<std::mutex> lk(g_umu);
+    UpchanContext& x = g_u;
+    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized");
+    if (ticket == 0 || ticket > x.nmarks) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanTicketDone: unknown ticket %llu", ticket);
+    XENG_HIP(hipSetDevice(x.gpu));
+    const hipError_t e = hipEventQuery(x.marks[(ticket - 1) % UpchanContext::NMARK]);
+    if (e != hipSuccess && e != hipErrorNotReady) XENG_HIP(e);
+    if (e == hipErrorNotReady) (void)hipGetLastError();
+    *done = e == hipSuccess;
+    return XENG_STATUS_SUCCESS;
+}
+
+int xengUpchanSync(void) {
+    std::lock_guard<std::mutex> lk(g_umu);
+    UpchanContext& x = g_u;
+    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized");
+    XENG_HIP(hipSetDevice(x.gpu));
+    XENG_HIP(hipStreamSynchronize(x.stream));
+    return XENG_STATUS_SUCCESS;
+}
+
+int xengUpchanDestroy(void) {
+    std::lock_guard<std::mutex> lk(g_umu);
+    return upchan_destroy_locked();
+}
+
+}  // extern "C"

@@ -89,6 +89,9 @@ SYMBOLS = {
     "xengBeamformPacketizeVoltages": [_vp, _vp, _i, _i, _i, _i, _i, _sz, _i, _i, _i, _i, _i, ctypes.c_uint64],
     "xengBeamformSetProfiling": [_i], "xengBeamformGetTimes": [ctypes.POINTER(ctypes.c_double), _pi],
     "xengBeamformGetRouteInfo": [_pi, _pi, _pi],
+    "xengUpchanInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengUpchanRun": [_vp, _vp, _vp, _ll], "xengUpchanRunParts": [_vp, _i, _vp, _vp, _vp, _ll],
+    "xengUpchanMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanWait": [ctypes.c_ulonglong], "xengUpchanTicketDone": [ctypes.c_ulonglong, _pi],
+    "xengUpchanSync": [], "xengUpchanDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -129,7 +132,8 @@ def lib():
 # XENG_STATUS_WOULD_BLOCK instead, and the caller gives the lock up to wait; xengSnap2UnpackAsync shares a mutex with the
 # synchronous call, which polls: it is made on the releasing handle.)
 ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xengBeamformTryRunVersioned", "xengBeamformTryRunParts", "xengBeamformTryRunSlabs",
-                "xengBeamformIntegrate", "xengBeamformIntegrateSingleBeam", "xengBeamformPacketizeVoltages", "xengBeamformMark", "xengMapAssignI32",
+                "xengBeamformIntegrate", "xengBeamformIntegrateSingleBeam", "xengBeamformPacketizeVoltages", "xengBeamformMark",
+                "xengUpchanRun", "xengUpchanRunParts", "xengUpchanMark", "xengUpchanTicketDone", "xengMapAssignI32",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

@@ -418,6 +418,34 @@ int xengBeamformGetTimes(double ms[2], int count[2]);   /* [0]=Run, [1]=Integrat
  * reference's cuBLAS CF32 GEMM (bf_src/cublas_beamform.cu:248-276) has one route. */
 int xengBeamformGetRouteInfo(int *tiles_total, int *tiles_bf16, int *outlier_inputs);
 
+/* ---------------------------------------------------------------- Upchannelising beamformer
+ * UpchanBeamform (lwa352-upchan-bf.py:94-113 with beamform_offline_block.py:211-245): a context of its own, independent of the
+ * Beamform context (either may live without the other), whose kernel runs on the beamformer's stream -- rings declared 'beam'
+ * cover it, and xengBeamformSync waits for it too.  One kernel per gulp (csrc/upchan_kernels.h):
+ *   in       u8[ntime][nchan][ninput], 4+4 bit as Beamform reads it; never written
+ *   frames   frame f = samples [f*N, f*N + N) of the gulp (N = nupchan in {8, 16, 32, 64}; frames never cross gulps)
+ *   FFT      X[f,c,i,k] = sum_n x[f*N+n, c, i] exp(-2 pi i k n / N), forward, no normalisation; fine channel j = (k + N/2) mod N,
+ *            so j ascends in frequency: centre sfreq + c*bw/nchan + (j - N/2)*bw/(nchan*N)
+ *   weights  cf32[nchan][N][nbeam][ninput], indexed by j; read as they are (16-byte aligned)
+ *   nframe_sum 0 (voltage):  out cf32[ntime/N][nbeam][nchan][N], v[f,b,c,j] = sum_i w[c,j,b,i] X[f,c,i,j]
+ *   nframe_sum > 0 (power):  out f32[ntime/N/nframe_sum][nbeam][nchan][N], sum of |v|^2 over nframe_sum consecutive frames
+ * (out 16-byte aligned; nothing past it is written).  fp32 throughout, the sum over inputs in a fixed order: bit-identical from
+ * run to run.  Rejected at Initialize: ninput not a positive multiple of 4, nupchan outside the set, ntime % nupchan,
+ * nframe_sum not dividing ntime/nupchan, nbeam*nupchan above 1024.  Rejected at Run without a launch: null or misaligned
+ * pointers; RunParts: parts that are not positive multiples of nupchan. */
+int xengUpchanInitialize(int gpu, int ninput, int nchan, int ntime, int nupchan, int nbeam, int nframe_sum);
+/* weights_version as xengBeamformRunVersioned's; the kernel reads the fp32 weights directly, so it is accepted and ignored */
+int xengUpchanRun(const void *in_dev, void *out_dev, const void *weights_dev, long long weights_version);
+/* one gulp in two spans: samples [0, ntime0) at in0_dev, [ntime0, ntime) at in1_dev */
+int xengUpchanRunParts(const void *in0_dev, int ntime0, const void *in1_dev, void *out_dev, const void *weights_dev,
+                       long long weights_version);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengBeamformMark / Wait / TicketDone */
+int xengUpchanMark(unsigned long long *ticket);
+int xengUpchanWait(unsigned long long ticket);
+int xengUpchanTicketDone(unsigned long long ticket, int *done);
+int xengUpchanSync(void);
+int xengUpchanDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
