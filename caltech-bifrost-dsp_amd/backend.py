@@ -247,6 +247,40 @@ class HipBackend:
     def upchan_sync(self):
         ffi.call("xengUpchanSync")
 
+    # ---- upchannelised correlator (UpchanCorr; include/xeng.h "Upchannelised correlator"): a context of its own, its kernels
+    # on the beamformer's stream
+    def upchan_corr_initialize(self, gpu, ninput, nchan, ntime, nupchan, fine_lo, fine_hi, nstage=0):
+        return self._lib.xengUpchanCorrInitialize(int(gpu), int(ninput), int(nchan), int(ntime), int(nupchan), int(fine_lo), int(fine_hi), int(nstage))
+
+    def upchan_corr_accumulate(self, in_arr):
+        """Enqueue only: upchan_corr_mark / upchan_corr_wait cover it."""
+        return self._enq.xengUpchanCorrAccumulate(in_arr.ptr)
+
+    def upchan_corr_accumulate_parts(self, part0, ntime0, part1):
+        """One gulp out of two consecutive spans of the input ring (samples [0, ntime0) in part0), no gathered copy."""
+        return self._enq.xengUpchanCorrAccumulateParts(part0.ptr, int(ntime0), part1.ptr)
+
+    def upchan_corr_dump(self, out_arr):
+        """Enqueue only: the integration so far into out_arr (cf32 [nfine][ninput][ninput]); the next one starts from zero."""
+        return self._enq.xengUpchanCorrDump(out_arr.ptr)
+
+    def upchan_corr_reset(self):
+        ffi.check("xengUpchanCorrReset", self._enq.xengUpchanCorrReset())
+
+    def upchan_corr_mark(self):
+        t = ctypes.c_ulonglong()
+        ffi.check("xengUpchanCorrMark", self._enq.xengUpchanCorrMark(ctypes.byref(t)))
+        return t.value
+
+    def upchan_corr_wait(self, ticket):
+        d = ctypes.c_int()
+        ffi.check("xengUpchanCorrTicketDone", self._enq.xengUpchanCorrTicketDone(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
+        if not d.value:
+            ffi.call("xengUpchanCorrWait", ctypes.c_ulonglong(ticket))
+
+    def upchan_corr_sync(self):
+        ffi.call("xengUpchanCorrSync")
+
     def last_error(self):
         return self._lib.xengGetLastError().decode()
 

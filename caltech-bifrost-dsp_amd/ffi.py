@@ -92,6 +92,10 @@ SYMBOLS = {
     "xengUpchanInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengUpchanRun": [_vp, _vp, _vp, _ll], "xengUpchanRunParts": [_vp, _i, _vp, _vp, _vp, _ll],
     "xengUpchanMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanWait": [ctypes.c_ulonglong], "xengUpchanTicketDone": [ctypes.c_ulonglong, _pi],
     "xengUpchanSync": [], "xengUpchanDestroy": [],
+    "xengUpchanCorrInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengUpchanCorrGetInfo": [_pi, _pi],
+    "xengUpchanCorrAccumulate": [_vp], "xengUpchanCorrAccumulateParts": [_vp, _i, _vp], "xengUpchanCorrDump": [_vp], "xengUpchanCorrReset": [],
+    "xengUpchanCorrMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanCorrWait": [ctypes.c_ulonglong], "xengUpchanCorrTicketDone": [ctypes.c_ulonglong, _pi],
+    "xengUpchanCorrSync": [], "xengUpchanCorrDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -133,7 +137,8 @@ def lib():
 # synchronous call, which polls: it is made on the releasing handle.)
 ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xengBeamformTryRunVersioned", "xengBeamformTryRunParts", "xengBeamformTryRunSlabs",
                 "xengBeamformIntegrate", "xengBeamformIntegrateSingleBeam", "xengBeamformPacketizeVoltages", "xengBeamformMark",
-                "xengUpchanRun", "xengUpchanRunParts", "xengUpchanMark", "xengUpchanTicketDone", "xengMapAssignI32",
+                "xengUpchanRun", "xengUpchanRunParts", "xengUpchanMark", "xengUpchanTicketDone", "xengUpchanCorrAccumulate",
+                "xengUpchanCorrAccumulateParts", "xengUpchanCorrDump", "xengUpchanCorrReset", "xengUpchanCorrMark", "xengUpchanCorrTicketDone", "xengMapAssignI32",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

@@ -446,6 +446,49 @@ int xengUpchanTicketDone(unsigned long long ticket, int *done);
 int xengUpchanSync(void);
 int xengUpchanDestroy(void);
 
+/* ---------------------------------------------------------------- Upchannelised correlator
+ * UpchanCorr (lwa352-upchan-imag.py:95-106: fft over fine_time, merge_axes, FrequencySelectBlock, blocks.correlate): a context
+ * of its own, independent of the Upchan and Beamform contexts, whose kernels run on the beamformer's stream -- rings declared
+ * 'beam' cover them, and xengBeamformSync waits for them too.  Three kernels (csrc/upchan_corr_kernels.h):
+ *   in       u8[ntime][nchan][ninput], 4+4 bit as Beamform reads it; never written
+ *   frames   frame f = samples [f*N, f*N + N) of the gulp (N = nupchan in {1, 2, 4, 8, 16, 32, 64}; frames never cross gulps)
+ *   FFT      X[f,c,i,k] = sum_n x[f*N+n, c, i] exp(-2 pi i k n / N), forward, no normalisation; fine channel j = (k + N/2) mod N
+ *            (ascending in frequency), merged index c*N + j; the fine channels [fine_lo, fine_hi) of that axis are kept, as
+ *            c' = c*N + j - fine_lo (the others are never correlated).  The twiddles 1 and -i are applied exactly, so N <= 4 is
+ *            exact on integer data.
+ *   out      cf32[nfine][ninput][ninput], nfine = fine_hi - fine_lo, V[c', i, j] = sum_f X[f, c', i] conj(X[f, c', j]) over every
+ *            frame accumulated since the last Dump / Reset (oracle golden_corr's convention; the X-engine's xgpu_lookup gives
+ *            the conjugate).  The full Hermitian matrix is written, so which triangle a convention keeps does not matter:
+ *            the lower triangle (i >= j) as accumulated, the upper as its exact conjugate, diagonal imaginary parts exactly 0.
+ *            16-byte aligned; nothing past it is written.
+ * Numerics: fp32.  Re += Xr_i Xr_j + Xi_i Xi_j and Im += Xi_i Xr_j - Xr_i Xi_j on f32-input MFMAs, frames in order, two per
+ * instruction (a gulp with an odd frame count is padded with a zero frame), one fmaf chain per gulp, the gulps' sums added
+ * in order: each element is one fixed sum over the integration, the same whatever nstage, however the gulps came in (whole
+ * or in parts), from run to run.  Within 1e-6 of sum_f |X_i||X_j| of the exact value; exact on integer data below 2^24
+ * (N <= 4).  No atomics.
+ * Accumulate stages a gulp's fine channels; every nstage gulps (0: a default of up to 8 within 4 GiB of staging) and at Dump
+ * the staged frames are contracted into an fp32 accumulator of nfine * ceil(ninput/32)*(ceil(ninput/32)+1)/2 * 8 KiB.
+ * ninput is padded internally to a multiple of 32 with zero inputs: any positive ninput is accepted.
+ * Rejected at Initialize: a non-positive size, nupchan outside the set, ntime % nupchan, an empty or out-of-range
+ * [fine_lo, fine_hi), nstage < 0.  Rejected without a launch: null or misaligned pointers; AccumulateParts: parts that are not
+ * positive multiples of nupchan.  Without a context: XENG_STATUS_INVALID_STATE. */
+int xengUpchanCorrInitialize(int gpu, int ninput, int nchan, int ntime, int nupchan, int fine_lo, int fine_hi, int nstage);
+/* the live context's nfine and staging depth (nstage as resolved) */
+int xengUpchanCorrGetInfo(int *nfine, int *nstage);
+/* enqueue only: one gulp, or one gulp in two spans (samples [0, ntime0) at in0_dev, [ntime0, ntime) at in1_dev) */
+int xengUpchanCorrAccumulate(const void *in_dev);
+int xengUpchanCorrAccumulateParts(const void *in0_dev, int ntime0, const void *in1_dev);
+/* enqueue only: contract what is staged, write the integration to out_dev, start the next one from zero */
+int xengUpchanCorrDump(void *out_dev);
+/* drop the integration in progress (nothing is launched) */
+int xengUpchanCorrReset(void);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengUpchanCorrMark(unsigned long long *ticket);
+int xengUpchanCorrWait(unsigned long long ticket);
+int xengUpchanCorrTicketDone(unsigned long long ticket, int *done);
+int xengUpchanCorrSync(void);
+int xengUpchanCorrDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
