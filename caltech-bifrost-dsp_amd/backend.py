@@ -233,16 +233,10 @@ class HipBackend:
         return self._enq.xengUpchanRunParts(part0.ptr, int(ntime0), part1.ptr, out_arr.ptr, weights.ptr, int(version))
 
     def upchan_mark(self):
-        t = ctypes.c_ulonglong()
-        ffi.check("xengUpchanMark", self._enq.xengUpchanMark(ctypes.byref(t)))
-        return t.value
+        return self._mark("xengUpchanMark")
 
     def upchan_wait(self, ticket):
-        # ask first, without giving up the interpreter lock; only a ticket the GPU has not reached yet is worth a blocking call
-        d = ctypes.c_int()
-        ffi.check("xengUpchanTicketDone", self._enq.xengUpchanTicketDone(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
-        if not d.value:
-            ffi.call("xengUpchanWait", ctypes.c_ulonglong(ticket))
+        self._wait("xengUpchanTicketDone", "xengUpchanWait", ticket)
 
     def upchan_sync(self):
         ffi.call("xengUpchanSync")
@@ -268,18 +262,26 @@ class HipBackend:
         ffi.check("xengUpchanCorrReset", self._enq.xengUpchanCorrReset())
 
     def upchan_corr_mark(self):
-        t = ctypes.c_ulonglong()
-        ffi.check("xengUpchanCorrMark", self._enq.xengUpchanCorrMark(ctypes.byref(t)))
-        return t.value
+        return self._mark("xengUpchanCorrMark")
 
     def upchan_corr_wait(self, ticket):
-        d = ctypes.c_int()
-        ffi.check("xengUpchanCorrTicketDone", self._enq.xengUpchanCorrTicketDone(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
-        if not d.value:
-            ffi.call("xengUpchanCorrWait", ctypes.c_ulonglong(ticket))
+        self._wait("xengUpchanCorrTicketDone", "xengUpchanCorrWait", ticket)
 
     def upchan_corr_sync(self):
         ffi.call("xengUpchanCorrSync")
+
+    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr)
+    def _mark(self, mark):
+        t = ctypes.c_ulonglong()
+        ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))
+        return t.value
+
+    def _wait(self, ticket_done, wait, ticket):
+        # ask first, without giving up the interpreter lock; only a ticket the GPU has not reached yet is worth a blocking call
+        d = ctypes.c_int()
+        ffi.check(ticket_done, getattr(self._enq, ticket_done)(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
+        if not d.value:
+            ffi.call(wait, ctypes.c_ulonglong(ticket))
 
     def last_error(self):
         return self._lib.xengGetLastError().decode()

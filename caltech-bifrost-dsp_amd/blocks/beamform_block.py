@@ -10,7 +10,6 @@ libxeng's fused nibble-decode + fp32-MFMA beamformer (csrc/beamform_kernels.h).
 out[c, b, t] = sum_i gains[c, b, i] * x[t, c, i], cf32 [nchan, nbeam, ntime_gulp]
 (beamformer_test.py:76-84).
 """
-import collections
 import json
 import time
 
@@ -19,7 +18,7 @@ import numpy as np
 from ..backend import default_backend
 from ..ndarray import XArray
 from ..proclog import cpu_affinity
-from .block_base import Block, COMMAND_INVALID, COMMAND_OK, declare_streams
+from .block_base import Block, COMMAND_INVALID, COMMAND_OK, InFlight, declare_streams, spans_outlive_release
 
 
 class Beamform(Block):
@@ -144,26 +143,9 @@ class Beamform(Block):
         # have completed (beam_mark / beam_wait tickets) -- the reference, and the path taken on a circular bifrost ring,
         # waits for the stream after every gulp (beamform_block.py:450), which leaves the GPU idle between gulps and, beside
         # the X-engine's persistent kernel, costs one launch boundary of that kernel per gulp.
-        streaming = (getattr(self.iring, 'span_memory_outlives_release', False) and getattr(self.oring, 'span_memory_outlives_release', False)
-                     and hasattr(self._bf, 'beam_mark'))
-        pending = collections.deque()           # (ticket, output span, input data kept alive)
-
-        def retire(keep):
-            while len(pending) > keep:
-                ticket, osp, _ = pending.popleft()
-                self._bf.beam_wait(ticket)
-                osp.close()
-        try:
-            self._main_loop(igulp_size, ogulp_size, streaming, pending, retire)
-        finally:
-            # An exception must not release spans that kernels in flight still read or write (their memory would go back
-            # to the ring, be handed out again or freed, under a running kernel): wait for the stream first.
-            if pending:
-                try:
-                    self._bf.beam_sync()
-                except Exception:
-                    pass
-                pending.clear()
+        streaming = spans_outlive_release(self.iring, self.oring) and hasattr(self._bf, 'beam_mark')
+        with InFlight(getattr(self._bf, 'beam_wait', None), self._bf.beam_sync) as inflight:
+            self._main_loop(igulp_size, ogulp_size, streaming, inflight)
 
     PUMP_GULPS = 8          # gulps per call of the native loop while no command is pending
 
@@ -199,7 +181,7 @@ class Beamform(Block):
             pump.abort()
             raise
 
-    def _main_loop(self, igulp_size, ogulp_size, streaming, pending, retire):
+    def _main_loop(self, igulp_size, ogulp_size, streaming, inflight):
         """Per input sequence: header work (_begin_sequence), then one of two per-gulp loops -- the native one (_pump_sequence) between
         native rings, the Python one (_python_sequence) otherwise (bifrost / Python rings, XENG_PUMP=0)."""
         with self.oring.begin_writing() as oring:
@@ -216,7 +198,7 @@ class Beamform(Block):
                             pump.set_slabs(seq['slab_npkt'], seq['slab_stride'], seq['slab_ntime'], seq['ihdr']['chan0'], self.ntime_gulp)
                         self._pump_sequence(pump, seq['this_gulp_time'], seq['igulp_size'], True, seq['slab'])
                     else:
-                        self._python_sequence(iseq, oseq, seq, ogulp_size, streaming, pending, retire)
+                        self._python_sequence(iseq, oseq, seq, ogulp_size, streaming, inflight)
 
     def _begin_sequence(self, iseq):
         """A new input sequence: frequencies (coefficients are rebuilt and re-uploaded on every sequence), the output header
@@ -299,7 +281,7 @@ class Beamform(Block):
         self.release_control_lock()
         return copy_pending
 
-    def _python_sequence(self, iseq, oseq, seq, ogulp_size, streaming, pending, retire):
+    def _python_sequence(self, iseq, oseq, seq, ogulp_size, streaming, inflight):
         """The per-gulp loop in Python (beamform_block.py:411-461)."""
         igulp_size, this_gulp_time, read_parts = seq['igulp_size'], seq['this_gulp_time'], seq['read_parts']
         copy_pending = True
@@ -313,7 +295,7 @@ class Beamform(Block):
             if self.update_pending:
                 copy_pending = self._load_pending_gains(this_gulp_time) or copy_pending
             if copy_pending:
-                retire(0)           # (kernels in flight may still read the device copy of the weights)
+                inflight.retire(0)  # (kernels in flight may still read the device copy of the weights)
                 self.gains_gpu[...] = self.gains_cpu
                 self._gains_version += 1
                 copy_pending = False
@@ -335,9 +317,9 @@ class Beamform(Block):
                 if rv != self._bf.BF_STATUS_SUCCESS:
                     raise RuntimeError("bfBeamformRun returned %d: %s" % (rv, self._bf.last_error()))
                 if streaming:
-                    pending.append((self._bf.beam_mark(), ospan, held))
+                    inflight.push(self._bf.beam_mark(), ospan, held)
                     ospan = None
-                    retire(self.STREAM_DEPTH)
+                    inflight.retire(self.STREAM_DEPTH)
                 else:
                     self._bf.beam_sync()          # BFSync() of beamform_block.py:450, this block's stream only
             finally:
@@ -349,4 +331,4 @@ class Beamform(Block):
             prev_time = curr_time
             self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': reserve_time, 'process_time': process_time,
                                       'gbps': 8 * igulp_size / max(process_time, 1e-9) / 1e9})
-        retire(0)                   # the sequence ends: every gulp in flight is committed first
+        inflight.retire(0)          # the sequence ends: every gulp in flight is committed first

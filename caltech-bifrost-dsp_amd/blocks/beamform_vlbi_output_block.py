@@ -37,7 +37,7 @@ import numpy as np
 from ..backend import default_backend
 from ..ndarray import XArray
 from ..proclog import cpu_affinity
-from .block_base import Block, declare_streams
+from .block_base import Block, declare_streams, gulp_time
 
 HEADER_BYTES = 16           # header at bytes [1, 16) of a slot, payload from byte 16 (16-byte aligned)
 
@@ -180,12 +180,7 @@ class BeamformVlbiOutput(Block):
             for ispan in iseq.read(igulp_size):
                 if ispan.size < igulp_size:
                     continue                                    # ignore final gulp
-                # the gulp's sample number from its place in the sequence: right for a reader that skipped gulps as well
-                offset = getattr(ispan, 'offset', None)
-                if offset is not None:
-                    this_gulp_time = seq0 + (offset // igulp_size) * self.ntime_gulp
-                elif getattr(ispan, 'skipped', 0):
-                    this_gulp_time += (ispan.skipped // igulp_size) * self.ntime_gulp
+                this_gulp_time = gulp_time(ispan, seq0, igulp_size, self.ntime_gulp, this_gulp_time)
                 if self.update_pending:
                     self._update_destination()
                 self.update_stats({'curr_sample': this_gulp_time})

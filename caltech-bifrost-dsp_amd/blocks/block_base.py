@@ -4,6 +4,7 @@ checks, the pending -> active command hand-off under a control lock, JSON comman
 (etcd callback shape), stats and proclogs.  etcd is optional (`etcd_client=None`), commands
 can be injected with process_command_strings() exactly as the reference's tests do
 (block_base.py:194-214)."""
+import collections
 import json
 import socket
 import time
@@ -33,6 +34,64 @@ def declare_streams(ring, *classes):
     f = getattr(ring, 'declare_streams', None)
     if f is not None:
         f(*classes)
+
+
+def spans_outlive_release(iring, oring):
+    """Both rings keep a span's memory alive while it is referenced (in-repo rings): a block may keep several gulps in flight
+    and let go of each gulp's spans when ITS kernels have completed.  A bifrost ring: wait for the kernels after every gulp."""
+    return getattr(iring, 'span_memory_outlives_release', False) and getattr(oring, 'span_memory_outlives_release', False)
+
+
+class InFlight(object):
+    """The calls of a streaming block whose kernels may still run, oldest first: (ticket, output span or None, input kept alive).
+    `wait(ticket)` / `sync()` are the backend's ticket wait and stream sync.  Used as a context manager: a block that leaves
+    with calls in flight (an exception) waits for the stream before it drops their spans, uncommitted -- released under a
+    running kernel, their memory would go back to the ring, to be handed out again or freed."""
+
+    def __init__(self, wait, sync):
+        self._wait, self._sync = wait, sync
+        self._calls = collections.deque()
+
+    def push(self, ticket, ospan, held):
+        self._calls.append((ticket, ospan, held))
+
+    def retire(self, keep):
+        """Wait for all but the newest `keep` calls, committing their output spans."""
+        while len(self._calls) > keep:
+            ticket, ospan, _ = self._calls.popleft()
+            self._wait(ticket)
+            if ospan is not None:
+                ospan.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self._calls:
+            try:
+                self._sync()
+            except Exception:
+                pass
+            self._calls.clear()
+
+
+def gulp_time(ispan, seq0, igulp_size, ntime_gulp, prev):
+    """The first sample of the gulp in `ispan` from its place in the sequence (`offset`, bytes from the sequence's start), or
+    after the gulps the reader skipped (`skipped` bytes right before it), or else `prev`."""
+    offset = getattr(ispan, 'offset', None)
+    if offset is not None:
+        return seq0 + (offset // igulp_size) * ntime_gulp
+    if getattr(ispan, 'skipped', 0):
+        return prev + (ispan.skipped // igulp_size) * ntime_gulp
+    return prev
+
+
+def split_frames(parts, row, nupchan, who):
+    """Samples in the first of a gulp's two parts (`row` bytes each), which must be whole frames of `nupchan` samples."""
+    ntime0 = parts[0].nbytes // row
+    if ntime0 % nupchan:
+        raise RuntimeError("%s: a gulp split after %d samples is not whole frames of %d" % (who, ntime0, nupchan))
+    return ntime0
 
 
 class Block(object):

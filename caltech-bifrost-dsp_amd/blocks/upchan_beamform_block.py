@@ -15,7 +15,6 @@ Input: u8 [ntime_gulp][nchan][ninput] spans (the Beamform input).  Output per gu
   nframe_sum > 0: f32  [nframe / nframe_sum][nbeam][nchan][nupchan]
 Fine channel j of coarse channel c is centred at sfreq + c*d + (j - nupchan/2)*d/nupchan, d = bw_hz / nchan.
 """
-import collections
 import json
 import time
 
@@ -24,7 +23,7 @@ import numpy as np
 from ..backend import default_backend
 from ..ndarray import XArray
 from ..proclog import cpu_affinity
-from .block_base import Block, COMMAND_INVALID, COMMAND_OK, declare_streams
+from .block_base import Block, COMMAND_INVALID, COMMAND_OK, InFlight, declare_streams, gulp_time, split_frames, spans_outlive_release
 
 
 class UpchanBeamform(Block):
@@ -156,27 +155,12 @@ class UpchanBeamform(Block):
         self.oring.resize(ogulp_size)
         # In-repo rings keep a span's memory alive while it is referenced: several gulps in flight, each output span committed
         # when ITS kernel has completed (tickets).  A bifrost ring: wait for the kernel after every gulp.
-        streaming = (getattr(self.iring, 'span_memory_outlives_release', False) and getattr(self.oring, 'span_memory_outlives_release', False))
-        pending = collections.deque()           # (ticket, output span, input kept alive)
+        streaming = spans_outlive_release(self.iring, self.oring)
+        with InFlight(self._bf.upchan_wait, self._bf.upchan_sync) as inflight, self.oring.begin_writing() as oring:
+            for iseq in self.iring.read(guarantee=self.guarantee):
+                self._sequence(iseq, oring, ogulp_size, streaming, inflight)
 
-        def retire(keep):
-            while len(pending) > keep:
-                ticket, osp, _ = pending.popleft()
-                self._bf.upchan_wait(ticket)
-                osp.close()
-        try:
-            with self.oring.begin_writing() as oring:
-                for iseq in self.iring.read(guarantee=self.guarantee):
-                    self._sequence(iseq, oring, ogulp_size, streaming, pending, retire)
-        finally:
-            if pending:         # (nothing a kernel in flight still touches is let go before the stream is idle)
-                try:
-                    self._bf.upchan_sync()
-                except Exception:
-                    pass
-                pending.clear()
-
-    def _sequence(self, iseq, oring, ogulp_size, streaming, pending, retire):
+    def _sequence(self, iseq, oring, ogulp_size, streaming, inflight):
         self.update_pending = True
         ihdr = json.loads(iseq.header.tostring())
         self.sequence_proclog.update(ihdr)
@@ -197,17 +181,12 @@ class UpchanBeamform(Block):
             for ispan in (read_parts(igulp_size) if read_parts is not None else iseq.read(igulp_size)):
                 if ispan.size < igulp_size:
                     continue                    # a short final gulp is skipped (as the reference's gulp_nframe reader does)
-                # the gulp's first sample from its place in the sequence: right after a reader skipped gulps as well
-                offset = getattr(ispan, 'offset', None)
-                if offset is not None:
-                    this_gulp_time = seq0 + (offset // igulp_size) * self.ntime_gulp
-                elif getattr(ispan, 'skipped', 0):
-                    this_gulp_time += (ispan.skipped // igulp_size) * self.ntime_gulp
+                this_gulp_time = gulp_time(ispan, seq0, igulp_size, self.ntime_gulp, this_gulp_time)
                 self.update_stats({'curr_sample': this_gulp_time})
                 if self.update_pending:
                     copy_pending = self._load_pending_weights(this_gulp_time) or copy_pending
                 if copy_pending:
-                    retire(0)                   # (kernels in flight may still read the device copy of the weights)
+                    inflight.retire(0)          # (kernels in flight may still read the device copy of the weights)
                     self.weights_gpu[...] = self.weights_cpu
                     self._weights_version += 1
                     copy_pending = False
@@ -218,9 +197,7 @@ class UpchanBeamform(Block):
                 try:
                     parts = getattr(ispan, 'parts', None)
                     if parts is not None and len(parts) == 2:
-                        ntime0 = parts[0].nbytes // row
-                        if ntime0 % self.nupchan:
-                            raise RuntimeError("UPCHAN: a gulp split after %d samples is not whole frames of %d" % (ntime0, self.nupchan))
+                        ntime0 = split_frames(parts, row, self.nupchan, "UPCHAN")
                         held = parts
                         rv = self._bf.upchan_run_parts(parts[0], ntime0, parts[1], ospan.data, self.weights_gpu, self._weights_version)
                     else:
@@ -229,9 +206,9 @@ class UpchanBeamform(Block):
                     if rv != self._bf.BF_STATUS_SUCCESS:
                         raise RuntimeError("xengUpchanRun returned %d: %s" % (rv, self._bf.last_error()))
                     if streaming:
-                        pending.append((self._bf.upchan_mark(), ospan, held))
+                        inflight.push(self._bf.upchan_mark(), ospan, held)
                         ospan = None
-                        retire(self.STREAM_DEPTH)
+                        inflight.retire(self.STREAM_DEPTH)
                     else:
                         self._bf.upchan_sync()
                 finally:
@@ -243,4 +220,4 @@ class UpchanBeamform(Block):
                 process_time = curr_time - prev_time
                 prev_time = curr_time
                 self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
-            retire(0)                           # the sequence ends: every gulp in flight is committed first
+            inflight.retire(0)                  # the sequence ends: every gulp in flight is committed first

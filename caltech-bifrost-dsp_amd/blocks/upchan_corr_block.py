@@ -15,13 +15,12 @@ Input: u8 [ntime_gulp][nchan][ninput] spans (the Beamform input).  Output: one s
 one output sequence per run of consecutive integrations, its header's seq0 the first one's start sample (as Corr's).  Merged
 fine channel m = c*N + j is centred at sfreq + c*d + (j - N/2)*d/N, d = bw_hz / nchan.
 """
-import collections
 import json
 import time
 
 from ..backend import default_backend
 from ..proclog import cpu_affinity
-from .block_base import Block, declare_streams
+from .block_base import Block, InFlight, declare_streams, gulp_time, split_frames, spans_outlive_release
 
 NUPCHAN = (1, 2, 4, 8, 16, 32, 64)
 
@@ -77,26 +76,10 @@ class UpchanCorr(Block):
         # In-repo rings keep a span's memory alive while it is referenced: several calls in flight, each input span held until
         # ITS stage kernel has completed, each output span committed when ITS dump kernel has (tickets).  A bifrost ring: wait
         # for the kernels after every gulp.
-        streaming = (getattr(self.iring, 'span_memory_outlives_release', False) and getattr(self.oring, 'span_memory_outlives_release', False))
-        pending = collections.deque()           # (ticket, output span or None, input kept alive)
-
-        def retire(keep):
-            while len(pending) > keep:
-                ticket, osp, _ = pending.popleft()
-                self._bf.upchan_corr_wait(ticket)
-                if osp is not None:
-                    osp.close()
-        try:
-            with self.oring.begin_writing() as oring:
-                for iseq in self.iring.read(guarantee=self.guarantee):
-                    self._sequence(iseq, oring, ogulp_size, streaming, pending, retire)
-        finally:
-            if pending:         # (nothing a kernel in flight still touches is let go before the stream is idle)
-                try:
-                    self._bf.upchan_corr_sync()
-                except Exception:
-                    pass
-                pending.clear()
+        streaming = spans_outlive_release(self.iring, self.oring)
+        with InFlight(self._bf.upchan_corr_wait, self._bf.upchan_corr_sync) as inflight, self.oring.begin_writing() as oring:
+            for iseq in self.iring.read(guarantee=self.guarantee):
+                self._sequence(iseq, oring, ogulp_size, streaming, inflight)
 
     def _drop(self, nlost, reset, why):
         """Integrations lost to gulps that were not read; the one in progress (reset) leaves nothing in the next one."""
@@ -105,7 +88,7 @@ class UpchanCorr(Block):
         self.update_stats({'ndropped': self.stats['ndropped'] + nlost})
         self.log.warning("UPCHAN_CORR >> %d integration(s) dropped: %s" % (nlost, why))
 
-    def _sequence(self, iseq, oring, ogulp_size, streaming, pending, retire):
+    def _sequence(self, iseq, oring, ogulp_size, streaming, inflight):
         ihdr = json.loads(iseq.header.tostring())
         self.sequence_proclog.update(ihdr)
         if ihdr['nchan'] != self.nchan or ihdr['nstand'] * ihdr['npol'] != self.ninput:
@@ -125,12 +108,7 @@ class UpchanCorr(Block):
             for ispan in (read_parts(igulp_size) if read_parts is not None else iseq.read(igulp_size)):
                 if ispan.size < igulp_size:
                     continue                    # a short final gulp is skipped (as the reference's gulp_nframe reader does)
-                # the gulp's first sample from its place in the sequence: right after a reader skipped gulps as well
-                offset = getattr(ispan, 'offset', None)
-                if offset is not None:
-                    this_gulp_time = seq0 + (offset // igulp_size) * self.ntime_gulp
-                elif getattr(ispan, 'skipped', 0):
-                    this_gulp_time += (ispan.skipped // igulp_size) * self.ntime_gulp
+                this_gulp_time = gulp_time(ispan, seq0, igulp_size, self.ntime_gulp, this_gulp_time)
                 if this_gulp_time != expected:
                     # gulps this reader never saw: an integration they belonged to is lost, and the output realigns to the
                     # next boundary in a sequence of its own (as Corr does)
@@ -140,7 +118,7 @@ class UpchanCorr(Block):
                     self._drop(max(0, k_hi - k_lo + 1), bool(pos), "samples [%d, %d) were not read" % (expected, this_gulp_time))
                     pos = None
                     if oseq is not None:
-                        retire(0)
+                        inflight.retire(0)
                         oseq.end()
                         oseq = None
                 expected = this_gulp_time + self.ntime_gulp
@@ -156,9 +134,7 @@ class UpchanCorr(Block):
                 prev_time = curr_time
                 parts = getattr(ispan, 'parts', None)
                 if parts is not None and len(parts) == 2:
-                    ntime0 = parts[0].nbytes // row
-                    if ntime0 % self.nupchan:
-                        raise RuntimeError("UPCHAN_CORR: a gulp split after %d samples is not whole frames of %d" % (ntime0, self.nupchan))
+                    ntime0 = split_frames(parts, row, self.nupchan, "UPCHAN_CORR")
                     held = parts
                     rv = self._bf.upchan_corr_accumulate_parts(parts[0], ntime0, parts[1])
                 else:
@@ -177,9 +153,9 @@ class UpchanCorr(Block):
                         pos = 0
                         self.update_stats({'nintegration': self.stats['nintegration'] + 1, 'last_end_sample': this_gulp_time + self.ntime_gulp})
                     if streaming:
-                        pending.append((self._bf.upchan_corr_mark(), ospan, held))
+                        inflight.push(self._bf.upchan_corr_mark(), ospan, held)
                         ospan = None
-                        retire(self.STREAM_DEPTH)
+                        inflight.retire(self.STREAM_DEPTH)
                     else:
                         self._bf.upchan_corr_sync()
                 finally:
@@ -192,6 +168,6 @@ class UpchanCorr(Block):
             if pos:                             # (the sequence ends inside an integration: it is not written)
                 self._bf.upchan_corr_reset()
         finally:
-            retire(0)                           # every call in flight is complete (and every output span committed) first
+            inflight.retire(0)                  # every call in flight is complete (and every output span committed) first
             if oseq is not None:
                 oseq.end()

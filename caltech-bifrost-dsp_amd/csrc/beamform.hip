@@ -41,10 +41,7 @@ struct BeamContext {
     unsigned long long* stamps = nullptr;   // diagnostic (XENG_BEAM_STAMPS=1): per wave {entry, first chunk, loop end, exit}
     int nchunk_i8 = 0;
     hipStream_t stream = nullptr;
-    // xengBeamformMark / Wait: completion tickets on the beam stream (a ring of events; ticket n -> marks[n % NMARK])
-    static constexpr int NMARK = 64;
-    hipEvent_t marks[NMARK] = {};
-    unsigned long long nmarks = 0;
+    TicketRing tickets;               // xengBeamformMark / Wait / TicketDone
     // gulps handed over as packet slabs (xengBeamformRunSlabs; slab.h): descriptors + the scratch gulp that an irregular slab is
     // scattered into -- written and read in stream order on the beam stream, so one set.  ONE helper launch per call: measured
     // (profiles/r04/slab_paths.txt) four short launches in front of a 35 us kernel pair cost 18 us, the same passes on a
@@ -85,8 +82,7 @@ static int beam_destroy_locked() {
     if (g_b.out_R) (void)hipFree(g_b.out_R);
     if (g_b.any_host) (void)hipHostFree(g_b.any_host);
     if (g_b.ev_route) (void)hipEventDestroy(g_b.ev_route);
-    for (int k = 0; k < BeamContext::NMARK; k++)
-        if (g_b.marks[k]) (void)hipEventDestroy(g_b.marks[k]);
+    g_b.tickets.destroy();
     if (g_b.stamps) (void)hipFree(g_b.stamps);
     slab_site_destroy(&g_b.slab_site);
     slab_index_prep_destroy(&g_b.slab_ix);
@@ -536,13 +532,7 @@ int xengBeamformMark(unsigned long long* ticket) {
     if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Beamform: not initialized");
     if (!ticket) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Mark: null ticket");
     XENG_HIP(hipSetDevice(x.gpu));
-    hipEvent_t& ev = x.marks[x.nmarks % BeamContext::NMARK];
-    if (!ev) XENG_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    const unsigned long long upto = stream_clock_now(STREAM_BEAM);      // (read BEFORE the record: everything counted precedes it)
-    XENG_HIP(hipEventRecord(ev, x.stream));
-    stream_clock_external_mark(STREAM_BEAM, ev, upto);                  // stamps of released spans find this event: none of their own on this stream
-    *ticket = ++x.nmarks;
-    return XENG_STATUS_SUCCESS;
+    return x.tickets.mark(x.stream, STREAM_BEAM, ticket);
 }
 
 int xengBeamformWait(unsigned long long ticket) {
@@ -552,11 +542,8 @@ int xengBeamformWait(unsigned long long ticket) {
         std::lock_guard<std::mutex> lk(g_bmu);
         BeamContext& x = g_b;
         if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Beamform: not initialized");
-        if (ticket == 0 || ticket > x.nmarks) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Wait: unknown ticket %llu", ticket);
+        if (!(ev = x.tickets.find(ticket))) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Wait: unknown ticket %llu", ticket);
         gpu = x.gpu;
-        // a ticket whose event slot has been re-recorded is NMARK marks old: wait for the newer record of that slot, which
-        // is later on the same stream
-        ev = x.marks[(ticket - 1) % BeamContext::NMARK];
     }
     XENG_HIP(hipSetDevice(gpu));
     XENG_HIP(hipEventSynchronize(ev));          // (outside the lock: the other block keeps enqueueing)
@@ -567,13 +554,10 @@ int xengBeamformTicketDone(unsigned long long ticket, int* done) {
     std::lock_guard<std::mutex> lk(g_bmu);
     BeamContext& x = g_b;
     if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Beamform: not initialized");
-    if (!done || ticket == 0 || ticket > x.nmarks) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "TicketDone: unknown ticket %llu", ticket);
+    const hipEvent_t ev = x.tickets.find(ticket);
+    if (!done || !ev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "TicketDone: unknown ticket %llu", ticket);
     XENG_HIP(hipSetDevice(x.gpu));
-    const hipError_t e = hipEventQuery(x.marks[(ticket - 1) % BeamContext::NMARK]);   // (a re-recorded slot: see Wait)
-    if (e != hipSuccess && e != hipErrorNotReady) XENG_HIP(e);
-    if (e == hipErrorNotReady) (void)hipGetLastError();
-    *done = e == hipSuccess;
-    return XENG_STATUS_SUCCESS;
+    return TicketRing::query(ev, done);
 }
 
 int xengBeamformGetRouteInfo(int* tiles_total, int* tiles_bf16, int* outlier_inputs) {

@@ -12,10 +12,7 @@ struct UpchanContext {
     bool live = false;
     int gpu = 0, ninput = 0, nchan = 0, ntime = 0, nupchan = 0, nbeam = 0, nframe_sum = 0;
     hipStream_t stream = nullptr;
-    // completion tickets (as xengBeamformMark): ticket n -> marks[(n - 1) % NMARK]
-    static constexpr int NMARK = 64;
-    hipEvent_t marks[NMARK] = {};
-    unsigned long long nmarks = 0;
+    TicketRing tickets;                 // xengUpchanMark / Wait / TicketDone
 };
 static std::mutex g_umu;
 static UpchanContext g_u;
@@ -25,8 +22,7 @@ static int upchan_destroy_locked() {
     (void)hipSetDevice(g_u.gpu);
     if (g_u.stream) (void)hipStreamSynchronize(g_u.stream);
     stream_clocks_forget(g_u.gpu, STREAM_BEAM);          // (the mark events lent to the stream clock go away below)
-    for (int k = 0; k < UpchanContext::NMARK; k++)
-        if (g_u.marks[k]) (void)hipEventDestroy(g_u.marks[k]);
+    g_u.tickets.destroy();
     g_u = UpchanContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -62,10 +58,8 @@ static int upchan_run(const void* in0_dev, int ntime0, const void* in1_dev, void
     std::lock_guard<std::mutex> lk(g_umu);
     UpchanContext& x = g_u;
     if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized (call xengUpchanInitialize)");
-    if (!in1_dev) { in1_dev = in0_dev; ntime0 = x.ntime; }
-    else if (ntime0 >= x.ntime || ntime0 % x.nupchan)
-        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: parts of %d + %d samples: both must be positive multiples of nupchan %d", ntime0,
-                  x.ntime - ntime0, x.nupchan);
+    int rc = gulp_parts("Upchan", in0_dev, &in1_dev, &ntime0, x.ntime, x.nupchan);
+    if (rc) return rc;
     XENG_HIP(hipSetDevice(x.gpu));
     const int nframe = x.ntime / x.nupchan, run = upchan_run_frames(x.nframe_sum);
     const int nthr = upchan_threads(x.nbeam, x.nupchan);
@@ -136,13 +130,7 @@ int xengUpchanMark(unsigned long long* ticket) {
     UpchanContext& x = g_u;
     if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized");
     XENG_HIP(hipSetDevice(x.gpu));
-    hipEvent_t& ev = x.marks[x.nmarks % UpchanContext::NMARK];
-    if (!ev) XENG_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    const unsigned long long upto = stream_clock_now(STREAM_BEAM);      // (read BEFORE the record: everything counted precedes it)
-    XENG_HIP(hipEventRecord(ev, x.stream));
-    stream_clock_external_mark(STREAM_BEAM, ev, upto);
-    *ticket = ++x.nmarks;
-    return XENG_STATUS_SUCCESS;
+    return x.tickets.mark(x.stream, STREAM_BEAM, ticket);
 }
 
 int xengUpchanWait(unsigned long long ticket) {
@@ -152,9 +140,8 @@ int xengUpchanWait(unsigned long long ticket) {
         std::lock_guard<std::mutex> lk(g_umu);
         UpchanContext& x = g_u;
         if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized");
-        if (ticket == 0 || ticket > x.nmarks) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanWait: unknown ticket %llu", ticket);
+        if (!(ev = x.tickets.find(ticket))) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanWait: unknown ticket %llu", ticket);
         gpu = x.gpu;
-        ev = x.marks[(ticket - 1) % UpchanContext::NMARK];      // (a re-recorded slot completes later on the same stream)
     }
     XENG_HIP(hipSetDevice(gpu));
     XENG_HIP(hipEventSynchronize(ev));          // (outside the lock)
@@ -166,22 +153,15 @@ int xengUpchanTicketDone(unsigned long long ticket, int* done) {
     std::lock_guard<std::mutex> lk(g_umu);
     UpchanContext& x = g_u;
     if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized");
-    if (ticket == 0 || ticket > x.nmarks) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanTicketDone: unknown ticket %llu", ticket);
+    const hipEvent_t ev = x.tickets.find(ticket);
+    if (!ev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanTicketDone: unknown ticket %llu", ticket);
     XENG_HIP(hipSetDevice(x.gpu));
-    const hipError_t e = hipEventQuery(x.marks[(ticket - 1) % UpchanContext::NMARK]);
-    if (e != hipSuccess && e != hipErrorNotReady) XENG_HIP(e);
-    if (e == hipErrorNotReady) (void)hipGetLastError();
-    *done = e == hipSuccess;
-    return XENG_STATUS_SUCCESS;
+    return TicketRing::query(ev, done);
 }
 
 int xengUpchanSync(void) {
     std::lock_guard<std::mutex> lk(g_umu);
-    UpchanContext& x = g_u;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    return XENG_STATUS_SUCCESS;
+    return context_sync("Upchan", g_u.live, g_u.gpu, g_u.stream);
 }
 
 int xengUpchanDestroy(void) {

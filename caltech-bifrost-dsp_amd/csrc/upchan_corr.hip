@@ -18,10 +18,7 @@ struct UpchanCorrContext {
     int staged = 0;                     // gulps staged since the last contraction
     bool fresh = true;                  // nothing contracted since the last dump / reset: the next contraction starts from zero
     hipStream_t stream = nullptr;
-    // completion tickets (as xengUpchanMark): ticket n -> marks[(n - 1) % NMARK]
-    static constexpr int NMARK = 64;
-    hipEvent_t marks[NMARK] = {};
-    unsigned long long nmarks = 0;
+    TicketRing tickets;                 // xengUpchanCorrMark / Wait / TicketDone
 };
 static std::mutex g_ccmu;
 static UpchanCorrContext g_cc;
@@ -35,8 +32,7 @@ static int upchan_corr_destroy_locked() {
     (void)hipSetDevice(g_cc.gpu);
     if (g_cc.stream) (void)hipStreamSynchronize(g_cc.stream);
     stream_clocks_forget(g_cc.gpu, STREAM_BEAM);         // (the mark events lent to the stream clock go away below)
-    for (int k = 0; k < UpchanCorrContext::NMARK; k++)
-        if (g_cc.marks[k]) (void)hipEventDestroy(g_cc.marks[k]);
+    g_cc.tickets.destroy();
     if (g_cc.stage) (void)hipFree(g_cc.stage);
     if (g_cc.acc) (void)hipFree(g_cc.acc);
     g_cc = UpchanCorrContext();
@@ -71,10 +67,8 @@ static int upchan_corr_accumulate(const void* in0_dev, int ntime0, const void* i
     std::lock_guard<std::mutex> lk(g_ccmu);
     UpchanCorrContext& x = g_cc;
     if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized (call xengUpchanCorrInitialize)");
-    if (!in1_dev) { in1_dev = in0_dev; ntime0 = x.ntime; }
-    else if (ntime0 >= x.ntime || ntime0 % x.nupchan)
-        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorr: parts of %d + %d samples: both must be positive multiples of nupchan %d", ntime0,
-                  x.ntime - ntime0, x.nupchan);
+    int rc = gulp_parts("UpchanCorr", in0_dev, &in1_dev, &ntime0, x.ntime, x.nupchan);
+    if (rc) return rc;
     XENG_HIP(hipSetDevice(x.gpu));
     const int c_lo = x.fine_lo / x.nupchan, c_hi = (x.fine_hi - 1) / x.nupchan + 1;
     const int nxb = (x.npad + UCC_SB - 1) / UCC_SB;
@@ -196,13 +190,7 @@ int xengUpchanCorrMark(unsigned long long* ticket) {
     UpchanCorrContext& x = g_cc;
     if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized");
     XENG_HIP(hipSetDevice(x.gpu));
-    hipEvent_t& ev = x.marks[x.nmarks % UpchanCorrContext::NMARK];
-    if (!ev) XENG_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    const unsigned long long upto = stream_clock_now(STREAM_BEAM);      // (read BEFORE the record: everything counted precedes it)
-    XENG_HIP(hipEventRecord(ev, x.stream));
-    stream_clock_external_mark(STREAM_BEAM, ev, upto);
-    *ticket = ++x.nmarks;
-    return XENG_STATUS_SUCCESS;
+    return x.tickets.mark(x.stream, STREAM_BEAM, ticket);
 }
 
 int xengUpchanCorrWait(unsigned long long ticket) {
@@ -212,9 +200,8 @@ int xengUpchanCorrWait(unsigned long long ticket) {
         std::lock_guard<std::mutex> lk(g_ccmu);
         UpchanCorrContext& x = g_cc;
         if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized");
-        if (ticket == 0 || ticket > x.nmarks) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrWait: unknown ticket %llu", ticket);
+        if (!(ev = x.tickets.find(ticket))) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrWait: unknown ticket %llu", ticket);
         gpu = x.gpu;
-        ev = x.marks[(ticket - 1) % UpchanCorrContext::NMARK];  // (a re-recorded slot completes later on the same stream)
     }
     XENG_HIP(hipSetDevice(gpu));
     XENG_HIP(hipEventSynchronize(ev));          // (outside the lock)
@@ -226,22 +213,15 @@ int xengUpchanCorrTicketDone(unsigned long long ticket, int* done) {
     std::lock_guard<std::mutex> lk(g_ccmu);
     UpchanCorrContext& x = g_cc;
     if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized");
-    if (ticket == 0 || ticket > x.nmarks) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrTicketDone: unknown ticket %llu", ticket);
+    const hipEvent_t ev = x.tickets.find(ticket);
+    if (!ev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrTicketDone: unknown ticket %llu", ticket);
     XENG_HIP(hipSetDevice(x.gpu));
-    const hipError_t e = hipEventQuery(x.marks[(ticket - 1) % UpchanCorrContext::NMARK]);
-    if (e != hipSuccess && e != hipErrorNotReady) XENG_HIP(e);
-    if (e == hipErrorNotReady) (void)hipGetLastError();
-    *done = e == hipSuccess;
-    return XENG_STATUS_SUCCESS;
+    return TicketRing::query(ev, done);
 }
 
 int xengUpchanCorrSync(void) {
     std::lock_guard<std::mutex> lk(g_ccmu);
-    UpchanCorrContext& x = g_cc;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    return XENG_STATUS_SUCCESS;
+    return context_sync("UpchanCorr", g_cc.live, g_cc.gpu, g_cc.stream);
 }
 
 int xengUpchanCorrDestroy(void) {

@@ -73,6 +73,25 @@ void stream_clocks_forget(int dev, StreamId which);                 // the strea
 // an event somebody records on the stream anyway (xengBeamformMark) serves as a clock mark: upto = stream_clock_now() read BEFORE the record
 unsigned long long stream_clock_now(StreamId which);
 void stream_clock_external_mark(StreamId which, hipEvent_t ev, unsigned long long upto);
+// Completion tickets on a library stream (xengBeamformMark / Wait / TicketDone and the Upchan, UpchanCorr ones), so that a block
+// can keep several gulps in flight and let go of each gulp's spans when ITS kernels are done: a ring of events, ticket n ->
+// ev[(n - 1) % NMARK].  A ticket whose slot has been re-recorded is NMARK marks old: the newer record of that slot is later on the
+// same stream, so waiting for it is still right.  The caller holds its context's lock (and waits for an event outside it).
+struct TicketRing {
+    static constexpr int NMARK = 64;
+    hipEvent_t ev[NMARK] = {};
+    unsigned long long n = 0;                                       // tickets handed out (the next one is n + 1)
+    // records the next event on `s` and lends it to the stream clock of `which` (stamps of released spans find it)
+    int mark(hipStream_t s, StreamId which, unsigned long long* ticket);
+    hipEvent_t find(unsigned long long ticket) const { return ticket == 0 || ticket > n ? nullptr : ev[(ticket - 1) % NMARK]; }
+    static int query(hipEvent_t e, int* done);                      // never blocks
+    void destroy();                                                 // after the stream has been synchronised and its clock forgotten
+};
+// Upchan / UpchanCorr: a gulp in one part (*in1 null: *in1 = in0, *ntime0 = ntime) or two (samples [*ntime0, ntime) at *in1),
+// each part whole frames of nupchan samples; `who` begins the error message
+int gulp_parts(const char* who, const void* in0, const void** in1, int* ntime0, int ntime, int nupchan);
+// xengUpchanSync / xengUpchanCorrSync with the context's lock held
+int context_sync(const char* who, bool live, int gpu, hipStream_t stream);
 // X-engine side of a stamp (xcorr.hip)
 void xgpu_pending_launch(unsigned long long* seq, unsigned long long* epoch, unsigned long long* nlaunch, unsigned long long* ctx);
 int xgpu_pending_poll(unsigned long long seq, unsigned long long epoch, bool* done, bool* launched, hipEvent_t* ev, int* gpu);

@@ -343,6 +343,44 @@ void EventTimer::destroy() {
     ncreated = npend = 0;
 }
 
+int TicketRing::mark(hipStream_t s, StreamId which, unsigned long long* ticket) {
+    hipEvent_t& e = ev[n % NMARK];
+    if (!e) XENG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    const unsigned long long upto = stream_clock_now(which);        // (read BEFORE the record: everything counted precedes it)
+    XENG_HIP(hipEventRecord(e, s));
+    stream_clock_external_mark(which, e, upto);
+    *ticket = ++n;
+    return XENG_STATUS_SUCCESS;
+}
+
+int TicketRing::query(hipEvent_t e, int* done) {
+    const hipError_t r = hipEventQuery(e);
+    if (r != hipSuccess && r != hipErrorNotReady) XENG_HIP(r);
+    if (r == hipErrorNotReady) (void)hipGetLastError();
+    *done = r == hipSuccess;
+    return XENG_STATUS_SUCCESS;
+}
+
+void TicketRing::destroy() {
+    for (int k = 0; k < NMARK; k++)
+        if (ev[k]) (void)hipEventDestroy(ev[k]);
+}
+
+int gulp_parts(const char* who, const void* in0, const void** in1, int* ntime0, int ntime, int nupchan) {
+    if (!*in1) { *in1 = in0; *ntime0 = ntime; }
+    else if (*ntime0 >= ntime || *ntime0 % nupchan)
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "%s: parts of %d + %d samples: both must be positive multiples of nupchan %d", who, *ntime0,
+                  ntime - *ntime0, nupchan);
+    return XENG_STATUS_SUCCESS;
+}
+
+int context_sync(const char* who, bool live, int gpu, hipStream_t stream) {
+    if (!live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "%s: not initialized", who);
+    XENG_HIP(hipSetDevice(gpu));
+    XENG_HIP(hipStreamSynchronize(stream));
+    return XENG_STATUS_SUCCESS;
+}
+
 }  // namespace xeng
 
 using namespace xeng;

@@ -265,53 +265,104 @@ def test_versioned_weights_are_resplit_only_on_change(gpu):
     gpu.ffi.call("xengBeamformDestroy")
 
 
-def test_completion_tickets_and_their_query(gpu):
-    """xengBeamformMark / Wait / TicketDone: a ticket whose kernels have completed reads done = 1 (and its output is
-    there); unknown tickets are errors; the query never blocks (it is what the blocks call before a blocking Wait)."""
-    import ctypes
-    ntime, nchan, ninput, nbeam = 256, 4, 64, 32
+def ticket_engine(gpu, name):
+    """One small call of each engine on the beamformer's stream, for the ticket test: its context initialised, run(out)
+    enqueues a whole result into the device buffer `out`, check(out) compares it with the restatement; and the names of the
+    backend's ticket methods."""
     rng = np.random.default_rng(11)
+    if name == "Beamform":
+        ntime, nchan, ninput, nbeam = 256, 4, 64, 32
+        vin = rng.integers(0, 256, (ntime, nchan, ninput), dtype=np.uint8)
+        w = block_weights(nchan, nbeam, ninput, seed=3)
+        gpu.ffi.call("xengBeamformInitialize", 0, ninput, nchan, ntime, nbeam, 0)
+        di, dw = gpu.ffi.DeviceBuffer(vin.size).upload(vin), gpu.ffi.DeviceBuffer(w.nbytes).upload(w)
+        expect = orc.beamform(vin, w, ntime, nchan, ninput, nbeam)
+
+        def run(o):
+            gpu.ffi.call("xengBeamformRunVersioned", di.ptr, o.ptr, dw.ptr, 1)
+
+        def check(o):
+            check_beams(o.download(np.complex64).reshape(nchan, nbeam, ntime), expect)
+        return run, check, nchan * nbeam * ntime * 8, ("beam_mark", "beam_wait"), (di, dw)
+    if name == "Upchan":
+        from tests.upchan_ref import upchan_beamform
+        ninput, nchan, nupchan, nbeam, ntime = 20, 3, 8, 3, 80
+        vin = rng.integers(0, 256, (ntime, nchan, ninput), dtype=np.uint8)
+        w = (rng.standard_normal((nchan, nupchan, nbeam, ninput)) + 1j * rng.standard_normal((nchan, nupchan, nbeam, ninput))).astype(np.complex64)
+        gpu.ffi.call("xengUpchanInitialize", 0, ninput, nchan, ntime, nupchan, nbeam, 0)
+        di, dw = gpu.ffi.DeviceBuffer(vin.size).upload(vin), gpu.ffi.DeviceBuffer(w.nbytes).upload(w)
+        expect = upchan_beamform(vin, w, nupchan, nbeam)
+
+        def run(o):
+            gpu.ffi.call("xengUpchanRun", di.ptr, o.ptr, dw.ptr, 1)
+
+        def check(o):
+            check_beams(o.download(np.complex64).reshape(expect.shape), expect)
+        return run, check, expect.size * 8, ("upchan_mark", "upchan_wait"), (di, dw)
+    from tests.upchan_corr_ref import upchan_corr_int
+    ninput, nchan, nupchan, ntime = 40, 3, 2, 30
     vin = rng.integers(0, 256, (ntime, nchan, ninput), dtype=np.uint8)
-    w = block_weights(nchan, nbeam, ninput, seed=3)
-    gpu.ffi.call("xengBeamformInitialize", 0, ninput, nchan, ntime, nbeam, 0)
+    gpu.ffi.call("xengUpchanCorrInitialize", 0, ninput, nchan, ntime, nupchan, 0, nchan * nupchan, 0)
     di = gpu.ffi.DeviceBuffer(vin.size).upload(vin)
-    dw = gpu.ffi.DeviceBuffer(w.nbytes).upload(w)
-    outs = [gpu.ffi.DeviceBuffer(nchan * nbeam * ntime * 8) for _ in range(6)]
+    re, im = upchan_corr_int(vin, nupchan)
+
+    def run(o):                                     # one gulp, one integration
+        gpu.ffi.call("xengUpchanCorrAccumulate", di.ptr)
+        gpu.ffi.call("xengUpchanCorrDump", o.ptr)
+
+    def check(o):
+        v = o.download(np.complex64).reshape(re.shape)
+        assert np.array_equal(v.real, re.astype(np.float32)) and np.array_equal(v.imag, im.astype(np.float32))
+    return run, check, re.size * 8, ("upchan_corr_mark", "upchan_corr_wait"), (di,)
+
+
+@pytest.mark.parametrize("name", ["Beamform", "Upchan", "UpchanCorr"])
+def test_completion_tickets_and_their_query(gpu, name):
+    """xeng<engine>Mark / Wait / TicketDone of the three engines on the beamformer's stream: tickets count from 1 after each
+    Initialize; a ticket whose kernels have completed reads done = 1 (and its output is there), every ticket does after Sync;
+    unknown tickets (0, last + 1) and null pointers are errors; the query never blocks (it is what the blocks call before a
+    blocking Wait)."""
+    import ctypes
+    call = gpu.ffi.call
+    run, check, nout, (mark, wait), _keep = ticket_engine(gpu, name)
+    outs = [gpu.ffi.DeviceBuffer(nout) for _ in range(6)]
     tickets, done = [], ctypes.c_int(-1)
     for o in outs:
-        gpu.ffi.call("xengBeamformRunVersioned", di.ptr, o.ptr, dw.ptr, 1)
+        run(o)
         t = ctypes.c_ulonglong()
-        gpu.ffi.call("xengBeamformMark", ctypes.byref(t))
+        call("xeng%sMark" % name, ctypes.byref(t))
         tickets.append(t.value)
-    assert tickets == sorted(set(tickets)) and tickets[0] >= 1
-    gpu.ffi.call("xengBeamformTicketDone", tickets[-1], ctypes.byref(done))      # returns at once, whatever the answer
+    assert tickets == list(range(1, 7))
+    call("xeng%sTicketDone" % name, tickets[-1], ctypes.byref(done))     # returns at once, whatever the answer
     assert done.value in (0, 1)
-    gpu.ffi.call("xengBeamformWait", tickets[2])
-    for t in tickets[:3]:                                                          # stream order: everything before it too
-        gpu.ffi.call("xengBeamformTicketDone", t, ctypes.byref(done))
+    call("xeng%sWait" % name, tickets[2])
+    for t in tickets[:3]:                                                 # stream order: everything before it too
+        call("xeng%sTicketDone" % name, t, ctypes.byref(done))
         assert done.value == 1
-    expect = orc.beamform(vin, w, ntime, nchan, ninput, nbeam)
-    check_beams(outs[2].download(np.complex64).reshape(nchan, nbeam, ntime), expect)
-    gpu.ffi.call("xengBeamformSync")
-    gpu.ffi.call("xengBeamformTicketDone", tickets[-1], ctypes.byref(done))
+    check(outs[2])
+    call("xeng%sSync" % name)
+    call("xeng%sTicketDone" % name, tickets[-1], ctypes.byref(done))
     assert done.value == 1
-    check_beams(outs[-1].download(np.complex64).reshape(nchan, nbeam, ntime), expect)
+    check(outs[-1])
     for bad in (0, tickets[-1] + 1):
         with pytest.raises(gpu.ffi.XengError):
-            gpu.ffi.call("xengBeamformTicketDone", bad, ctypes.byref(done))
+            call("xeng%sTicketDone" % name, bad, ctypes.byref(done))
         with pytest.raises(gpu.ffi.XengError):
-            gpu.ffi.call("xengBeamformWait", bad)
+            call("xeng%sWait" % name, bad)
     with pytest.raises(gpu.ffi.XengError):
-        gpu.ffi.call("xengBeamformTicketDone", tickets[0], None)
-    # the backend's beam_wait (query first, blocking call only when needed) through both branches
+        call("xeng%sTicketDone" % name, tickets[0], None)
+    with pytest.raises(gpu.ffi.XengError):
+        call("xeng%sMark" % name, None)
+    # the backend's wait (query first, blocking call only when needed) through both branches
     from caltech_bifrost_dsp_amd.backend import HipBackend
     be = HipBackend()
-    gpu.ffi.call("xengBeamformRunVersioned", di.ptr, outs[0].ptr, dw.ptr, 1)
-    tk = be.beam_mark()
-    be.beam_wait(tk)
-    be.beam_wait(tk)                 # already complete: answered by the query
-    check_beams(outs[0].download(np.complex64).reshape(nchan, nbeam, ntime), expect)
-    gpu.ffi.call("xengBeamformDestroy")
+    run(outs[0])
+    tk = getattr(be, mark)()
+    assert tk == tickets[-1] + 1
+    getattr(be, wait)(tk)
+    getattr(be, wait)(tk)            # already complete: answered by the query
+    check(outs[0])
+    call("xeng%sDestroy" % name)
 
 
 @pytest.mark.parametrize("ntime,nchan,ninput,nbeam,kind", [

@@ -255,6 +255,55 @@ def test_skipped_gulps_drop_their_integrations(missing, ndropped):
         assert np.allclose(s.view(np.complex64).reshape(exp.shape), exp, rtol=1e-6)
 
 
+def test_a_failing_gulp_lets_go_of_the_calls_in_flight_only_after_their_kernels():
+    """The third gulp's call fails with two integrations in flight: the block raises, and every span a call in flight holds
+    (its input, its uncommitted output) was still alive when that call's ticket was waited for (the sequence's own exit
+    retires them) or the stream synchronised; let go under a running kernel, their memory would go back to the ring."""
+    import weakref
+
+    class Failing(UpchanCorrOracleBackend):
+        def __init__(self):
+            super().__init__()
+            self.held, self.by_ticket, self.alive = [], {}, []
+
+        def upchan_corr_accumulate(self, in_arr):
+            if len(self.by_ticket) == 2:
+                return 3
+            self.held.append(weakref.ref(in_arr))
+            return super().upchan_corr_accumulate(in_arr)
+
+        def upchan_corr_dump(self, out_arr):
+            self.held.append(weakref.ref(out_arr))
+            return super().upchan_corr_dump(out_arr)
+
+        def upchan_corr_mark(self):
+            t = super().upchan_corr_mark()
+            self.by_ticket[t], self.held = self.held, []
+            return t
+
+        def upchan_corr_wait(self, ticket):
+            self.alive.append(all(r() is not None for r in self.by_ticket.pop(ticket)))
+            super().upchan_corr_wait(ticket)
+
+        def upchan_corr_sync(self):
+            self.alive.extend(all(r() is not None for r in refs) for refs in self.by_ticket.values())
+            self.by_ticket.clear()
+
+    nchan, nstand, N, g = 2, 2, 4, 16
+    ninput = 2 * nstand
+    vin = np.random.default_rng(6).integers(0, 256, (6 * g, nchan, ninput), dtype=np.uint8)
+    r0, r1 = Ring("gpu-input"), Ring("uc-output")
+    be = Failing()
+    uc = UpchanCorr(LOG, r0, r1, nchan=nchan, ninput=ninput, ntime_gulp=g, nupchan=N, nframe_per_integration=g // N, backend=be)
+    sink = Sink(r1, nchan * N * ninput * ninput * 8)
+    src = Source(r0, [(source_header(nchan, nstand, 2), vin, g * nchan * ninput)], wait_readers=1)
+    sink.start()
+    src.start()
+    with pytest.raises(RuntimeError, match="xengUpchanCorrAccumulate returned 3"):
+        uc.main()
+    assert be.alive == [True, True] and not be.by_ticket
+
+
 def test_constructor_rejections():
     be = UpchanCorrOracleBackend()
     ok = dict(nchan=2, ninput=4, ntime_gulp=32, nupchan=8, nframe_per_integration=8)

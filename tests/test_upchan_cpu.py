@@ -245,6 +245,42 @@ def test_gulp_times_follow_the_span_position_after_skipped_gulps():
     assert times == sorted(times) and times[-1] == 1000 + (ngulp - 1) * g
 
 
+def test_a_failing_gulp_waits_for_the_stream_before_the_gulps_in_flight_let_go():
+    """The third run fails with two gulps in flight: the block raises, and it has waited for the stream (upchan_sync) while
+    the spans of those gulps -- inputs and uncommitted outputs -- were still held; let go under a running kernel, their
+    memory would go back to the ring.  Nothing in flight is committed."""
+    import weakref
+
+    class Failing(UpchanOracleBackend):
+        def __init__(self):
+            super().__init__()
+            self.held, self.syncs = [], []          # (input, output) of every run that succeeded; at each sync, which are alive
+
+        def upchan_run(self, in_arr, out_arr, weights, version=0):
+            if len(self.held) == 2:
+                return 3
+            self.held.append((weakref.ref(in_arr), weakref.ref(out_arr)))
+            return super().upchan_run(in_arr, out_arr, weights, version)
+
+        def upchan_sync(self):
+            self.syncs.append([i() is not None and o() is not None for i, o in self.held])
+
+    nchan, nstand, nbeam, N, g = 2, 2, 2, 8, 16
+    ninput = 2 * nstand
+    vin = np.random.default_rng(6).integers(0, 256, (6 * g, nchan, ninput), dtype=np.uint8)
+    r0, r1 = Ring("gpu-input"), Ring("up-output")
+    be = Failing()
+    up = UpchanBeamform(LOG, r0, r1, nchan=nchan, nbeam=nbeam, ninput=ninput, ntime_gulp=g, nupchan=N, backend=be)
+    sink = Sink(r1, (g // N) * nbeam * nchan * N * 8)
+    src = Source(r0, [(source_header(nchan, nstand, 2), vin, g * nchan * ninput)], wait_readers=1)
+    sink.start()
+    src.start()
+    with pytest.raises(RuntimeError, match="xengUpchanRun returned 3"):
+        up.main()
+    assert len(be.held) == 2 and be.syncs == [[True, True]]
+    assert not getattr(be, "waits", [])                             # (nothing was retired: neither gulp was committed)
+
+
 def test_bad_gulp_shape_is_refused():
     with pytest.raises(ValueError):
         UpchanBeamform(LOG, Ring("a"), Ring("b"), nchan=1, nbeam=1, ninput=4, ntime_gulp=30, nupchan=8, backend=UpchanOracleBackend())
