@@ -224,6 +224,11 @@ class HipBackend:
     def upchan_initialize(self, gpu, ninput, nchan, ntime, nupchan, nbeam, nframe_sum):
         return self._lib.xengUpchanInitialize(int(gpu), int(ninput), int(nchan), int(ntime), int(nupchan), int(nbeam), int(nframe_sum))
 
+    def upchan_initialize_dual_pol(self, gpu, ninput, nchan, ntime, nupchan, nbeam, nframe_sum):
+        """The same context in dual-pol mode: beams 2p / 2p+1 are X / Y, and each run writes [XX, YY, Re(XY*), Im(XY*)] per pair
+        and window (include/xeng.h xengUpchanInitializeDualPol); run, mark, wait and sync are the calls above."""
+        return self._lib.xengUpchanInitializeDualPol(int(gpu), int(ninput), int(nchan), int(ntime), int(nupchan), int(nbeam), int(nframe_sum))
+
     def upchan_run(self, in_arr, out_arr, weights, version=0):
         """Enqueue only: upchan_mark / upchan_wait cover it."""
         return self._enq.xengUpchanRun(in_arr.ptr, out_arr.ptr, weights.ptr, int(version))

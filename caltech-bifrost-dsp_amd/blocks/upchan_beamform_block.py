@@ -10,9 +10,16 @@ timed `load_sample`) instead of pointing from RA/Dec, with calibration at fine r
 weight (the reference scales the delay by it, :137); every beam is formed (the reference's TODO at :214-215); the power mode
 writes |v|^2 summed over frames (the reference's output writes np.abs(v)).
 
+dual_pol=True (nframe_sum > 0, nbeam even; xengUpchanInitializeDualPol): beams 2p / 2p+1 are the X / Y pols of pair p, and
+the block emits their 2x2 products per fine channel, [XX, YY, Re(XY*), Im(XY*)] summed over each window, as BeamformSumBeams
+does for the coarse-channel beams (beamform_sum_beams_block.py; the reference's beamformer_sum_test.py:64-77).  The commands
+are unchanged: `beamcoeffs` / `calgains` of beam_id 2p steer X and of 2p+1 steer Y, so Jones-mixed weights (both pols of every
+stand feeding each output pol) stay possible.  XX / YY are bit-identical to the power mode's outputs of beams 2p / 2p+1.
+
 Input: u8 [ntime_gulp][nchan][ninput] spans (the Beamform input).  Output per gulp:
   nframe_sum = 0: cf32 [nframe][nbeam][nchan][nupchan]          (nframe = ntime_gulp / nupchan)
   nframe_sum > 0: f32  [nframe / nframe_sum][nbeam][nchan][nupchan]
+  dual_pol:       f32  [nframe / nframe_sum][nbeam / 2][nchan][nupchan][4]   (header nbeam = nstand = nbeam / 2, npol = 2)
 Fine channel j of coarse channel c is centred at sfreq + c*d + (j - nupchan/2)*d/nupchan, d = bw_hz / nchan.
 """
 import json
@@ -30,8 +37,11 @@ class UpchanBeamform(Block):
     STREAM_DEPTH = 4        # gulps whose kernels may be in flight behind the one being enqueued (in-repo rings)
 
     def __init__(self, log, iring, oring, nchan=256, nbeam=1, ninput=352 * 2, ntime_gulp=2500, nupchan=32, nframe_sum=0,
-                 guarantee=True, core=-1, gpu=-1, etcd_client=None, backend=None):
+                 guarantee=True, core=-1, gpu=-1, etcd_client=None, backend=None, dual_pol=False):
         super(UpchanBeamform, self).__init__(log, iring, oring, guarantee, core, etcd_client=etcd_client)
+        if dual_pol and (nbeam % 2 or not nframe_sum):
+            raise ValueError("UPCHAN: dual_pol needs an even nbeam (X / Y pairs; %d given) and nframe_sum > 0 (%d given)" % (nbeam, nframe_sum))
+        self.dual_pol = bool(dual_pol)
         self._bf = backend if backend is not None else default_backend()
         self.nchan, self.nbeam, self.ninput, self.ntime_gulp = nchan, nbeam, ninput, ntime_gulp
         self.nupchan, self.nframe_sum, self.gpu = nupchan, nframe_sum, gpu
@@ -54,9 +64,12 @@ class UpchanBeamform(Block):
         self.define_command_key('coeffs', type=dict, initial_val={})
         for b in range(nbeam):
             self.update_stats({'cal_gains%d' % b: [False, ] * ninput})
-        rv = self._bf.upchan_initialize(self.gpu, ninput, nchan, ntime_gulp, nupchan, nbeam, nframe_sum)
+        if self.dual_pol:
+            rv = self._bf.upchan_initialize_dual_pol(self.gpu, ninput, nchan, ntime_gulp, nupchan, nbeam, nframe_sum)
+        else:
+            rv = self._bf.upchan_initialize(self.gpu, ninput, nchan, ntime_gulp, nupchan, nbeam, nframe_sum)
         if rv != self._bf.BF_STATUS_SUCCESS:
-            raise RuntimeError("xengUpchanInitialize returned %d: %s" % (rv, self._bf.last_error()))
+            raise RuntimeError("xengUpchanInitialize%s returned %d: %s" % ("DualPol" if self.dual_pol else "", rv, self._bf.last_error()))
 
     def _etcd_callback(self, watchresponse):
         """Every command is enacted as it arrives (all share the `coeffs` key, as Beamform's do)."""
@@ -139,7 +152,9 @@ class UpchanBeamform(Block):
         ohdr = ihdr.copy()
         ohdr.update(nstand=self.nbeam, nbeam=self.nbeam, nupchan=self.nupchan, nframe_sum=self.nframe_sum, nbit=32, npol=1,
                     fine_bw_hz=chan_bw / self.nupchan, fine_sfreq=ihdr['sfreq'] - chan_bw / 2)
-        if self.nframe_sum:
+        if self.dual_pol:                       # (the keys BeamformSumBeams sets on the live power beams)
+            ohdr.update(nstand=self.nbeam // 2, nbeam=self.nbeam // 2, npol=2, complex=True)
+        elif self.nframe_sum:
             ohdr.pop('complex', None)
         else:
             ohdr['complex'] = True
@@ -151,7 +166,10 @@ class UpchanBeamform(Block):
             self._bf.set_device(self.gpu)
         self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
         nout = self.nframe // self.nframe_sum if self.nframe_sum else self.nframe
-        ogulp_size = nout * self.nbeam * self.nchan * self.nupchan * (4 if self.nframe_sum else 8)
+        if self.dual_pol:
+            ogulp_size = nout * (self.nbeam // 2) * self.nchan * self.nupchan * 16
+        else:
+            ogulp_size = nout * self.nbeam * self.nchan * self.nupchan * (4 if self.nframe_sum else 8)
         self.oring.resize(ogulp_size)
         # In-repo rings keep a span's memory alive while it is referenced: several gulps in flight, each output span committed
         # when ITS kernel has completed (tickets).  A bifrost ring: wait for the kernel after every gulp.

@@ -11,6 +11,7 @@ namespace xeng {
 struct UpchanContext {
     bool live = false;
     int gpu = 0, ninput = 0, nchan = 0, ntime = 0, nupchan = 0, nbeam = 0, nframe_sum = 0;
+    bool dual = false;                  // xengUpchanInitializeDualPol: [XX, YY, Re XY*, Im XY*] per pair of beams
     hipStream_t stream = nullptr;
     TicketRing tickets;                 // xengUpchanMark / Wait / TicketDone
 };
@@ -41,6 +42,11 @@ static int upchan_threads(int nbeam, int nupchan) {
 template <int N>
 static void upchan_launch_n(int ppt, dim3 grid, dim3 block, hipStream_t s, const uint8_t* in0, const uint8_t* in1, int ntime0,
                             const float2* w, float* out, const UpchanContext& x, int nframe, int run) {
+    if (x.dual) {                       // (ppt beams per thread: whole pairs, 2 or 4)
+        if (ppt == 2) hipLaunchKernelGGL((upchan_beamform_kernel<N, 2, true>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run);
+        else hipLaunchKernelGGL((upchan_beamform_kernel<N, 4, true>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run);
+        return;
+    }
     switch (ppt) {
     case 1: hipLaunchKernelGGL((upchan_beamform_kernel<N, 1>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run); break;
     case 2: hipLaunchKernelGGL((upchan_beamform_kernel<N, 2>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run); break;
@@ -62,8 +68,11 @@ static int upchan_run(const void* in0_dev, int ntime0, const void* in1_dev, void
     if (rc) return rc;
     XENG_HIP(hipSetDevice(x.gpu));
     const int nframe = x.ntime / x.nupchan, run = upchan_run_frames(x.nframe_sum);
+    // a thread owns ppt beams of one fine channel.  Dual-pol: ppt / 2 whole pairs (1 or 2, as nbeam / 2 * nupchan <= 512) on the
+    // power mode's thread count, so that phase A has as many threads (with fewer, each would run two FFTs per chunk: 1.6x the
+    // time at 4 beams); the threads past the last pair only help with phase A
     const int nthr = upchan_threads(x.nbeam, x.nupchan);
-    const int ppt = (x.nbeam * x.nupchan + nthr - 1) / nthr;
+    const int ppt = x.dual ? (x.nbeam / 2 * x.nupchan + nthr - 1) / nthr * 2 : (x.nbeam * x.nupchan + nthr - 1) / nthr;
     const dim3 grid((unsigned)(x.nchan * ((nframe + run - 1) / run))), block((unsigned)nthr);
     const uint8_t* a = (const uint8_t*)in0_dev;
     const uint8_t* b = (const uint8_t*)in1_dev;
@@ -80,13 +89,7 @@ static int upchan_run(const void* in0_dev, int ntime0, const void* in1_dev, void
     return XENG_STATUS_SUCCESS;
 }
 
-}  // namespace xeng
-
-using namespace xeng;
-
-extern "C" {
-
-int xengUpchanInitialize(int gpu, int ninput, int nchan, int ntime, int nupchan, int nbeam, int nframe_sum) {
+static int upchan_initialize(int gpu, int ninput, int nchan, int ntime, int nupchan, int nbeam, int nframe_sum, bool dual) {
     if (ninput <= 0 || ninput % 4 || nchan <= 0 || ntime <= 0 || nbeam <= 0 || nframe_sum < 0)
         XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: bad sizes ninput=%d nchan=%d ntime=%d nbeam=%d nframe_sum=%d (inputs a multiple of 4)",
                   ninput, nchan, ntime, nbeam, nframe_sum);
@@ -100,6 +103,8 @@ int xengUpchanInitialize(int gpu, int ninput, int nchan, int ntime, int nupchan,
         XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: nbeam %d x nupchan %d above %d", nbeam, nupchan, UC_MAXB);
     if ((long long)nchan * nframe > 0x7FFFFFFFLL || (long long)ninput * nchan > 0x7FFFFFFFLL)
         XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: %d channels x %d inputs x %d frames is more than one launch takes", nchan, ninput, nframe);
+    if (dual && (nbeam % 2 || nframe_sum == 0))
+        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: dual-pol needs an even nbeam (%d) and nframe_sum > 0 (%d)", nbeam, nframe_sum);
     std::lock_guard<std::mutex> lk(g_umu);
     upchan_destroy_locked();
     UpchanContext& x = g_u;
@@ -108,8 +113,23 @@ int xengUpchanInitialize(int gpu, int ninput, int nchan, int ntime, int nupchan,
     int rc = get_stream(STREAM_BEAM, &x.stream);
     if (rc) return rc;
     x.ninput = ninput; x.nchan = nchan; x.ntime = ntime; x.nupchan = nupchan; x.nbeam = nbeam; x.nframe_sum = nframe_sum;
+    x.dual = dual;
     x.live = true;
     return XENG_STATUS_SUCCESS;
+}
+
+}  // namespace xeng
+
+using namespace xeng;
+
+extern "C" {
+
+int xengUpchanInitialize(int gpu, int ninput, int nchan, int ntime, int nupchan, int nbeam, int nframe_sum) {
+    return upchan_initialize(gpu, ninput, nchan, ntime, nupchan, nbeam, nframe_sum, false);
+}
+
+int xengUpchanInitializeDualPol(int gpu, int ninput, int nchan, int ntime, int nupchan, int nbeam, int nframe_sum) {
+    return upchan_initialize(gpu, ninput, nchan, ntime, nupchan, nbeam, nframe_sum, true);
 }
 
 // weights_version: the kernel reads the fp32 weights as they are (no prepared copy), so any version means "as they are now"

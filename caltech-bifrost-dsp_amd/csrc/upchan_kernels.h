@@ -10,16 +10,22 @@
 //   w    cf32[nchan][N][nbeam][ninput]  (indexed by j)
 //   voltage: out cf32[nframe][nbeam][nchan][N],        v[f,b,c,j] = sum_i w[c,j,b,i] X[f,c,i,j]
 //   power:   out f32 [nframe/nframe_sum][nbeam][nchan][N], sum of |v|^2 over nframe_sum consecutive frames
+//   dual-pol: out f32 [nframe/nframe_sum][nbeam/2][nchan][N][4], [XX, YY, Re(XY*), Im(XY*)] of X = v[.,2p,.], Y = v[.,2p+1,.]
 //
 // Decomposition: one work-group per (coarse channel c, run of frames).  It walks the inputs in chunks of UC_IC:
 //   phase A  one thread per (frame, input) of the chunk: N byte loads, decode, radix-2 FFT in registers, the N outputs to LDS
 //            in fine-channel order (xs[frame][input][j], rows padded by one word against bank conflicts)
 //   phase B  thread t owns fine channel j = t % N and beams b = t / N + q * (blockDim / N), q < PPT, for UC_FT frames: its
 //            accumulators stay in registers across all chunks, its weights w[c][j][b][chunk] come straight from memory (16 B
-//            loads, each weight read once per work-group), X[f][i][j] from LDS (one read serves every beam of the thread)
+//            loads, each weight read once per work-group), X[f][i][j] from LDS (one read serves every beam of the thread);
+//            dual-pol (DUAL): PPT / 2 whole pairs instead, beams 2p and 2p+1 of p = t / N + q * (blockDim / N), q < PPT / 2, so the
+//            2x2 products of a pair are formed in the registers that hold both voltages
 // The sum over inputs is a fixed-order fp32 FMA chain per output (chunk by chunk, input by input): no atomics, no
 // scheduling-dependent order, so results are bit-identical from run to run.  A work-group's run of frames is a whole
-// number of power windows (the host picks it), so detection and integration finish in the same registers.
+// number of power windows (the host picks it), so detection and integration finish in the same registers.  The voltage chain
+// and the |v|^2 chain of a beam do not depend on the thread that owns it, so XX / YY of pair p are the power mode's outputs of
+// beams 2p / 2p+1, bit for bit; the cross terms are a fixed-order chain of their own (BeamformSumBeams's convention,
+// oracle orc_beamform_integrate: Re += xr*yr + xi*yi, Im += xi*yr - xr*yi, frame by frame).
 //
 // upchan.hip is compiled with -fno-slp-vectorize (Makefile): otherwise hipcc packs the complex products into the
 // op_sel:[0,1] VOP3P form of DESIGN.md 4.10, which tests/test_isa_rules.py refuses.
@@ -77,7 +83,8 @@ __device__ __forceinline__ int uc_logical_block(int bid, int nwg) {
 // grid: nchan * ceil(nframe / run) work-groups; blockDim a multiple of 64 and of N, <= 256, with blockDim * PPT >= nbeam * N.
 // in1 / ntime0: samples [ntime0, ntime) are at in1 (a gulp in two spans; ntime0 % N == 0); one part: in1 = in0, ntime0 = ntime.
 // run: frames per work-group (UC_FT in voltage mode; in power mode a whole number of nframe_sum windows).
-template <int N, int PPT>
+// DUAL (nframe_sum > 0, nbeam even, PPT even): PPT / 2 pairs per thread, blockDim * PPT / 2 >= nbeam / 2 * N.
+template <int N, int PPT, bool DUAL = false>
 __global__ __launch_bounds__(256) void upchan_beamform_kernel(const uint8_t* __restrict__ in0, const uint8_t* __restrict__ in1, int ntime0,
                                                               const float2* __restrict__ w, float* __restrict__ out, int nchan, int ninput,
                                                               int nbeam, int nframe, int nframe_sum, int run) {
@@ -94,11 +101,15 @@ __global__ __launch_bounds__(256) void upchan_beamform_kernel(const uint8_t* __r
         sincospif(-(float)tid / 32.0f, &s, &co);
         tw[tid] = make_float2(co, s);
     }
+    static_assert(!DUAL || PPT % 2 == 0, "dual-pol threads own whole pairs");
     const int j = tid % N, b0 = tid / N, bs = nthr / N;
     const size_t row = (size_t)nchan * ninput;                  // bytes per sample
-    float pw[PPT];
+    float pw[PPT];                                              // |v|^2 of beam q (XX / YY of pair q / 2 when DUAL)
+    float px[DUAL ? PPT : 1];                                   // Re / Im of X conj(Y) of pair q / 2 (DUAL)
 #pragma unroll
     for (int q = 0; q < PPT; q++) pw[q] = 0.f;
+#pragma unroll
+    for (int q = 0; q < (DUAL ? PPT : 1); q++) px[q] = 0.f;
 
     for (int s0 = r0; s0 < r1; s0 += UC_FT) {
         float2 acc[PPT][UC_FT];
@@ -141,7 +152,7 @@ __global__ __launch_bounds__(256) void upchan_beamform_kernel(const uint8_t* __r
                 float4 wv[PPT];
 #pragma unroll
                 for (int q = 0; q < PPT; q++) {
-                    const int b = b0 + q * bs;
+                    const int b = DUAL ? 2 * (b0 + (q >> 1) * bs) + (q & 1) : b0 + q * bs;
                     wv[q] = b < nbeam ? *reinterpret_cast<const float4*>(w + (((size_t)c * N + j) * nbeam + b) * ninput + i0 + i2)
                                       : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
@@ -163,6 +174,33 @@ __global__ __launch_bounds__(256) void upchan_beamform_kernel(const uint8_t* __r
             }
         }
         // ---- epilogue of the sub-tile: voltages, or |v|^2 into the window sums
+        if constexpr (DUAL) {
+#pragma unroll
+            for (int q = 0; q < PPT; q += 2) {
+                const int p = b0 + (q >> 1) * bs;
+                if (2 * p >= nbeam) continue;
+#pragma unroll
+                for (int f = 0; f < UC_FT; f++) {
+                    const int fg = s0 + f;
+                    if (fg >= r1) break;
+                    const float2 X = acc[q][f], Y = acc[q + 1][f];
+                    pw[q] = __builtin_fmaf(X.x, X.x, pw[q]);
+                    pw[q] = __builtin_fmaf(X.y, X.y, pw[q]);
+                    pw[q + 1] = __builtin_fmaf(Y.x, Y.x, pw[q + 1]);
+                    pw[q + 1] = __builtin_fmaf(Y.y, Y.y, pw[q + 1]);
+                    px[q] = __builtin_fmaf(X.x, Y.x, px[q]);
+                    px[q] = __builtin_fmaf(X.y, Y.y, px[q]);
+                    px[q + 1] = __builtin_fmaf(X.y, Y.x, px[q + 1]);
+                    px[q + 1] = __builtin_fmaf(-X.x, Y.y, px[q + 1]);
+                    if ((fg + 1) % nframe_sum == 0) {
+                        reinterpret_cast<float4*>(out)[(((size_t)(fg / nframe_sum) * (nbeam >> 1) + p) * nchan + c) * N + j] =
+                            make_float4(pw[q], pw[q + 1], px[q], px[q + 1]);
+                        pw[q] = pw[q + 1] = px[q] = px[q + 1] = 0.f;
+                    }
+                }
+            }
+            continue;
+        }
 #pragma unroll
         for (int q = 0; q < PPT; q++) {
             const int b = b0 + q * bs;

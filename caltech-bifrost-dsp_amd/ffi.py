@@ -89,7 +89,7 @@ SYMBOLS = {
     "xengBeamformPacketizeVoltages": [_vp, _vp, _i, _i, _i, _i, _i, _sz, _i, _i, _i, _i, _i, ctypes.c_uint64],
     "xengBeamformSetProfiling": [_i], "xengBeamformGetTimes": [ctypes.POINTER(ctypes.c_double), _pi],
     "xengBeamformGetRouteInfo": [_pi, _pi, _pi],
-    "xengUpchanInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengUpchanRun": [_vp, _vp, _vp, _ll], "xengUpchanRunParts": [_vp, _i, _vp, _vp, _vp, _ll],
+    "xengUpchanInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengUpchanInitializeDualPol": [_i, _i, _i, _i, _i, _i, _i], "xengUpchanRun": [_vp, _vp, _vp, _ll], "xengUpchanRunParts": [_vp, _i, _vp, _vp, _vp, _ll],
     "xengUpchanMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanWait": [ctypes.c_ulonglong], "xengUpchanTicketDone": [ctypes.c_ulonglong, _pi],
     "xengUpchanSync": [], "xengUpchanDestroy": [],
     "xengUpchanCorrInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengUpchanCorrGetInfo": [_pi, _pi],

@@ -434,6 +434,16 @@ int xengBeamformGetRouteInfo(int *tiles_total, int *tiles_bf16, int *outlier_inp
  * nframe_sum not dividing ntime/nupchan, nbeam*nupchan above 1024.  Rejected at Run without a launch: null or misaligned
  * pointers; RunParts: parts that are not positive multiples of nupchan. */
 int xengUpchanInitialize(int gpu, int ninput, int nchan, int ntime, int nupchan, int nbeam, int nframe_sum);
+/* The same context in dual-pol mode (replaces any live one, as Initialize does; either call replaces it again).  Beams 2p / 2p+1
+ * are the X / Y pols of pair p, and Run / RunParts (same input and weight contracts) write their 2x2 products instead of |v|^2,
+ * as BeamformSumBeams does for the coarse-channel beams (beamformer_sum_test.py:64-77):
+ *   out f32[ntime/N/nframe_sum][nbeam/2][nchan][N][4] = [XX, YY, Re(XY*), Im(XY*)], X = v[f,2p,c,j], Y = v[f,2p+1,c,j],
+ *            XX = sum |X|^2, YY = sum |Y|^2, XY* = sum X conj(Y), each sum over the nframe_sum frames of a window
+ * Each 4-float group is 16-byte aligned (one vector store); nothing past the output is written.  XX / YY of pair p are bit-identical
+ * to the power mode's outputs of beams 2p / 2p+1 under the same input and weights; the cross terms are a fixed-order fp32 chain of
+ * their own: bit-identical from run to run.  Rejected at Initialize, before any device is touched: everything Initialize rejects,
+ * an odd nbeam, nframe_sum = 0. */
+int xengUpchanInitializeDualPol(int gpu, int ninput, int nchan, int ntime, int nupchan, int nbeam, int nframe_sum);
 /* weights_version as xengBeamformRunVersioned's; the kernel reads the fp32 weights directly, so it is accepted and ignored */
 int xengUpchanRun(const void *in_dev, void *out_dev, const void *weights_dev, long long weights_version);
 /* one gulp in two spans: samples [0, ntime0) at in0_dev, [ntime0, ntime) at in1_dev */
