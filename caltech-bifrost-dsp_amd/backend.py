@@ -16,6 +16,13 @@ def _dev(a):
     return d if d is not None else a.contents.data
 
 
+def _host_floats(a):
+    """float* to a host float32 array (kept alive by the caller for the call), or NULL for None."""
+    if a is None:
+        return None
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
 class HipBackend:
     BF_STATUS_SUCCESS = ffi.STATUS_SUCCESS
     space_in = "cuda"          # memory space the compute entry points expect
@@ -246,6 +253,15 @@ class HipBackend:
     def upchan_sync(self):
         ffi.call("xengUpchanSync")
 
+    def upchan_set_pfb(self, ntap, coeffs):
+        """The PFB front end (include/xeng.h xengUpchanSetPfb): coeffs float32 [ntap * nupchan] on the host, or None with ntap 1
+        (the plain FFT).  Waits for the context's work in flight; the history starts empty."""
+        return self._lib.xengUpchanSetPfb(int(ntap), _host_floats(coeffs))
+
+    def upchan_reset(self):
+        """The next run sees zeros before its gulp (host state only)."""
+        ffi.check("xengUpchanReset", self._enq.xengUpchanReset())
+
     # ---- upchannelised correlator (UpchanCorr; include/xeng.h "Upchannelised correlator"): a context of its own, its kernels
     # on the beamformer's stream
     def upchan_corr_initialize(self, gpu, ninput, nchan, ntime, nupchan, fine_lo, fine_hi, nstage=0):
@@ -264,7 +280,19 @@ class HipBackend:
         return self._enq.xengUpchanCorrDump(out_arr.ptr)
 
     def upchan_corr_reset(self):
+        """Drops the integration in progress and the PFB history."""
         ffi.check("xengUpchanCorrReset", self._enq.xengUpchanCorrReset())
+
+    def upchan_corr_set_pfb(self, ntap, coeffs):
+        """As upchan_set_pfb, for the UpchanCorr context (include/xeng.h xengUpchanCorrSetPfb)."""
+        return self._lib.xengUpchanCorrSetPfb(int(ntap), _host_floats(coeffs))
+
+    def upchan_corr_prime(self, in_arr):
+        """Enqueue only: the PFB history from this gulp's tail, nothing accumulated; upchan_corr_mark / wait cover it."""
+        return self._enq.xengUpchanCorrPrime(in_arr.ptr)
+
+    def upchan_corr_prime_parts(self, part0, ntime0, part1):
+        return self._enq.xengUpchanCorrPrimeParts(part0.ptr, int(ntime0), part1.ptr)
 
     def upchan_corr_mark(self):
         return self._mark("xengUpchanCorrMark")

@@ -16,6 +16,12 @@ does for the coarse-channel beams (beamform_sum_beams_block.py; the reference's 
 are unchanged: `beamcoeffs` / `calgains` of beam_id 2p steer X and of 2p+1 steer Y, so Jones-mixed weights (both pols of every
 stand feeding each output pol) stay possible.  XX / YY are bit-identical to the power mode's outputs of beams 2p / 2p+1.
 
+pfb_ntap > 1 (or pfb_coeffs given; xengUpchanSetPfb): a polyphase filter bank front end, y[f, n] = sum_k h[k*N + n]
+x[(f - P + 1 + k)*N + n] before each frame's FFT, so that a tone between fine channels no longer leaks into the whole coarse
+channel.  The default coefficients are pfb.pfb_coeffs (sinc * Hamming, sum N).  The history of the last (P - 1)*N samples is
+kept on the device across gulps: it is reset at every sequence start and whenever a gulp does not follow the previous one
+(gulp_time), so that the samples not seen count as zero.  The header then carries `pfb_ntap`.  No reference counterpart.
+
 Input: u8 [ntime_gulp][nchan][ninput] spans (the Beamform input).  Output per gulp:
   nframe_sum = 0: cf32 [nframe][nbeam][nchan][nupchan]          (nframe = ntime_gulp / nupchan)
   nframe_sum > 0: f32  [nframe / nframe_sum][nbeam][nchan][nupchan]
@@ -31,13 +37,14 @@ from ..backend import default_backend
 from ..ndarray import XArray
 from ..proclog import cpu_affinity
 from .block_base import Block, COMMAND_INVALID, COMMAND_OK, InFlight, declare_streams, gulp_time, split_frames, spans_outlive_release
+from .pfb import pfb_config
 
 
 class UpchanBeamform(Block):
     STREAM_DEPTH = 4        # gulps whose kernels may be in flight behind the one being enqueued (in-repo rings)
 
     def __init__(self, log, iring, oring, nchan=256, nbeam=1, ninput=352 * 2, ntime_gulp=2500, nupchan=32, nframe_sum=0,
-                 guarantee=True, core=-1, gpu=-1, etcd_client=None, backend=None, dual_pol=False):
+                 guarantee=True, core=-1, gpu=-1, etcd_client=None, backend=None, dual_pol=False, pfb_ntap=1, pfb_coeffs=None):
         super(UpchanBeamform, self).__init__(log, iring, oring, guarantee, core, etcd_client=etcd_client)
         if dual_pol and (nbeam % 2 or not nframe_sum):
             raise ValueError("UPCHAN: dual_pol needs an even nbeam (X / Y pairs; %d given) and nframe_sum > 0 (%d given)" % (nbeam, nframe_sum))
@@ -48,6 +55,8 @@ class UpchanBeamform(Block):
         if ntime_gulp % nupchan or (nframe_sum and (ntime_gulp // nupchan) % nframe_sum):
             raise ValueError("UPCHAN: gulps of %d samples are not whole frames of %d (or windows of %d frames)" % (ntime_gulp, nupchan, nframe_sum))
         self.nframe = ntime_gulp // nupchan
+        self.pfb_ntap, pfb_h = pfb_config("UPCHAN", pfb_ntap, pfb_coeffs, nupchan, ntime_gulp)
+        self.pfb = pfb_h is not None            # (ntap 1 without coefficients: the plain FFT, no PFB call at all)
         declare_streams(iring, 'beam')          # (the kernel runs on the beamformer's stream)
         declare_streams(oring, 'beam')
         if self.gpu != -1:
@@ -70,6 +79,10 @@ class UpchanBeamform(Block):
             rv = self._bf.upchan_initialize(self.gpu, ninput, nchan, ntime_gulp, nupchan, nbeam, nframe_sum)
         if rv != self._bf.BF_STATUS_SUCCESS:
             raise RuntimeError("xengUpchanInitialize%s returned %d: %s" % ("DualPol" if self.dual_pol else "", rv, self._bf.last_error()))
+        if self.pfb:
+            rv = self._bf.upchan_set_pfb(self.pfb_ntap, pfb_h)
+            if rv != self._bf.BF_STATUS_SUCCESS:
+                raise RuntimeError("xengUpchanSetPfb returned %d: %s" % (rv, self._bf.last_error()))
 
     def _etcd_callback(self, watchresponse):
         """Every command is enacted as it arrives (all share the `coeffs` key, as Beamform's do)."""
@@ -158,6 +171,8 @@ class UpchanBeamform(Block):
             ohdr.pop('complex', None)
         else:
             ohdr['complex'] = True
+        if self.pfb:
+            ohdr['pfb_ntap'] = self.pfb_ntap
         return ohdr
 
     def main(self):
@@ -194,6 +209,7 @@ class UpchanBeamform(Block):
         read_parts = getattr(iseq, 'read_parts', None)
         copy_pending = True
         this_gulp_time = seq0
+        expected = None                         # (PFB) the gulp that continues the history: none at the sequence's start
         with oring.begin_sequence(time_tag=iseq.time_tag, header=json.dumps(self.output_header(ihdr))) as oseq:
             prev_time = time.time()
             for ispan in (read_parts(igulp_size) if read_parts is not None else iseq.read(igulp_size)):
@@ -201,6 +217,10 @@ class UpchanBeamform(Block):
                     continue                    # a short final gulp is skipped (as the reference's gulp_nframe reader does)
                 this_gulp_time = gulp_time(ispan, seq0, igulp_size, self.ntime_gulp, this_gulp_time)
                 self.update_stats({'curr_sample': this_gulp_time})
+                if self.pfb_ntap > 1:
+                    if this_gulp_time != expected:
+                        self._bf.upchan_reset()     # (a new sequence, or gulps not read: what came before counts as zero)
+                    expected = this_gulp_time + self.ntime_gulp
                 if self.update_pending:
                     copy_pending = self._load_pending_weights(this_gulp_time) or copy_pending
                 if copy_pending:

@@ -4,6 +4,7 @@
 #include <mutex>
 
 #include "upchan_kernels.h"
+#include "upchan_pfb.h"
 #include "xeng_common.h"
 
 namespace xeng {
@@ -12,6 +13,7 @@ struct UpchanContext {
     bool live = false;
     int gpu = 0, ninput = 0, nchan = 0, ntime = 0, nupchan = 0, nbeam = 0, nframe_sum = 0;
     bool dual = false;                  // xengUpchanInitializeDualPol: [XX, YY, Re XY*, Im XY*] per pair of beams
+    PfbState pfb;                       // xengUpchanSetPfb (ntap 1 without coefficients: the plain FFT)
     hipStream_t stream = nullptr;
     TicketRing tickets;                 // xengUpchanMark / Wait / TicketDone
 };
@@ -24,6 +26,7 @@ static int upchan_destroy_locked() {
     if (g_u.stream) (void)hipStreamSynchronize(g_u.stream);
     stream_clocks_forget(g_u.gpu, STREAM_BEAM);          // (the mark events lent to the stream clock go away below)
     g_u.tickets.destroy();
+    g_u.pfb.release();
     g_u = UpchanContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -39,19 +42,27 @@ static int upchan_threads(int nbeam, int nupchan) {
     return units >= 256 ? 256 : (units + 63) / 64 * 64;
 }
 
-template <int N>
+// pfb...: nothing (the plain FFT) or one UcPfb (the PFB instantiations)
+template <int N, typename... Pfb>
 static void upchan_launch_n(int ppt, dim3 grid, dim3 block, hipStream_t s, const uint8_t* in0, const uint8_t* in1, int ntime0,
-                            const float2* w, float* out, const UpchanContext& x, int nframe, int run) {
+                            const float2* w, float* out, const UpchanContext& x, int nframe, int run, Pfb... pfb) {
     if (x.dual) {                       // (ppt beams per thread: whole pairs, 2 or 4)
-        if (ppt == 2) hipLaunchKernelGGL((upchan_beamform_kernel<N, 2, true>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run);
-        else hipLaunchKernelGGL((upchan_beamform_kernel<N, 4, true>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run);
+        if (ppt == 2) hipLaunchKernelGGL((upchan_beamform_kernel<N, 2, true, Pfb...>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run, pfb...);
+        else hipLaunchKernelGGL((upchan_beamform_kernel<N, 4, true, Pfb...>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run, pfb...);
         return;
     }
     switch (ppt) {
-    case 1: hipLaunchKernelGGL((upchan_beamform_kernel<N, 1>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run); break;
-    case 2: hipLaunchKernelGGL((upchan_beamform_kernel<N, 2>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run); break;
-    default: hipLaunchKernelGGL((upchan_beamform_kernel<N, 4>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run); break;
+    case 1: hipLaunchKernelGGL((upchan_beamform_kernel<N, 1, false, Pfb...>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run, pfb...); break;
+    case 2: hipLaunchKernelGGL((upchan_beamform_kernel<N, 2, false, Pfb...>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run, pfb...); break;
+    default: hipLaunchKernelGGL((upchan_beamform_kernel<N, 4, false, Pfb...>), grid, block, 0, s, in0, in1, ntime0, w, out, x.nchan, x.ninput, x.nbeam, nframe, x.nframe_sum, run, pfb...); break;
     }
+}
+
+template <int N>
+static void upchan_launch_pfb(int ppt, dim3 grid, dim3 block, hipStream_t s, const uint8_t* in0, const uint8_t* in1, int ntime0,
+                              const float2* w, float* out, const UpchanContext& x, int nframe, int run) {
+    if (x.pfb.h) upchan_launch_n<N>(ppt, grid, block, s, in0, in1, ntime0, w, out, x, nframe, run, x.pfb.args());
+    else upchan_launch_n<N>(ppt, grid, block, s, in0, in1, ntime0, w, out, x, nframe, run);
 }
 
 // Every argument is checked before the context is looked at where it can be (a bad call is told apart from a missing
@@ -79,10 +90,14 @@ static int upchan_run(const void* in0_dev, int ntime0, const void* in1_dev, void
     const float2* w = (const float2*)weights_dev;
     float* o = (float*)out_dev;
     switch (x.nupchan) {
-    case 8: upchan_launch_n<8>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
-    case 16: upchan_launch_n<16>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
-    case 32: upchan_launch_n<32>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
-    default: upchan_launch_n<64>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
+    case 8: upchan_launch_pfb<8>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
+    case 16: upchan_launch_pfb<16>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
+    case 32: upchan_launch_pfb<32>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
+    default: upchan_launch_pfb<64>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
+    }
+    if (x.pfb.hist) {                   // the history for the next gulp, before the tick: the input span's stamp covers the copies
+        XENG_HIP(hipGetLastError());
+        if ((rc = pfb_refresh(x.pfb, x.stream, a, ntime0, b, x.ntime, x.nupchan, (size_t)x.nchan * x.ninput))) return rc;
     }
     stream_tick(STREAM_BEAM);
     XENG_HIP(hipGetLastError());
@@ -142,6 +157,26 @@ int xengUpchanRunParts(const void* in0_dev, int ntime0, const void* in1_dev, voi
     (void)weights_version;
     if (!in1_dev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: null second part");
     return upchan_run(in0_dev, ntime0, in1_dev, out_dev, weights_dev);
+}
+
+int xengUpchanSetPfb(int ntap, const float* coeffs) {
+    int rc = pfb_check_args("UpchanSetPfb", ntap, coeffs);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g_umu);
+    UpchanContext& x = g_u;
+    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized (call xengUpchanInitialize)");
+    if ((rc = pfb_check_sizes("UpchanSetPfb", ntap, coeffs, x.nupchan, x.ntime))) return rc;
+    XENG_HIP(hipSetDevice(x.gpu));
+    XENG_HIP(hipStreamSynchronize(x.stream));   // (launches in flight read the coefficients and the history)
+    return pfb_set("UpchanSetPfb", x.pfb, ntap, coeffs, x.nupchan, (size_t)x.nchan * x.ninput);
+}
+
+int xengUpchanReset(void) {
+    std::lock_guard<std::mutex> lk(g_umu);
+    UpchanContext& x = g_u;
+    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized");
+    x.pfb.valid = false;
+    return XENG_STATUS_SUCCESS;
 }
 
 int xengUpchanMark(unsigned long long* ticket) {

@@ -4,6 +4,7 @@
 #include <mutex>
 
 #include "upchan_corr_kernels.h"
+#include "upchan_pfb.h"
 #include "xeng_common.h"
 
 namespace xeng {
@@ -17,6 +18,7 @@ struct UpchanCorrContext {
     float* acc = nullptr;               // [nfine][ntp][Re, Im][16][64]
     int staged = 0;                     // gulps staged since the last contraction
     bool fresh = true;                  // nothing contracted since the last dump / reset: the next contraction starts from zero
+    PfbState pfb;                       // xengUpchanCorrSetPfb (ntap 1 without coefficients: the plain FFT)
     hipStream_t stream = nullptr;
     TicketRing tickets;                 // xengUpchanCorrMark / Wait / TicketDone
 };
@@ -35,6 +37,7 @@ static int upchan_corr_destroy_locked() {
     g_cc.tickets.destroy();
     if (g_cc.stage) (void)hipFree(g_cc.stage);
     if (g_cc.acc) (void)hipFree(g_cc.acc);
+    g_cc.pfb.release();
     g_cc = UpchanCorrContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -55,8 +58,12 @@ static int upchan_corr_contract_locked(UpchanCorrContext& x) {
 
 template <int N>
 static void upchan_corr_stage_n(dim3 grid, const UpchanCorrContext& x, const uint8_t* in0, const uint8_t* in1, int ntime0, int c_lo) {
-    hipLaunchKernelGGL((upchan_corr_stage_kernel<N>), grid, dim3(UCC_SB), 0, x.stream, in0, in1, ntime0, x.stage, x.nchan, x.ninput, x.npad,
-                       x.nframe, x.nfp, x.fine_stride, x.staged * x.nfp, x.fine_lo, x.fine_hi, c_lo);
+    if (x.pfb.h)
+        hipLaunchKernelGGL((upchan_corr_stage_kernel<N, UcPfb>), grid, dim3(UCC_SB), 0, x.stream, in0, in1, ntime0, x.stage, x.nchan, x.ninput, x.npad,
+                           x.nframe, x.nfp, x.fine_stride, x.staged * x.nfp, x.fine_lo, x.fine_hi, c_lo, x.pfb.args());
+    else
+        hipLaunchKernelGGL((upchan_corr_stage_kernel<N>), grid, dim3(UCC_SB), 0, x.stream, in0, in1, ntime0, x.stage, x.nchan, x.ninput, x.npad,
+                           x.nframe, x.nfp, x.fine_stride, x.staged * x.nfp, x.fine_lo, x.fine_hi, c_lo);
 }
 
 // Every argument is checked before the context is looked at where it can be (a bad call is told apart from a missing
@@ -84,9 +91,29 @@ static int upchan_corr_accumulate(const void* in0_dev, int ntime0, const void* i
     case 32: upchan_corr_stage_n<32>(grid, x, a, b, ntime0, c_lo); break;
     default: upchan_corr_stage_n<64>(grid, x, a, b, ntime0, c_lo); break;
     }
+    if (x.pfb.hist) {                   // the history for the next gulp, before the tick: the input span's stamp covers the copies
+        XENG_HIP(hipGetLastError());
+        if ((rc = pfb_refresh(x.pfb, x.stream, a, ntime0, b, x.ntime, x.nupchan, (size_t)x.nchan * x.ninput))) return rc;
+    }
     stream_tick(STREAM_BEAM);
     XENG_HIP(hipGetLastError());
     if (++x.staged == x.nstage) return upchan_corr_contract_locked(x);
+    return XENG_STATUS_SUCCESS;
+}
+
+// xengUpchanCorrPrime[Parts]: the history from this gulp's tail, nothing staged
+static int upchan_corr_prime(const void* in0_dev, int ntime0, const void* in1_dev) {
+    if (!in0_dev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrPrime: null input");
+    if (in1_dev && ntime0 <= 0) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrPrime: first part of %d samples", ntime0);
+    std::lock_guard<std::mutex> lk(g_ccmu);
+    UpchanCorrContext& x = g_cc;
+    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized (call xengUpchanCorrInitialize)");
+    int rc = gulp_parts("UpchanCorrPrime", in0_dev, &in1_dev, &ntime0, x.ntime, x.nupchan);
+    if (rc || !x.pfb.hist) return rc;   // (no history without taps before the frame's own)
+    XENG_HIP(hipSetDevice(x.gpu));
+    if ((rc = pfb_refresh(x.pfb, x.stream, (const uint8_t*)in0_dev, ntime0, (const uint8_t*)in1_dev, x.ntime, x.nupchan, (size_t)x.nchan * x.ninput)))
+        return rc;
+    stream_tick(STREAM_BEAM);
     return XENG_STATUS_SUCCESS;
 }
 
@@ -181,7 +208,29 @@ int xengUpchanCorrReset(void) {
     if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized");
     x.staged = 0;                       // (staged frames are overwritten by the next gulps; the next contraction starts from zero)
     x.fresh = true;
+    x.pfb.valid = false;                // (the next gulp's first frames see zeros before it)
     return XENG_STATUS_SUCCESS;
+}
+
+int xengUpchanCorrSetPfb(int ntap, const float* coeffs) {
+    int rc = pfb_check_args("UpchanCorrSetPfb", ntap, coeffs);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g_ccmu);
+    UpchanCorrContext& x = g_cc;
+    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized (call xengUpchanCorrInitialize)");
+    if ((rc = pfb_check_sizes("UpchanCorrSetPfb", ntap, coeffs, x.nupchan, x.ntime))) return rc;
+    XENG_HIP(hipSetDevice(x.gpu));
+    XENG_HIP(hipStreamSynchronize(x.stream));   // (launches in flight read the coefficients and the history)
+    return pfb_set("UpchanCorrSetPfb", x.pfb, ntap, coeffs, x.nupchan, (size_t)x.nchan * x.ninput);
+}
+
+int xengUpchanCorrPrime(const void* in_dev) {
+    return upchan_corr_prime(in_dev, 0, nullptr);
+}
+
+int xengUpchanCorrPrimeParts(const void* in0_dev, int ntime0, const void* in1_dev) {
+    if (!in1_dev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrPrime: null second part");
+    return upchan_corr_prime(in0_dev, ntime0, in1_dev);
 }
 
 int xengUpchanCorrMark(unsigned long long* ticket) {

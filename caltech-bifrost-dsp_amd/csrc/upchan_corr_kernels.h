@@ -12,7 +12,8 @@
 // Three kernels, all on one stream:
 //   stage     one thread per (coarse channel, frame, input): N byte loads, decode, radix-2 FFT in registers, the selected fine
 //             channels to stage[c'][frame][input] (fp32 re/im pairs, inputs padded with zeros to a multiple of 32, frames of a
-//             gulp padded with a zero frame to an even count).  A gulp goes to one of nstage slots of frames.
+//             gulp padded with a zero frame to an even count).  A gulp goes to one of nstage slots of frames.  With the PFB front
+//             end (xengUpchanCorrSetPfb) ntap * N byte loads weighted into the FFT's input (uc_pfb_frame, upchan_kernels.h).
 //   contract  one wave per (fine channel, 32x32 tile pair ti >= tj of inputs): the accumulator tile (Re and Im, 16 registers
 //             each) from memory; per staged gulp v_mfma_f32_32x32x2_f32 over its frames two at a time, in frame order, from a
 //             zero C: Re += Xr_i Xr_j, Re += Xi_i Xi_j, Im += Xi_i Xr_j, Im += (-Xr_i) Xi_j; that gulp's sum added to the
@@ -88,11 +89,14 @@ __device__ __forceinline__ int ucc_acc_index(int row, int col) {
 
 // grid: nxb * nfp * (c_hi - c_lo) work-groups of UCC_SB threads, nxb = npad / UCC_SB rounded up; coarse channels [c_lo, c_hi)
 // are those that hold a selected fine channel.  Frame f of the gulp goes to stage frame frame0 + f; frames f >= nframe (the
-// pad frame) and inputs i >= ninput are written as zeros.
-template <int N>
+// pad frame) and inputs i >= ninput are written as zeros.  Pfb: empty (the plain FFT, the kernel as it was before the PFB
+// existed) or one UcPfb (upchan_kernels.h): the item's N samples are the PFB's y[n] (uc_pfb_frame), then the same FFT.
+template <int N, typename... Pfb>
 __global__ __launch_bounds__(UCC_SB) void upchan_corr_stage_kernel(const uint8_t* __restrict__ in0, const uint8_t* __restrict__ in1, int ntime0,
                                                                    float2* __restrict__ stage, int nchan, int ninput, int npad, int nframe, int nfp,
-                                                                   size_t fine_stride, int frame0, int fine_lo, int fine_hi, int c_lo) {
+                                                                   size_t fine_stride, int frame0, int fine_lo, int fine_hi, int c_lo, Pfb... pfb) {
+    constexpr bool PFB = sizeof...(Pfb) > 0;
+    static_assert(sizeof...(Pfb) <= 1, "one UcPfb at most");
     __shared__ float2 tw[32];
     const int tid = threadIdx.x;
     if (N >= 8 && tid < 32) {
@@ -109,13 +113,17 @@ __global__ __launch_bounds__(UCC_SB) void upchan_corr_stage_kernel(const uint8_t
     float2 v[N];
     if (f < nframe && i < ninput) {
         const size_t row = (size_t)nchan * ninput;               // bytes per sample
-        const int t0 = f * N;
-        const uint8_t* p = t0 < ntime0 ? in0 + (size_t)t0 * row : in1 + (size_t)(t0 - ntime0) * row;
-        p += (size_t)c * ninput + i;
+        if constexpr (PFB) {
+            uc_pfb_frame<N>(v, in0, in1, ntime0, f, row, (size_t)c * ninput + i, pfb...);
+        } else {
+            const int t0 = f * N;
+            const uint8_t* p = t0 < ntime0 ? in0 + (size_t)t0 * row : in1 + (size_t)(t0 - ntime0) * row;
+            p += (size_t)c * ninput + i;
 #pragma unroll
-        for (int n = 0; n < N; n++) {
-            const uint32_t u = p[(size_t)n * row];
-            v[uc_bitrev<N>(n)] = make_float2(uc_hi(u), uc_lo(u));
+            for (int n = 0; n < N; n++) {
+                const uint32_t u = p[(size_t)n * row];
+                v[uc_bitrev<N>(n)] = make_float2(uc_hi(u), uc_lo(u));
+            }
         }
         ucc_fft<N>(v, tw);
     } else {

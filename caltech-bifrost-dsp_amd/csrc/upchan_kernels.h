@@ -14,7 +14,8 @@
 //
 // Decomposition: one work-group per (coarse channel c, run of frames).  It walks the inputs in chunks of UC_IC:
 //   phase A  one thread per (frame, input) of the chunk: N byte loads, decode, radix-2 FFT in registers, the N outputs to LDS
-//            in fine-channel order (xs[frame][input][j], rows padded by one word against bank conflicts)
+//            in fine-channel order (xs[frame][input][j], rows padded by one word against bank conflicts); with the PFB front end
+//            (a UcPfb argument, xengUpchanSetPfb) ntap * N byte loads, the tap frames weighted into the FFT's input (uc_pfb_frame)
 //   phase B  thread t owns fine channel j = t % N and beams b = t / N + q * (blockDim / N), q < PPT, for UC_FT frames: its
 //            accumulators stay in registers across all chunks, its weights w[c][j][b][chunk] come straight from memory (16 B
 //            loads, each weight read once per work-group), X[f][i][j] from LDS (one read serves every beam of the thread);
@@ -38,6 +39,7 @@ namespace xeng {
 constexpr int UC_FT = 8;        // frames per sub-tile (accumulators per beam and thread)
 constexpr int UC_IC = 16;       // inputs per chunk (phase A items = UC_FT * UC_IC = 128)
 constexpr int UC_MAXB = 1024;   // nbeam * nupchan per work-group: blockDim <= 256 threads x PPT <= 4
+constexpr int UC_MAXTAP = 8;    // PFB taps (xengUpchanSetPfb, xengUpchanCorrSetPfb)
 
 // twiddles exp(-2 pi i k / 64), k < 32: every N in {8, 16, 32, 64} reads its own as tw[k * 64 / N]
 __device__ __forceinline__ float2 uc_tw(const float2* tw, int k64) { return tw[k64]; }
@@ -73,6 +75,48 @@ __host__ __device__ constexpr int uc_bitrev(int n) {
 __device__ __forceinline__ float uc_hi(uint32_t u) { return (float)((int32_t)(u << 24) >> 28); }
 __device__ __forceinline__ float uc_lo(uint32_t u) { return (float)((int32_t)(u << 28) >> 28); }
 
+// PFB front end (xengUpchanSetPfb, xengUpchanCorrSetPfb): the kernel argument of the PFB instantiations
+struct UcPfb {
+    const float* h;             // [ntap][N] fp32 coefficients
+    const uint8_t* hist;        // u8 [(ntap - 1) * N][nchan][ninput]: the samples right before the gulp (null when ntap = 1)
+    int ntap;                   // 1 <= ntap <= UC_MAXTAP
+    int hist_valid;             // 0: the samples before the gulp count as zero (hist is not read)
+};
+
+// One (frame, input) item through the PFB: v[bitrev(n)] = y[n] = sum_k h[k*N + n] x[(fg - ntap + 1 + k)*N + n], k ascending, one
+// fp32 fmaf chain per component from zero.  Tap frames before the gulp (fs < 0) come from hist (frame fs = its samples
+// [(ntap - 1 + fs) * N, +N)), or are skipped as zeros without hist_valid.  Gulp frames are N-aligned and each part holds whole
+// frames, so every tap frame lies wholly in hist, in0 or in1.  h is read at wave-uniform addresses; `off` is the byte offset of
+// (channel, input) within a sample.
+template <int N>
+__device__ __forceinline__ void uc_pfb_frame(float2 (&v)[N], const uint8_t* __restrict__ in0, const uint8_t* __restrict__ in1, int ntime0,
+                                             int fg, size_t row, size_t off, const UcPfb& q) {
+#pragma unroll
+    for (int n = 0; n < N; n++) v[n] = make_float2(0.f, 0.f);
+    for (int k = 0; k < q.ntap; k++) {
+        const int fs = fg - q.ntap + 1 + k;
+        const uint8_t* p;
+        if (fs >= 0) {
+            const int t0 = fs * N;
+            p = t0 < ntime0 ? in0 + (size_t)t0 * row : in1 + (size_t)(t0 - ntime0) * row;
+        } else if (q.hist_valid) {
+            p = q.hist + (size_t)((q.ntap - 1 + fs) * N) * row;
+        } else {
+            continue;
+        }
+        p += off;
+        const float* hk = q.h + k * N;
+#pragma unroll
+        for (int n = 0; n < N; n++) {
+            const uint32_t u = p[(size_t)n * row];
+            const float c = hk[n];
+            float2& y = v[uc_bitrev<N>(n)];
+            y.x = __builtin_fmaf(c, uc_hi(u), y.x);
+            y.y = __builtin_fmaf(c, uc_lo(u), y.y);
+        }
+    }
+}
+
 // Work-group -> (channel, frame run) with the runs of one channel on one XCD group, next to each other in time: they read the
 // same weights (cdna_hip_programming T1 remap, bijective for any count; a speed choice only).
 __device__ __forceinline__ int uc_logical_block(int bid, int nwg) {
@@ -84,10 +128,14 @@ __device__ __forceinline__ int uc_logical_block(int bid, int nwg) {
 // in1 / ntime0: samples [ntime0, ntime) are at in1 (a gulp in two spans; ntime0 % N == 0); one part: in1 = in0, ntime0 = ntime.
 // run: frames per work-group (UC_FT in voltage mode; in power mode a whole number of nframe_sum windows).
 // DUAL (nframe_sum > 0, nbeam even, PPT even): PPT / 2 pairs per thread, blockDim * PPT / 2 >= nbeam / 2 * N.
-template <int N, int PPT, bool DUAL = false>
+// Pfb: empty -- the plain FFT, with the parameter list (and so the code) the kernel had before the PFB existed -- or one UcPfb,
+// the PFB front end: phase A forms y[n] of uc_pfb_frame before the FFT; phase B and the epilogues are the same.
+template <int N, int PPT, bool DUAL = false, typename... Pfb>
 __global__ __launch_bounds__(256) void upchan_beamform_kernel(const uint8_t* __restrict__ in0, const uint8_t* __restrict__ in1, int ntime0,
                                                               const float2* __restrict__ w, float* __restrict__ out, int nchan, int ninput,
-                                                              int nbeam, int nframe, int nframe_sum, int run) {
+                                                              int nbeam, int nframe, int nframe_sum, int run, Pfb... pfb) {
+    constexpr bool PFB = sizeof...(Pfb) > 0;
+    static_assert(sizeof...(Pfb) <= 1, "one UcPfb at most");
     constexpr int P = N + 1;                                    // LDS row pitch in float2
     __shared__ float2 xs[UC_FT * UC_IC * P];
     __shared__ float2 tw[32];
@@ -126,13 +174,17 @@ __global__ __launch_bounds__(256) void upchan_beamform_kernel(const uint8_t* __r
                 const int fg = s0 + f, i = i0 + ii;
                 float2 v[N];
                 if (fg < r1 && i < ninput) {
-                    const int t0 = fg * N;
-                    const uint8_t* p = t0 < ntime0 ? in0 + (size_t)t0 * row : in1 + (size_t)(t0 - ntime0) * row;
-                    p += (size_t)c * ninput + i;
+                    if constexpr (PFB) {
+                        uc_pfb_frame<N>(v, in0, in1, ntime0, fg, row, (size_t)c * ninput + i, pfb...);
+                    } else {
+                        const int t0 = fg * N;
+                        const uint8_t* p = t0 < ntime0 ? in0 + (size_t)t0 * row : in1 + (size_t)(t0 - ntime0) * row;
+                        p += (size_t)c * ninput + i;
 #pragma unroll
-                    for (int n = 0; n < N; n++) {
-                        const uint32_t u = p[(size_t)n * row];
-                        v[uc_bitrev<N>(n)] = make_float2(uc_hi(u), uc_lo(u));
+                        for (int n = 0; n < N; n++) {
+                            const uint32_t u = p[(size_t)n * row];
+                            v[uc_bitrev<N>(n)] = make_float2(uc_hi(u), uc_lo(u));
+                        }
                     }
                     uc_fft<N>(v, tw);
                 } else {

@@ -91,11 +91,12 @@ SYMBOLS = {
     "xengBeamformGetRouteInfo": [_pi, _pi, _pi],
     "xengUpchanInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengUpchanInitializeDualPol": [_i, _i, _i, _i, _i, _i, _i], "xengUpchanRun": [_vp, _vp, _vp, _ll], "xengUpchanRunParts": [_vp, _i, _vp, _vp, _vp, _ll],
     "xengUpchanMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanWait": [ctypes.c_ulonglong], "xengUpchanTicketDone": [ctypes.c_ulonglong, _pi],
-    "xengUpchanSync": [], "xengUpchanDestroy": [],
+    "xengUpchanSync": [], "xengUpchanDestroy": [], "xengUpchanSetPfb": [_i, ctypes.POINTER(ctypes.c_float)], "xengUpchanReset": [],
     "xengUpchanCorrInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengUpchanCorrGetInfo": [_pi, _pi],
     "xengUpchanCorrAccumulate": [_vp], "xengUpchanCorrAccumulateParts": [_vp, _i, _vp], "xengUpchanCorrDump": [_vp], "xengUpchanCorrReset": [],
     "xengUpchanCorrMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanCorrWait": [ctypes.c_ulonglong], "xengUpchanCorrTicketDone": [ctypes.c_ulonglong, _pi],
-    "xengUpchanCorrSync": [], "xengUpchanCorrDestroy": [],
+    "xengUpchanCorrSync": [], "xengUpchanCorrDestroy": [], "xengUpchanCorrSetPfb": [_i, ctypes.POINTER(ctypes.c_float)],
+    "xengUpchanCorrPrime": [_vp], "xengUpchanCorrPrimeParts": [_vp, _i, _vp],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -139,6 +140,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengBeamformIntegrate", "xengBeamformIntegrateSingleBeam", "xengBeamformPacketizeVoltages", "xengBeamformMark",
                 "xengUpchanRun", "xengUpchanRunParts", "xengUpchanMark", "xengUpchanTicketDone", "xengUpchanCorrAccumulate",
                 "xengUpchanCorrAccumulateParts", "xengUpchanCorrDump", "xengUpchanCorrReset", "xengUpchanCorrMark", "xengUpchanCorrTicketDone", "xengMapAssignI32",
+                "xengUpchanReset", "xengUpchanCorrPrime", "xengUpchanCorrPrimeParts",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

@@ -423,7 +423,8 @@ int xengBeamformGetRouteInfo(int *tiles_total, int *tiles_bf16, int *outlier_inp
  * Beamform context (either may live without the other), whose kernel runs on the beamformer's stream -- rings declared 'beam'
  * cover it, and xengBeamformSync waits for it too.  One kernel per gulp (csrc/upchan_kernels.h):
  *   in       u8[ntime][nchan][ninput], 4+4 bit as Beamform reads it; never written
- *   frames   frame f = samples [f*N, f*N + N) of the gulp (N = nupchan in {8, 16, 32, 64}; frames never cross gulps)
+ *   frames   frame f = samples [f*N, f*N + N) of the gulp (N = nupchan in {8, 16, 32, 64}); with the PFB front end of
+ *            xengUpchanSetPfb (below) it also reads the (P-1)*N samples before it, otherwise frames never cross gulps
  *   FFT      X[f,c,i,k] = sum_n x[f*N+n, c, i] exp(-2 pi i k n / N), forward, no normalisation; fine channel j = (k + N/2) mod N,
  *            so j ascends in frequency: centre sfreq + c*bw/nchan + (j - N/2)*bw/(nchan*N)
  *   weights  cf32[nchan][N][nbeam][ninput], indexed by j; read as they are (16-byte aligned)
@@ -449,6 +450,21 @@ int xengUpchanRun(const void *in_dev, void *out_dev, const void *weights_dev, lo
 /* one gulp in two spans: samples [0, ntime0) at in0_dev, [ntime0, ntime) at in1_dev */
 int xengUpchanRunParts(const void *in0_dev, int ntime0, const void *in1_dev, void *out_dev, const void *weights_dev,
                        long long weights_version);
+/* Polyphase filter bank front end (no reference counterpart: its offline chain is the plain FFT).  P = ntap taps, h = coeffs,
+ * P*N fp32 values on the host, x[t] = the decoded samples of one (coarse channel, input), t counting samples of the continuous
+ * stream.  Output frame f of a gulp reads its own frame and the P-1 frames before it:
+ *   y[f, n] = sum_{k=0}^{P-1} h[k*N + n] x[(f - P + 1 + k)*N + n],  n = 0..N-1, a fixed-order fp32 fmaf chain (k ascending)
+ *   X[f, c, i, k'] = sum_n y[f, n] exp(-2 pi i k' n / N); everything after X (fine channel order, weights, beams, power,
+ *   dual-pol) is unchanged.  Output frame f is still labelled by gulp frame f: the group delay of (P-1)*N/2 samples is not
+ *   compensated.  Samples before the first one the context has seen since SetPfb / Reset count as zero.
+ * The context keeps the last (P-1)*N samples u8[(P-1)*N][nchan][ninput] in a history on the device, refreshed from each gulp's
+ * tail by D2D copies on the beamformer's stream behind its launch.  ntap = 1 with coeffs = NULL: the plain FFT (the state after
+ * Initialize / InitializeDualPol); ntap = 1 with coefficients: a windowed FFT.  Waits for the context's work in flight, then
+ * uploads the coefficients and clears the history.  Rejected before anything is touched: ntap outside 1..8, NULL coeffs with
+ * ntap > 1, a non-finite coefficient, ntime < (P-1)*N; without a context XENG_STATUS_INVALID_STATE. */
+int xengUpchanSetPfb(int ntap, const float *coeffs);
+/* the next Run sees zeros before its gulp (a gap, a new sequence): host state only, nothing is launched */
+int xengUpchanReset(void);
 /* completion tickets for everything enqueued on the beamformer's stream so far, as xengBeamformMark / Wait / TicketDone */
 int xengUpchanMark(unsigned long long *ticket);
 int xengUpchanWait(unsigned long long ticket);
@@ -461,7 +477,8 @@ int xengUpchanDestroy(void);
  * of its own, independent of the Upchan and Beamform contexts, whose kernels run on the beamformer's stream -- rings declared
  * 'beam' cover them, and xengBeamformSync waits for them too.  Three kernels (csrc/upchan_corr_kernels.h):
  *   in       u8[ntime][nchan][ninput], 4+4 bit as Beamform reads it; never written
- *   frames   frame f = samples [f*N, f*N + N) of the gulp (N = nupchan in {1, 2, 4, 8, 16, 32, 64}; frames never cross gulps)
+ *   frames   frame f = samples [f*N, f*N + N) of the gulp (N = nupchan in {1, 2, 4, 8, 16, 32, 64}); with the PFB front end of
+ *            xengUpchanCorrSetPfb (below) it also reads the (P-1)*N samples before it, otherwise frames never cross gulps
  *   FFT      X[f,c,i,k] = sum_n x[f*N+n, c, i] exp(-2 pi i k n / N), forward, no normalisation; fine channel j = (k + N/2) mod N
  *            (ascending in frequency), merged index c*N + j; the fine channels [fine_lo, fine_hi) of that axis are kept, as
  *            c' = c*N + j - fine_lo (the others are never correlated).  The twiddles 1 and -i are applied exactly, so N <= 4 is
@@ -490,8 +507,16 @@ int xengUpchanCorrAccumulate(const void *in_dev);
 int xengUpchanCorrAccumulateParts(const void *in0_dev, int ntime0, const void *in1_dev);
 /* enqueue only: contract what is staged, write the integration to out_dev, start the next one from zero */
 int xengUpchanCorrDump(void *out_dev);
-/* drop the integration in progress (nothing is launched) */
+/* drop the integration in progress and invalidate the PFB history (nothing is launched) */
 int xengUpchanCorrReset(void);
+/* The PFB front end of xengUpchanSetPfb for this context: the same definition, history, rules and checks (CorrInitialize
+ * returns the context to ntap = 1 without coefficients).  Dump leaves the history alone: contiguous integrations continue the
+ * filter. */
+int xengUpchanCorrSetPfb(int ntap, const float *coeffs);
+/* enqueue only: the history from this gulp's tail (one part, or two as AccumulateParts takes them), nothing accumulated --
+ * for a reader that waits for an integration boundary; nothing to do without a history (ntap = 1) */
+int xengUpchanCorrPrime(const void *in_dev);
+int xengUpchanCorrPrimeParts(const void *in0_dev, int ntime0, const void *in1_dev);
 /* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
 int xengUpchanCorrMark(unsigned long long *ticket);
 int xengUpchanCorrWait(unsigned long long ticket);
