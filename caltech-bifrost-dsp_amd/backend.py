@@ -303,7 +303,44 @@ class HipBackend:
     def upchan_corr_sync(self):
         ffi.call("xengUpchanCorrSync")
 
-    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr)
+    # ---- fine-channel power beams from live beams (UpchanSumBeams; include/xeng.h "Fine-channel power beams from live beams"):
+    # a context of its own, its kernels on the beamformer's stream
+    def upchan_sum_beams_initialize(self, gpu, nchan, nbeam, ntime, nupchan, pair0, npair, nframe_sum):
+        return self._lib.xengUpchanSumBeamsInitialize(int(gpu), int(nchan), int(nbeam), int(ntime), int(nupchan), int(pair0), int(npair), int(nframe_sum))
+
+    def upchan_sum_beams_info(self):
+        """(gulps per window, windows per gulp, gulps of the window in progress already run)"""
+        g, w, p = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        ffi.call("xengUpchanSumBeamsGetInfo", ctypes.byref(g), ctypes.byref(w), ctypes.byref(p))
+        return g.value, w.value, p.value
+
+    def upchan_sum_beams_run(self, in_arr, out_arr):
+        """Enqueue only: out_arr (None on a gulp that completes no window) gets f32 [nwin][npair][nchan][nupchan][4];
+        upchan_sum_beams_mark / wait cover it."""
+        return self._enq.xengUpchanSumBeamsRun(in_arr.ptr, out_arr.ptr if out_arr is not None else None)
+
+    def upchan_sum_beams_set_pfb(self, ntap, coeffs):
+        """As upchan_set_pfb, for the UpchanSumBeams context (include/xeng.h xengUpchanSumBeamsSetPfb)."""
+        return self._lib.xengUpchanSumBeamsSetPfb(int(ntap), _host_floats(coeffs))
+
+    def upchan_sum_beams_prime(self, in_arr):
+        """Enqueue only: the PFB history from this gulp's tail, nothing summed; upchan_sum_beams_mark / wait cover it."""
+        return self._enq.xengUpchanSumBeamsPrime(in_arr.ptr)
+
+    def upchan_sum_beams_reset(self):
+        """Drops the window in progress and the PFB history (host state only)."""
+        ffi.check("xengUpchanSumBeamsReset", self._enq.xengUpchanSumBeamsReset())
+
+    def upchan_sum_beams_mark(self):
+        return self._mark("xengUpchanSumBeamsMark")
+
+    def upchan_sum_beams_wait(self, ticket):
+        self._wait("xengUpchanSumBeamsTicketDone", "xengUpchanSumBeamsWait", ticket)
+
+    def upchan_sum_beams_sync(self):
+        ffi.call("xengUpchanSumBeamsSync")
+
+    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

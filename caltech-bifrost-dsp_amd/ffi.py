@@ -97,6 +97,10 @@ SYMBOLS = {
     "xengUpchanCorrMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanCorrWait": [ctypes.c_ulonglong], "xengUpchanCorrTicketDone": [ctypes.c_ulonglong, _pi],
     "xengUpchanCorrSync": [], "xengUpchanCorrDestroy": [], "xengUpchanCorrSetPfb": [_i, ctypes.POINTER(ctypes.c_float)],
     "xengUpchanCorrPrime": [_vp], "xengUpchanCorrPrimeParts": [_vp, _i, _vp],
+    "xengUpchanSumBeamsInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengUpchanSumBeamsGetInfo": [_pi, _pi, _pi],
+    "xengUpchanSumBeamsRun": [_vp, _vp], "xengUpchanSumBeamsSetPfb": [_i, ctypes.POINTER(ctypes.c_float)], "xengUpchanSumBeamsPrime": [_vp],
+    "xengUpchanSumBeamsReset": [], "xengUpchanSumBeamsMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanSumBeamsWait": [ctypes.c_ulonglong],
+    "xengUpchanSumBeamsTicketDone": [ctypes.c_ulonglong, _pi], "xengUpchanSumBeamsSync": [], "xengUpchanSumBeamsDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -141,6 +145,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengUpchanRun", "xengUpchanRunParts", "xengUpchanMark", "xengUpchanTicketDone", "xengUpchanCorrAccumulate",
                 "xengUpchanCorrAccumulateParts", "xengUpchanCorrDump", "xengUpchanCorrReset", "xengUpchanCorrMark", "xengUpchanCorrTicketDone", "xengMapAssignI32",
                 "xengUpchanReset", "xengUpchanCorrPrime", "xengUpchanCorrPrimeParts",
+                "xengUpchanSumBeamsRun", "xengUpchanSumBeamsPrime", "xengUpchanSumBeamsReset", "xengUpchanSumBeamsMark", "xengUpchanSumBeamsTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

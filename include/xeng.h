@@ -524,6 +524,53 @@ int xengUpchanCorrTicketDone(unsigned long long ticket, int *done);
 int xengUpchanCorrSync(void);
 int xengUpchanCorrDestroy(void);
 
+/* ---------------------------------------------------------------- Fine-channel power beams from live beams
+ * UpchanSumBeams (no reference counterpart: the reference's fine-channel beams are offline only): a context of its own,
+ * independent of the Beamform, Upchan and UpchanCorr contexts, whose kernels run on the beamformer's stream -- rings declared
+ * 'beam' cover them, and xengBeamformSync waits for them too.  One kernel per gulp (csrc/upchan_beams_kernels.h):
+ *   in       cf32[nchan][nbeam][ntime], the output of xengBeamformRun in voltage mode, 16-byte aligned; never written
+ *   pairs    p in [pair0, pair0 + npair): X = beam 2p, Y = beam 2p+1 (BeamformSumBeams' convention)
+ *   frames   frame f = samples [f*N, f*N + N) of the gulp (N = nupchan in {8, 16, 32, 64}); with the PFB front end of
+ *            xengUpchanSumBeamsSetPfb (below) it also reads the (P-1)*N samples before it, otherwise frames never cross gulps
+ *   FFT      V[f,c,b,k] = sum_n v[c,b,f*N+n] exp(-2 pi i k n / N), forward, no normalisation; fine channel j = (k + N/2) mod N,
+ *            so j ascends in frequency: centre sfreq + c*bw/nchan + (j - N/2)*bw/(nchan*N)
+ *   products per pair, fine channel and frame, X = V[f,c,2p,j], Y = V[f,c,2p+1,j]: XX = |X|^2, YY = |Y|^2,
+ *            Re XY* = xr*yr + xi*yi, Im XY* = xi*yr - xr*yi
+ *   windows  W = nframe_sum frames, F = ntime/N frames per gulp.  W | F: F/W windows per gulp.  F | W: one window per G = W/F
+ *            gulps, carried in a device accumulator of the context; each gulp's partial sum is a fixed-order chain over its
+ *            frames and the partial sums of a window's gulps are added in order.  Any other W is rejected.
+ *   out      f32[nwin][npair][nchan][N][4] = [XX, YY, Re XY*, Im XY*], nwin = F/W (W | F) or 1 (F | W): the layout of
+ *            xengUpchanInitializeDualPol's output.  16-byte aligned; nothing past it is written.
+ * Numerics: fp32, every sum a fixed-order chain, no atomics: bit-identical from run to run, whatever else runs on the GPU.
+ * In exact arithmetic the output equals xengUpchanInitializeDualPol's on the beamformer's input with the coarse weights copied
+ * to every fine channel (the beamformer, the PFB and the FFT are linear).
+ * Rejected at Initialize, before any device is touched: a non-positive size (pair0 < 0), nupchan outside the set,
+ * ntime % nupchan, W neither dividing nor a multiple of F, pairs outside [0, nbeam/2).  Rejected at Run / Prime without a
+ * launch: null (Run: where the gulp completes a window) or misaligned pointers.  Without a context: XENG_STATUS_INVALID_STATE. */
+int xengUpchanSumBeamsInitialize(int gpu, int nchan, int nbeam, int ntime, int nupchan, int pair0, int npair, int nframe_sum);
+/* the live context's gulps per window (G, 1 when W | F), windows per gulp (F/W, 1 when F | W), and how many gulps of the window
+ * in progress Run has taken (0 .. G-1; the next Run writes out_dev when it is G-1) */
+int xengUpchanSumBeamsGetInfo(int *gulps_per_window, int *windows_per_gulp, int *pos);
+/* enqueue only: one gulp.  out_dev is written by a gulp that completes a window; with G > 1 it may be NULL on the others. */
+int xengUpchanSumBeamsRun(const void *in_dev, void *out_dev);
+/* The PFB front end of xengUpchanSetPfb applied to the complex beam samples: y[f,n] = sum_k h[k*N + n] v[(f-P+1+k)*N + n], a
+ * fixed-order fp32 fmaf chain (k ascending), then the FFT.  The same rules and checks (Initialize returns the context to ntap = 1
+ * without coefficients): waits for the context's work in flight, uploads the coefficients, clears the history; rejects ntap
+ * outside 1..8, NULL coeffs with ntap > 1, a non-finite coefficient, ntime < (P-1)*N.  The history of the last (P-1)*N samples
+ * of every selected (channel, beam) row lives on the device in two halves: the kernel reads one and writes the other. */
+int xengUpchanSumBeamsSetPfb(int ntap, const float *coeffs);
+/* enqueue only: the history from this gulp's tail, nothing summed and the window position unchanged -- for a reader that
+ * waits for a window boundary; nothing to do without a history (ntap = 1) */
+int xengUpchanSumBeamsPrime(const void *in_dev);
+/* drop the window in progress and invalidate the PFB history (host state only, nothing is launched) */
+int xengUpchanSumBeamsReset(void);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengUpchanSumBeamsMark(unsigned long long *ticket);
+int xengUpchanSumBeamsWait(unsigned long long ticket);
+int xengUpchanSumBeamsTicketDone(unsigned long long ticket, int *done);
+int xengUpchanSumBeamsSync(void);
+int xengUpchanSumBeamsDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
