@@ -340,7 +340,51 @@ class HipBackend:
     def upchan_sum_beams_sync(self):
         ffi.call("xengUpchanSumBeamsSync")
 
-    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams)
+    # ---- per-input fine-channel spectra (UpchanSpectra; include/xeng.h "Per-input fine-channel spectra"): a context of its own,
+    # its kernel on the beamformer's stream
+    def upchan_spectra_initialize(self, gpu, ninput, nchan, ntime, nupchan, nframe_sum):
+        return self._lib.xengUpchanSpectraInitialize(int(gpu), int(ninput), int(nchan), int(ntime), int(nupchan), int(nframe_sum))
+
+    def upchan_spectra_info(self):
+        """(gulps per window, windows per gulp, gulps of the window in progress already run)"""
+        g, w, p = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        ffi.call("xengUpchanSpectraGetInfo", ctypes.byref(g), ctypes.byref(w), ctypes.byref(p))
+        return g.value, w.value, p.value
+
+    def upchan_spectra_run(self, in_arr, out_arr):
+        """Enqueue only: out_arr (None on a gulp that completes no window) gets f32 [nwin][2][nchan][nupchan][ninput];
+        upchan_spectra_mark / wait cover it."""
+        return self._enq.xengUpchanSpectraRun(in_arr.ptr, out_arr.ptr if out_arr is not None else None)
+
+    def upchan_spectra_run_parts(self, part0, ntime0, part1, out_arr):
+        """One gulp out of two consecutive spans of the input ring (samples [0, ntime0) in part0), one launch, no gathered copy."""
+        return self._enq.xengUpchanSpectraRunParts(part0.ptr, int(ntime0), part1.ptr, out_arr.ptr if out_arr is not None else None)
+
+    def upchan_spectra_set_pfb(self, ntap, coeffs):
+        """As upchan_set_pfb, for the UpchanSpectra context (include/xeng.h xengUpchanSpectraSetPfb)."""
+        return self._lib.xengUpchanSpectraSetPfb(int(ntap), _host_floats(coeffs))
+
+    def upchan_spectra_prime(self, in_arr):
+        """Enqueue only: the PFB history from this gulp's tail, nothing summed; upchan_spectra_mark / wait cover it."""
+        return self._enq.xengUpchanSpectraPrime(in_arr.ptr)
+
+    def upchan_spectra_prime_parts(self, part0, ntime0, part1):
+        return self._enq.xengUpchanSpectraPrimeParts(part0.ptr, int(ntime0), part1.ptr)
+
+    def upchan_spectra_reset(self):
+        """Drops the window in progress and the PFB history (host state only)."""
+        ffi.check("xengUpchanSpectraReset", self._enq.xengUpchanSpectraReset())
+
+    def upchan_spectra_mark(self):
+        return self._mark("xengUpchanSpectraMark")
+
+    def upchan_spectra_wait(self, ticket):
+        self._wait("xengUpchanSpectraTicketDone", "xengUpchanSpectraWait", ticket)
+
+    def upchan_spectra_sync(self):
+        ffi.call("xengUpchanSpectraSync")
+
+    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

@@ -72,6 +72,7 @@ __device__ __forceinline__ void ucc_fft(float2 (&v)[N], const float2* tw) {
     }
 }
 
+#ifndef UCC_FFT_ONLY     // (defined by a translation unit that wants ucc_fft alone: upchan_spectra_kernels.h)
 // tile pair index tp = ti (ti + 1) / 2 + tj, tj <= ti
 __device__ __forceinline__ void ucc_tile_pair(int tp, int& ti, int& tj) {
     int t = (int)((sqrtf(8.0f * (float)tp + 1.0f) - 1.0f) * 0.5f);
@@ -233,5 +234,7 @@ __global__ __launch_bounds__(256) void upchan_corr_dump_kernel(const float* __re
         out[((size_t)fine * ninput + i) * ninput + j] = make_float2(re, im);
     }
 }
+
+#endif  // UCC_FFT_ONLY
 
 }  // namespace xeng

@@ -101,6 +101,11 @@ SYMBOLS = {
     "xengUpchanSumBeamsRun": [_vp, _vp], "xengUpchanSumBeamsSetPfb": [_i, ctypes.POINTER(ctypes.c_float)], "xengUpchanSumBeamsPrime": [_vp],
     "xengUpchanSumBeamsReset": [], "xengUpchanSumBeamsMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanSumBeamsWait": [ctypes.c_ulonglong],
     "xengUpchanSumBeamsTicketDone": [ctypes.c_ulonglong, _pi], "xengUpchanSumBeamsSync": [], "xengUpchanSumBeamsDestroy": [],
+    "xengUpchanSpectraInitialize": [_i, _i, _i, _i, _i, _i], "xengUpchanSpectraGetInfo": [_pi, _pi, _pi],
+    "xengUpchanSpectraRun": [_vp, _vp], "xengUpchanSpectraRunParts": [_vp, _i, _vp, _vp], "xengUpchanSpectraSetPfb": [_i, ctypes.POINTER(ctypes.c_float)],
+    "xengUpchanSpectraPrime": [_vp], "xengUpchanSpectraPrimeParts": [_vp, _i, _vp], "xengUpchanSpectraReset": [],
+    "xengUpchanSpectraMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanSpectraWait": [ctypes.c_ulonglong],
+    "xengUpchanSpectraTicketDone": [ctypes.c_ulonglong, _pi], "xengUpchanSpectraSync": [], "xengUpchanSpectraDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -146,6 +151,8 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengUpchanCorrAccumulateParts", "xengUpchanCorrDump", "xengUpchanCorrReset", "xengUpchanCorrMark", "xengUpchanCorrTicketDone", "xengMapAssignI32",
                 "xengUpchanReset", "xengUpchanCorrPrime", "xengUpchanCorrPrimeParts",
                 "xengUpchanSumBeamsRun", "xengUpchanSumBeamsPrime", "xengUpchanSumBeamsReset", "xengUpchanSumBeamsMark", "xengUpchanSumBeamsTicketDone",
+                "xengUpchanSpectraRun", "xengUpchanSpectraRunParts", "xengUpchanSpectraPrime", "xengUpchanSpectraPrimeParts", "xengUpchanSpectraReset",
+                "xengUpchanSpectraMark", "xengUpchanSpectraTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

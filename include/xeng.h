@@ -571,6 +571,62 @@ int xengUpchanSumBeamsTicketDone(unsigned long long ticket, int *done);
 int xengUpchanSumBeamsSync(void);
 int xengUpchanSumBeamsDestroy(void);
 
+/* ---------------------------------------------------------------- Per-input fine-channel spectra
+ * UpchanSpectra (no reference counterpart: the reference has no per-input fine-channel product and no interference
+ * statistic): per input and fine channel, the power and the squared power summed over a window of frames -- the fine-resolution
+ * bandpass of every input and, from the two together, the spectral-kurtosis estimator (blocks/spectral_kurtosis.py).  A context
+ * of its own, independent of the Beamform, Upchan, UpchanCorr and UpchanSumBeams contexts, whose kernel runs on the
+ * beamformer's stream -- rings declared 'beam' cover it, and xengBeamformSync waits for it too.  One kernel per gulp
+ * (csrc/upchan_spectra_kernels.h); the channelised data never reaches memory:
+ *   in       u8[ntime][nchan][ninput], 4+4 bit as Beamform reads it; never written
+ *   frames   frame f = samples [f*N, f*N + N) of the gulp (N = nupchan in {1, 2, 4, 8, 16, 32, 64}); with the PFB front end of
+ *            xengUpchanSpectraSetPfb (below) it also reads the (P-1)*N samples before it, otherwise frames never cross gulps
+ *   FFT      X[f,c,i,k] = sum_n x[f*N+n, c, i] exp(-2 pi i k n / N), forward, no normalisation; fine channel j = (k + N/2) mod N
+ *            (ascending in frequency, as UpchanBeamform and UpchanCorr order them).  The twiddles 1 and -i are applied exactly,
+ *            so N <= 4 is exact on integer data.
+ *   moments  p[f,c,j,i] = fmaf(re X, re X, im X * im X) in fp32 (|X|^2: the product of the imaginary part rounded, then one
+ *            fused multiply-add);  S1[w,c,j,i] = sum_f p,  S2[w,c,j,i] = sum_f p * p (the same fp32 p squared), over the
+ *            W = nframe_sum frames of window w
+ *   windows  F = ntime/N frames per gulp.  W | F: F/W windows per gulp.  F | W: one window per G = W/F gulps, carried in a
+ *            device accumulator of the context: gulp 0 of a window assigns it, the following ones add to it in order, the last
+ *            writes accumulator + its own sum to out (no clearing pass; out is not touched by the other gulps).  Any other W
+ *            is rejected.
+ *   out      f32[nwin][2][nchan][N][ninput], plane 0 = S1, plane 1 = S2; nwin = F/W (W | F) or 1 (F | W).  16-byte aligned;
+ *            nothing past it is written.
+ * Numerics: fp32.  The frames f0, f0 + 1, ... of a window (or of a gulp's part of it) are dealt to s = min(4, W, F) slots,
+ * frame f0 + m to slot m mod s; each slot sums its frames in ascending order (S1 += p; S2 = fmaf(p, p, S2), from zero) and the
+ * slots are added in slot order, ((s0 + s1) + s2) + s3; the sums of a window's gulps are added in gulp order.  Every output is
+ * one fixed sum that depends on the data and the configuration only: no atomics, bit-identical from run to run, for whole and
+ * two-part gulps, whatever else runs on the GPU.  Exact on integer data while S2 stays below 2^24 (N <= 4).
+ * Rejected at Initialize, before any device is touched: a non-positive size, nupchan outside the set, ntime % nupchan, W neither
+ * dividing nor a multiple of F, nchan * ninput above 2^24.  Rejected at Run / Prime without a launch: null (out: where the gulp
+ * completes a window) or misaligned pointers; RunParts / PrimeParts: parts that are not positive multiples of nupchan.
+ * Without a context: XENG_STATUS_INVALID_STATE. */
+int xengUpchanSpectraInitialize(int gpu, int ninput, int nchan, int ntime, int nupchan, int nframe_sum);
+/* the live context's gulps per window (G, 1 when W | F), windows per gulp (F/W, 1 when F | W), and how many gulps of the window
+ * in progress Run has taken (0 .. G-1; the next Run writes out_dev when it is G-1) */
+int xengUpchanSpectraGetInfo(int *gulps_per_window, int *windows_per_gulp, int *pos);
+/* enqueue only: one gulp, or one gulp in two spans (samples [0, ntime0) at in0_dev, [ntime0, ntime) at in1_dev).  out_dev is
+ * written by a gulp that completes a window; with G > 1 it may be NULL on the others. */
+int xengUpchanSpectraRun(const void *in_dev, void *out_dev);
+int xengUpchanSpectraRunParts(const void *in0_dev, int ntime0, const void *in1_dev, void *out_dev);
+/* The PFB front end of xengUpchanSetPfb for this context: the same definition, history (u8[(P-1)*N][nchan][ninput] on the
+ * device, refreshed from each gulp's tail behind its launch), rules and checks (Initialize returns the context to ntap = 1
+ * without coefficients). */
+int xengUpchanSpectraSetPfb(int ntap, const float *coeffs);
+/* enqueue only: the history from this gulp's tail (one part, or two as RunParts takes them), nothing summed and the window
+ * position unchanged -- for a reader that waits for a window boundary; nothing to do without a history (ntap = 1) */
+int xengUpchanSpectraPrime(const void *in_dev);
+int xengUpchanSpectraPrimeParts(const void *in0_dev, int ntime0, const void *in1_dev);
+/* drop the window in progress and invalidate the PFB history (host state only, nothing is launched) */
+int xengUpchanSpectraReset(void);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengUpchanSpectraMark(unsigned long long *ticket);
+int xengUpchanSpectraWait(unsigned long long ticket);
+int xengUpchanSpectraTicketDone(unsigned long long ticket, int *done);
+int xengUpchanSpectraSync(void);
+int xengUpchanSpectraDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
