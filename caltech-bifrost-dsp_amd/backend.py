@@ -384,7 +384,49 @@ class HipBackend:
     def upchan_spectra_sync(self):
         ffi.call("xengUpchanSpectraSync")
 
-    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra)
+    # ---- incoherent dedispersion of fine-channel power beams (BeamDedisperse; include/xeng.h "Incoherent dedispersion of
+    # fine-channel power beams"): a context of its own, its kernels on the beamformer's stream
+    def dedisp_initialize(self, gpu, npair, nfine, nwin, ndm, max_delay, nprod):
+        return self._lib.xengDedispInitialize(int(gpu), int(npair), int(nfine), int(nwin), int(ndm), int(max_delay), int(nprod))
+
+    def dedisp_set_delays(self, delays):
+        """delays: host int32 [ndm][nfine], C-contiguous, in windows.  Waits for the context's work in flight; clears the history."""
+        return self._lib.xengDedispSetDelays(delays.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+
+    def dedisp_set_weights(self, weights):
+        """weights: host float32 [nfine] or None (all ones).  Waits for the context's work in flight; the history stays."""
+        return self._lib.xengDedispSetWeights(_host_floats(weights))
+
+    def dedisp_run(self, in_arr, nwin_call, out_arr):
+        """Enqueue only: f32 [nwin_call][npair][nfine][4] in, f32 [nwin_call][npair][ndm][nprod] out; dedisp_mark / wait cover it."""
+        return self._enq.xengDedispRun(in_arr.ptr, int(nwin_call), out_arr.ptr)
+
+    def dedisp_reset(self):
+        """The next input counts as window 0 of an empty history (host state only)."""
+        ffi.check("xengDedispReset", self._enq.xengDedispReset())
+
+    def dedisp_info(self):
+        """(largest delay of the table in use, -1 without one; windows taken since the last reset)"""
+        s, n = ctypes.c_int(), ctypes.c_longlong()
+        ffi.call("xengDedispGetInfo", ctypes.byref(s), ctypes.byref(n))
+        return s.value, n.value
+
+    def dedisp_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the history hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengDedispCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def dedisp_mark(self):
+        return self._mark("xengDedispMark")
+
+    def dedisp_wait(self, ticket):
+        self._wait("xengDedispTicketDone", "xengDedispWait", ticket)
+
+    def dedisp_sync(self):
+        ffi.call("xengDedispSync")
+
+    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

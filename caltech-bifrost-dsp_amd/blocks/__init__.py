@@ -16,7 +16,9 @@ from .tbf_source_block import TbfSource
 from .upchan_corr_block import UpchanCorr
 from .upchan_sum_beams_block import UpchanSumBeams
 from .upchan_spectra_block import UpchanSpectra
+from .beam_dedisperse_block import BeamDedisperse
+from .dedisp import dm_delays
 from .spectral_kurtosis import incoherent_beam, sk_flags, sk_limits, spectral_kurtosis
 
-__all__ = ["Block", "Corr", "CorrAcc", "Beamform", "BeamformSumBeams", "Copy", "CorrSubsel", "CorrOutputFull", "Snap2Ingest", "BeamformOutput", "CorrOutputPart", "BeamformVlbiOutput", "UpchanBeamform", "TbfSource", "UpchanCorr", "UpchanSumBeams", "UpchanSpectra", "spectral_kurtosis", "sk_limits", "sk_flags", "incoherent_beam", "regtile_index", "tri_index",
+__all__ = ["Block", "Corr", "CorrAcc", "Beamform", "BeamformSumBeams", "Copy", "CorrSubsel", "CorrOutputFull", "Snap2Ingest", "BeamformOutput", "CorrOutputPart", "BeamformVlbiOutput", "UpchanBeamform", "TbfSource", "UpchanCorr", "UpchanSumBeams", "UpchanSpectra", "BeamDedisperse", "dm_delays", "spectral_kurtosis", "sk_limits", "sk_flags", "incoherent_beam", "regtile_index", "tri_index",
            "COMMAND_OK", "COMMAND_NOT_RECOGNIZED", "COMMAND_WRONG_TYPE", "COMMAND_INVALID"]

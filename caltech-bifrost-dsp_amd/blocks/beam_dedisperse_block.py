@@ -1,0 +1,253 @@
+"""BeamDedisperse: incoherent dedispersion of fine-channel power beams over a grid of DM trials.
+
+Reads the output ring of UpchanSumBeams (live) or of UpchanBeamform(dual_pol=True) (from dumps), in device space: spans of
+  f32 [nwin][npair][nchan][nupchan][4] = [XX, YY, Re(XY*), Im(XY*)]
+and writes one output span per input span,
+  f32 [nwin][npair][ndm][nprod],   nprod = 1 (stokes='I': XX + YY) or 4 (stokes='full': the four words, each by itself)
+where output window n of trial d is the sum over the nfine = nchan*nupchan fine channels of window n - (S - s[d][q]) of channel
+q, times the channel's weight (xengDedisp*, csrc/dedisp_kernels.h; the definition is in include/xeng.h).  s = dm_delays(...) is
+built per sequence from the header's fine-channel frequencies and the window length tsamp = acc_len * nchan / bw_hz; S = max s
+is the block's latency in windows (`dedisp_latency` in the output header): all trials share one time axis, output n is the
+pulse that reached the top fine channel at window n - S, and the first S windows of a sequence are partial sums.  The history
+lives on the device across spans.  No reference counterpart: the reference has no dedisperser.
+
+A new sequence or a gap in the input (spans this reader never saw) resets the context; after a gap the output restarts in a
+sequence of its own (UpchanSumBeams' rule).  A `weights` command (a list of nfine finite numbers; 0 leaves a channel out, e.g.
+one flagged by UpchanSpectra's spectral kurtosis) takes effect at the next span, on the history already held too.
+"""
+import collections
+import json
+import time
+
+import numpy as np
+
+from ..backend import default_backend
+from ..ndarray import XArray
+from ..proclog import cpu_affinity
+from .block_base import Block, declare_streams, gulp_time, spans_outlive_release
+from .dedisp import dm_delays
+
+STOKES = {'I': 1, 'full': 4}
+
+
+class BeamDedisperse(Block):
+    STREAM_DEPTH = 4        # spans whose kernels may be in flight behind the one being enqueued (in-repo rings)
+
+    def __init__(self, log, iring, oring, npair, nchan, nupchan, nwin, dms, max_delay=None, weights=None, stokes='I', guarantee=True,
+                 core=-1, gpu=-1, etcd_client=None, backend=None):
+        super(BeamDedisperse, self).__init__(log, iring, oring, guarantee, core, etcd_client=etcd_client)
+        who = "BEAM_DEDISPERSE"
+        if stokes not in STOKES:
+            raise ValueError("%s: stokes %r not one of %s" % (who, stokes, sorted(STOKES)))
+        if min(npair, nchan, nupchan, nwin) <= 0:
+            raise ValueError("%s: sizes npair=%r nchan=%r nupchan=%r nwin=%r must be positive" % (who, npair, nchan, nupchan, nwin))
+        self.dms = np.asarray(dms, np.float64).reshape(-1)
+        if self.dms.size == 0 or not np.all(np.isfinite(self.dms)) or self.dms.min() < 0:
+            raise ValueError("%s: the DM trials must be a non-empty list of finite, non-negative numbers" % who)
+        if max_delay is not None and max_delay < 0:
+            raise ValueError("%s: max_delay %r is negative" % (who, max_delay))
+        self.npair, self.nchan, self.nupchan, self.nwin, self.gpu = npair, nchan, nupchan, nwin, gpu
+        self.nfine, self.ndm, self.nprod, self.stokes = nchan * nupchan, int(self.dms.size), STOKES[stokes], stokes
+        self.max_delay = max_delay
+        self._weights = self._checked_weights(weights) if weights is not None else None
+        self._bf = backend if backend is not None else default_backend()
+        declare_streams(iring, 'beam')          # (the kernels run on the beamformer's stream)
+        declare_streams(oring, 'beam', 'copy')  # (the kernel writes the span itself, or a copy does from a device buffer)
+        if self.gpu != -1:
+            self._bf.set_device(self.gpu)
+        self.define_command_key('weights', type=list, condition=lambda v: self._checked_weights(v, quiet=True) is not None)
+        self.update_stats({'nwindow': 0, 'ngap': 0, 'dedisp_latency': -1})
+        self._ctx_delay = None                  # max_delay of the live context
+        if max_delay is not None:
+            self._initialize(max_delay)
+
+    def _checked_weights(self, w, quiet=False):
+        try:
+            a = np.ascontiguousarray(w, np.float32).reshape(-1)
+            ok = a.size == self.nfine and bool(np.all(np.isfinite(a)))
+        except (TypeError, ValueError):
+            a, ok = None, False
+        if ok:
+            return a
+        if quiet:
+            return None
+        raise ValueError("BEAM_DEDISPERSE: the weights must be %d finite numbers" % self.nfine)
+
+    def _initialize(self, max_delay):
+        rv = self._bf.dedisp_initialize(self.gpu, self.npair, self.nfine, self.nwin, self.ndm, max_delay, self.nprod)
+        if rv != self._bf.BF_STATUS_SUCCESS:
+            raise RuntimeError("xengDedispInitialize returned %d: %s" % (rv, self._bf.last_error()))
+        self._ctx_delay = max_delay
+        if self._weights is not None:
+            self._set_weights()
+
+    def _set_weights(self):
+        rv = self._bf.dedisp_set_weights(self._weights)
+        if rv != self._bf.BF_STATUS_SUCCESS:
+            raise RuntimeError("xengDedispSetWeights returned %d: %s" % (rv, self._bf.last_error()))
+
+    def _check_header(self, ihdr):
+        """The dual-pol fine-channel power beams of UpchanSumBeams / UpchanBeamform(dual_pol=True) only."""
+        who = "BEAM_DEDISPERSE"
+        if ihdr.get('nchan') != self.nchan or ihdr.get('nbeam') != self.npair:
+            raise ValueError("%s: %r channels x %r pairs in the header, %d x %d configured" % (who, ihdr.get('nchan'), ihdr.get('nbeam'), self.nchan,
+                                                                                              self.npair))
+        if ihdr.get('npol') != 2 or ihdr.get('nbit') != 32:
+            raise ValueError("%s: the input is not dual-pol f32 power beams (npol %r, nbit %r)" % (who, ihdr.get('npol'), ihdr.get('nbit')))
+        if ihdr.get('nupchan') != self.nupchan:
+            raise ValueError("%s: nupchan %r in the header, %d configured" % (who, ihdr.get('nupchan'), self.nupchan))
+        for k in ('nframe_sum', 'fine_sfreq', 'fine_bw_hz', 'bw_hz'):
+            if not isinstance(ihdr.get(k), (int, float)) or isinstance(ihdr.get(k), bool) or (k != 'fine_sfreq' and not ihdr[k] > 0):
+                raise ValueError("%s: the header's '%s' is %r: not fine-channel power beams summed over windows" % (who, k, ihdr.get(k)))
+        if 'ndm' in ihdr:
+            raise ValueError("%s: the input carries 'ndm': it has been dedispersed already" % who)
+        acc_len = ihdr['nframe_sum'] * self.nupchan
+        if ihdr.get('acc_len', acc_len) != acc_len:
+            raise ValueError("%s: acc_len %r in the header is not nframe_sum x nupchan = %d" % (who, ihdr.get('acc_len'), acc_len))
+        return acc_len
+
+    def delays(self, ihdr, acc_len):
+        """(int32 [ndm][nfine], tsamp): the table of a sequence from its header."""
+        tsamp = acc_len * self.nchan / ihdr['bw_hz']
+        freqs = ihdr['fine_sfreq'] + ihdr['fine_bw_hz'] * np.arange(self.nfine)
+        return np.ascontiguousarray(dm_delays(freqs, self.dms, tsamp)), tsamp
+
+    def output_header(self, ihdr, start, S, tsamp):
+        ohdr = ihdr.copy()
+        ohdr.update(ndm=self.ndm, dms=self.dms.tolist(), dedisp_latency=int(S), nprod=self.nprod, tsamp=tsamp, seq0=start)
+        return ohdr
+
+    def main(self):
+        cpu_affinity.set_core(self.core)
+        if self.gpu != -1:
+            self._bf.set_device(self.gpu)
+        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
+        self._oshape = (self.nwin, self.npair, self.ndm, self.nprod)
+        ogulp_size = int(np.prod(self._oshape)) * 4
+        self.oring.resize(ogulp_size)
+        # Streaming, tickets and the staged copy into a pinned-host output ring: as UpchanSumBeams (upchan_sum_beams_block.py)
+        streaming = spans_outlive_release(self.iring, self.oring)
+        self._staged = streaming and self.oring.space == 'cuda_host' and hasattr(self._bf, 'copy_async')
+        self._dev = None if streaming else XArray(shape=self._oshape, dtype=np.float32, space=self._bf.space_in)
+        self._stages_free = []
+        pending = collections.deque()           # (ticket, output span, input kept alive, device buffer or None)
+        copying = collections.deque()           # (stamp of the copy, output span, device buffer)
+
+        def finish_copies(keep):
+            while copying and (len(copying) > keep or self._bf.copy_done(copying[0][0])):
+                stamp, osp, stage = copying.popleft()
+                self._bf.copy_wait(stamp)       # (returns at once when it is done)
+                osp.close()
+                self._stages_free.append(stage)
+
+        def retire(keep):
+            while len(pending) > keep:
+                ticket, osp, _, stage = pending.popleft()
+                self._bf.dedisp_wait(ticket)
+                if stage is None:
+                    osp.close()
+                else:
+                    copying.append((self._bf.copy_async(osp.data, stage), osp, stage))
+            finish_copies(2 if keep else 0)
+
+        try:
+            with self.oring.begin_writing() as oring:
+                for iseq in self.iring.read(guarantee=self.guarantee):
+                    self._sequence(iseq, oring, ogulp_size, streaming, pending, retire)
+        finally:
+            # (spans of kernels in flight are not released by an exception before the stream is idle)
+            if pending or copying:
+                try:
+                    self._bf.dedisp_sync()
+                    for stamp, _, _ in copying:
+                        self._bf.copy_wait(stamp)
+                except Exception:
+                    pass
+                pending.clear()
+                copying.clear()
+
+    def _load_pending_weights(self):
+        """A `weights` command: on the device before the next span is enqueued (SetWeights waits for the spans in flight)."""
+        self.update_command_vals()
+        w = self.command_vals.get('weights')
+        if w is not None:
+            self._weights = self._checked_weights(w)
+            self._set_weights()
+
+    def _sequence(self, iseq, oring, ogulp_size, streaming, pending, retire):
+        ihdr = json.loads(iseq.header.tostring())
+        self.sequence_proclog.update(ihdr)
+        acc_len = self._check_header(ihdr)
+        table, tsamp = self.delays(ihdr, acc_len)
+        S = int(table.max())
+        if self.max_delay is not None and S > self.max_delay:
+            raise ValueError("BEAM_DEDISPERSE: DM %g needs a delay of %d windows of %g s, max_delay is %d" % (self.dms.max(), S, tsamp, self.max_delay))
+        retire(0)
+        if self.max_delay is None and self._ctx_delay != S:
+            self._initialize(S)                 # (a history as long as this sequence's table needs)
+        rv = self._bf.dedisp_set_delays(table)  # (clears the history and the window count: a new sequence starts from nothing)
+        if rv != self._bf.BF_STATUS_SUCCESS:
+            raise RuntimeError("xengDedispSetDelays returned %d: %s" % (rv, self._bf.last_error()))
+        self.update_stats({'dedisp_latency': S})
+        seq0 = ihdr['seq0']
+        ntime_span = self.nwin * acc_len        # samples of the beamformer's clock per span
+        igulp_size = self.nwin * self.npair * self.nfine * 16
+        this_gulp_time = seq0
+        expected = seq0
+        oseq = None
+        try:
+            prev_time = time.time()
+            for ispan in iseq.read(igulp_size):
+                if ispan.size < igulp_size:
+                    continue                    # a short final span is skipped (as the reference's gulp_nframe reader does)
+                this_gulp_time = gulp_time(ispan, seq0, igulp_size, ntime_span, this_gulp_time)
+                if this_gulp_time != expected:
+                    # windows this reader never saw: what the history holds does not line up with what comes now
+                    self._bf.dedisp_reset()
+                    self.update_stats({'ngap': self.stats['ngap'] + 1})
+                    self.log.warning("BEAM_DEDISPERSE >> samples [%d, %d) were not read: the history starts again" % (expected, this_gulp_time))
+                    if oseq is not None:
+                        retire(0)
+                        oseq.end()
+                        oseq = None
+                expected = this_gulp_time + ntime_span
+                self.update_stats({'curr_sample': this_gulp_time})
+                if self.update_pending:
+                    self._load_pending_weights()
+                held = ispan.data
+                if oseq is None:
+                    oseq = oring.begin_sequence(time_tag=this_gulp_time, header=json.dumps(self.output_header(ihdr, this_gulp_time, S, tsamp)))
+                curr_time = time.time()
+                acquire_time = curr_time - prev_time
+                prev_time = curr_time
+                ospan = oseq.reserve(ogulp_size)
+                stage = None
+                try:
+                    if self._staged:
+                        stage = self._stages_free.pop() if self._stages_free else XArray(shape=(ogulp_size,), dtype=np.uint8, space=self._bf.space_in)
+                    target = stage if stage is not None else (ospan.data if streaming else self._dev)
+                    rv = self._bf.dedisp_run(held, self.nwin, target)
+                    if rv != self._bf.BF_STATUS_SUCCESS:
+                        raise RuntimeError("xengDedispRun returned %d: %s" % (rv, self._bf.last_error()))
+                    self.update_stats({'nwindow': self.stats['nwindow'] + self.nwin, 'last_end_sample': this_gulp_time + ntime_span})
+                    osp, ospan = ospan, None
+                    if streaming:
+                        pending.append((self._bf.dedisp_mark(), osp, held, stage))
+                        retire(self.STREAM_DEPTH)
+                    else:
+                        self._bf.dedisp_sync()
+                        try:
+                            osp.data_view(np.float32).reshape(self._oshape)[...] = self._dev      # (synchronous copy)
+                        finally:
+                            osp.close()
+                finally:
+                    if ospan is not None:
+                        ospan.close()
+                curr_time = time.time()
+                process_time = curr_time - prev_time
+                prev_time = curr_time
+                self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
+        finally:
+            retire(0)                           # every call in flight is complete (and every output span committed) first
+            if oseq is not None:
+                oseq.end()

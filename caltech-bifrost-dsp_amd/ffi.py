@@ -106,6 +106,10 @@ SYMBOLS = {
     "xengUpchanSpectraPrime": [_vp], "xengUpchanSpectraPrimeParts": [_vp, _i, _vp], "xengUpchanSpectraReset": [],
     "xengUpchanSpectraMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanSpectraWait": [ctypes.c_ulonglong],
     "xengUpchanSpectraTicketDone": [ctypes.c_ulonglong, _pi], "xengUpchanSpectraSync": [], "xengUpchanSpectraDestroy": [],
+    "xengDedispInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengDedispSetDelays": [_pi], "xengDedispSetWeights": [ctypes.POINTER(ctypes.c_float)],
+    "xengDedispRun": [_vp, _i, _vp], "xengDedispReset": [], "xengDedispGetInfo": [_pi, ctypes.POINTER(ctypes.c_longlong)],
+    "xengDedispMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengDedispWait": [ctypes.c_ulonglong], "xengDedispTicketDone": [ctypes.c_ulonglong, _pi],
+    "xengDedispSync": [], "xengDedispDestroy": [], "xengDedispCheckGuards": [_pi],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -153,6 +157,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengUpchanSumBeamsRun", "xengUpchanSumBeamsPrime", "xengUpchanSumBeamsReset", "xengUpchanSumBeamsMark", "xengUpchanSumBeamsTicketDone",
                 "xengUpchanSpectraRun", "xengUpchanSpectraRunParts", "xengUpchanSpectraPrime", "xengUpchanSpectraPrimeParts", "xengUpchanSpectraReset",
                 "xengUpchanSpectraMark", "xengUpchanSpectraTicketDone",
+                "xengDedispRun", "xengDedispReset", "xengDedispMark", "xengDedispTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

@@ -627,6 +627,58 @@ int xengUpchanSpectraTicketDone(unsigned long long ticket, int *done);
 int xengUpchanSpectraSync(void);
 int xengUpchanSpectraDestroy(void);
 
+/* ---------------------------------------------------------------- Incoherent dedispersion of fine-channel power beams
+ * BeamDedisperse (no reference counterpart: the reference has no dedisperser): a direct (brute-force) incoherent dedisperser
+ * over a caller-supplied grid of DM trials, streaming across calls through a history ring on the device.  A context of its own,
+ * independent of all others, whose kernels run on the beamformer's stream -- rings declared 'beam' cover them, and
+ * xengBeamformSync waits for them too.  Two kernels per call (csrc/dedisp_kernels.h):
+ *   in       f32[nwin_call][npair][nfine][4] = [XX, YY, Re XY*, Im XY*], the output span of xengUpchanSumBeamsRun or of
+ *            xengUpchanInitializeDualPol unchanged: nfine = nchan*nupchan, q = c*N + j ascending in frequency, the centre of
+ *            channel q at fine_sfreq + q*fine_bw_hz.  16-byte aligned; never written.  1 <= nwin_call <= nwin.
+ *   products nprod = 1: I = XX + YY (one f32 add, at ingest); nprod = 4: the four words, each dedispersed by itself
+ *   delays   s[d][q], int32[ndm][nfine] on the host, 0 <= s <= max_delay, in windows (xengDedispSetDelays; the library knows
+ *            nothing of the dispersion constant).  S = max s; the back-delay is b[d][q] = S - s[d][q].
+ *   weights  w[q], f32[nfine] on the host, finite; NULL or never set: all ones (xengDedispSetWeights).  A channel whose weight is
+ *            exactly 0 is left out, not multiplied: a NaN or Inf in it never reaches an output.
+ *   out      f32[nwin_call][npair][ndm][nprod], 16-byte aligned; nothing past it is written.  With n counting windows since the
+ *            last reset (xengDedispReset, xengDedispSetDelays, Initialize):
+ *              y[n][p][d] = sum_q w[q] * x[n - b[d][q]][p][q],   terms with n - b[d][q] < 0 count as zero
+ *            All trials share one time axis: output n is the pulse that reached the top channel (delay 0) at window n - S; the
+ *            first S outputs after a reset are partial sums.
+ *   state    a device ring of L = max_delay + nwin windows, f32[npair][nfine][nprod][L] (time the fastest axis, window n at slot
+ *            n mod L), holding I or the four words UNWEIGHTED: new weights apply to every later output, old windows included.
+ * Numerics: fp32, no atomics; every output is one fixed-order sum.  The channels are cut into 4 segments of Q = ceil(nfine / 4)
+ * consecutive channels, segment k = [k*Q, min((k+1)*Q, nfine)); a segment's partial sum P_k starts from +0 and takes its channels
+ * in ascending q, one fmaf(w[q], x, sum) each (a term that counts as zero or is left out enters as fmaf(w[q], +0, sum)); the
+ * output is ((P_0 + P_1) + P_2) + P_3.  The order depends on nfine alone: not on nwin_call, on how a run of windows is split
+ * over calls, on the ring's wrap position, or on what else runs on the GPU -- bit-identical in all of these.  Exact on integer
+ * data while every sum stays below 2^24.
+ * Rejected at Initialize, before any device is touched: a non-positive size, nprod outside {1, 4}, max_delay < 0, a history
+ * above XENG_DEDISP_MAX_HISTORY_BYTES, npair > 65535, ndm*nfine > 2^28, ndm*nwin > 2^30.  Rejected by the setters and Run without
+ * a launch: a NULL (SetDelays, Run) or misaligned pointer, nwin_call outside 1..nwin, a negative delay or one above max_delay, a
+ * non-finite weight; Run before SetDelays and every call without a context: XENG_STATUS_INVALID_STATE. */
+#define XENG_DEDISP_MAX_HISTORY_BYTES (1LL << 32)
+int xengDedispInitialize(int gpu, int npair, int nfine, int nwin, int ndm, int max_delay, int nprod);
+/* Both setters wait for the context's work in flight (as xengUpchanSetPfb does) and upload from the host.  SetDelays clears the
+ * history and the window count, because S moves the time axis; SetWeights clears neither. */
+int xengDedispSetDelays(const int *delays);
+int xengDedispSetWeights(const float *weights);
+/* enqueue only: nwin_call windows in, nwin_call out */
+int xengDedispRun(const void *in_dev, int nwin_call, void *out_dev);
+/* host state only, nothing is launched: the next input counts as window 0 of an empty history */
+int xengDedispReset(void);
+/* S of the table in use (-1 before SetDelays) and the windows taken since the last reset */
+int xengDedispGetInfo(int *max_delay_in_use, long long *nwindows_since_reset);
+/* The history is allocated between two guard bands of 64 KiB: waits for the context's work, reads them back and reports
+ * whether both still hold their pattern (*intact = 1) -- for tests and for chasing a stray write; not a per-call function. */
+int xengDedispCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengDedispMark(unsigned long long *ticket);
+int xengDedispWait(unsigned long long ticket);
+int xengDedispTicketDone(unsigned long long ticket, int *done);
+int xengDedispSync(void);
+int xengDedispDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
