@@ -10,9 +10,8 @@
 
 namespace xeng {
 
-struct DedispContext {
-    bool live = false;
-    int gpu = 0, npair = 0, nfine = 0, nwin = 0, ndm = 0, max_delay = 0, nprod = 0;
+struct DedispContext : BeamStreamContext {
+    int npair = 0, nfine = 0, nwin = 0, ndm = 0, max_delay = 0, nprod = 0;
     int L = 0;                          // windows of the history ring: max_delay + nwin
     uint8_t* hist_alloc = nullptr;      // DD_GUARD bytes of DD_GUARD_BYTE, the history, DD_GUARD bytes of DD_GUARD_BYTE
     float* hist = nullptr;              // f32[npair][nfine][nprod][L], inside hist_alloc
@@ -21,8 +20,6 @@ struct DedispContext {
     int S = -1;                         // the table's largest delay; -1: no table yet
     long long nwindows = 0;             // windows taken since the last reset
     int head = 0;                       // slot of the next window
-    hipStream_t stream = nullptr;
-    TicketRing tickets;                 // xengDedispMark / Wait / TicketDone
 
     size_t hist_bytes() const { return (size_t)npair * nfine * nprod * (size_t)L * sizeof(float); }
 };
@@ -33,10 +30,7 @@ static DedispContext g_dd;
 
 static int dedisp_destroy_locked() {
     if (!g_dd.live) return XENG_STATUS_SUCCESS;
-    (void)hipSetDevice(g_dd.gpu);
-    if (g_dd.stream) (void)hipStreamSynchronize(g_dd.stream);
-    stream_clocks_forget(g_dd.gpu, STREAM_BEAM);         // (the mark events lent to the stream clock go away below)
-    g_dd.tickets.destroy();
+    beam_context_close(g_dd);
     if (g_dd.hist_alloc) (void)hipFree(g_dd.hist_alloc);
     if (g_dd.bt) (void)hipFree(g_dd.bt);
     if (g_dd.w) (void)hipFree(g_dd.w);
@@ -79,9 +73,7 @@ int xengDedispInitialize(int gpu, int npair, int nfine, int nwin, int ndm, int m
     std::lock_guard<std::mutex> lk(g_ddmu);
     dedisp_destroy_locked();
     DedispContext& x = g_dd;
-    x.gpu = gpu < 0 ? 0 : gpu;
-    XENG_HIP(hipSetDevice(x.gpu));
-    int rc = get_stream(STREAM_BEAM, &x.stream);
+    int rc = beam_context_open(x, gpu);
     if (rc) return rc;
     x.npair = npair; x.nfine = nfine; x.nwin = nwin; x.ndm = ndm; x.max_delay = max_delay; x.nprod = nprod;
     x.L = (int)L;
@@ -202,45 +194,10 @@ int xengDedispCheckGuards(int* intact) {
     return XENG_STATUS_SUCCESS;
 }
 
-int xengDedispMark(unsigned long long* ticket) {
-    if (!ticket) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "DedispMark: null ticket");
-    std::lock_guard<std::mutex> lk(g_ddmu);
-    DedispContext& x = g_dd;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Dedisp: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    return x.tickets.mark(x.stream, STREAM_BEAM, ticket);
-}
-
-int xengDedispWait(unsigned long long ticket) {
-    hipEvent_t ev = nullptr;
-    int gpu = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_ddmu);
-        DedispContext& x = g_dd;
-        if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Dedisp: not initialized");
-        if (!(ev = x.tickets.find(ticket))) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "DedispWait: unknown ticket %llu", ticket);
-        gpu = x.gpu;
-    }
-    XENG_HIP(hipSetDevice(gpu));
-    XENG_HIP(hipEventSynchronize(ev));          // (outside the lock)
-    return XENG_STATUS_SUCCESS;
-}
-
-int xengDedispTicketDone(unsigned long long ticket, int* done) {
-    if (!done) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "DedispTicketDone: null result");
-    std::lock_guard<std::mutex> lk(g_ddmu);
-    DedispContext& x = g_dd;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Dedisp: not initialized");
-    const hipEvent_t ev = x.tickets.find(ticket);
-    if (!ev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "DedispTicketDone: unknown ticket %llu", ticket);
-    XENG_HIP(hipSetDevice(x.gpu));
-    return TicketRing::query(ev, done);
-}
-
-int xengDedispSync(void) {
-    std::lock_guard<std::mutex> lk(g_ddmu);
-    return context_sync("Dedisp", g_dd.live, g_dd.gpu, g_dd.stream);
-}
+int xengDedispMark(unsigned long long* ticket) { return beam_context_mark(g_ddmu, g_dd, "Dedisp", ticket); }
+int xengDedispWait(unsigned long long ticket) { return beam_context_wait(g_ddmu, g_dd, "Dedisp", ticket); }
+int xengDedispTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_ddmu, g_dd, "Dedisp", ticket, done); }
+int xengDedispSync(void) { return beam_context_sync(g_ddmu, g_dd, "Dedisp"); }
 
 int xengDedispDestroy(void) {
     std::lock_guard<std::mutex> lk(g_ddmu);

@@ -9,23 +9,16 @@
 
 namespace xeng {
 
-struct UpchanContext {
-    bool live = false;
-    int gpu = 0, ninput = 0, nchan = 0, ntime = 0, nupchan = 0, nbeam = 0, nframe_sum = 0;
+struct UpchanContext : PfbContext {
+    int ninput = 0, nchan = 0, nbeam = 0, nframe_sum = 0;
     bool dual = false;                  // xengUpchanInitializeDualPol: [XX, YY, Re XY*, Im XY*] per pair of beams
-    PfbState pfb;                       // xengUpchanSetPfb (ntap 1 without coefficients: the plain FFT)
-    hipStream_t stream = nullptr;
-    TicketRing tickets;                 // xengUpchanMark / Wait / TicketDone
 };
 static std::mutex g_umu;
 static UpchanContext g_u;
 
 static int upchan_destroy_locked() {
     if (!g_u.live) return XENG_STATUS_SUCCESS;
-    (void)hipSetDevice(g_u.gpu);
-    if (g_u.stream) (void)hipStreamSynchronize(g_u.stream);
-    stream_clocks_forget(g_u.gpu, STREAM_BEAM);          // (the mark events lent to the stream clock go away below)
-    g_u.tickets.destroy();
+    beam_context_close(g_u);
     g_u.pfb.release();
     g_u = UpchanContext();
     return XENG_STATUS_SUCCESS;
@@ -65,17 +58,13 @@ static void upchan_launch_pfb(int ppt, dim3 grid, dim3 block, hipStream_t s, con
     else upchan_launch_n<N>(ppt, grid, block, s, in0, in1, ntime0, w, out, x, nframe, run);
 }
 
-// Every argument is checked before the context is looked at where it can be (a bad call is told apart from a missing
-// context, and nothing is launched); what depends on the context's sizes is checked right after.
 static int upchan_run(const void* in0_dev, int ntime0, const void* in1_dev, void* out_dev, const void* weights_dev) {
-    if (!in0_dev || !out_dev || !weights_dev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: null buffer");
+    if (!out_dev || !weights_dev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: null buffer");
     if ((uintptr_t)weights_dev % 16 || (uintptr_t)out_dev % 16)
         XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: weights %p / output %p not 16-byte aligned", weights_dev, out_dev);
-    if (in1_dev && ntime0 <= 0) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Upchan: first part of %d samples", ntime0);
-    std::lock_guard<std::mutex> lk(g_umu);
+    std::unique_lock<std::mutex> lk(g_umu, std::defer_lock);
     UpchanContext& x = g_u;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized (call xengUpchanInitialize)");
-    int rc = gulp_parts("Upchan", in0_dev, &in1_dev, &ntime0, x.ntime, x.nupchan);
+    int rc = gulp_begin(lk, x, "Upchan", "", in0_dev, &in1_dev, &ntime0);
     if (rc) return rc;
     XENG_HIP(hipSetDevice(x.gpu));
     const int nframe = x.ntime / x.nupchan, run = upchan_run_frames(x.nframe_sum);
@@ -95,10 +84,7 @@ static int upchan_run(const void* in0_dev, int ntime0, const void* in1_dev, void
     case 32: upchan_launch_pfb<32>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
     default: upchan_launch_pfb<64>(ppt, grid, block, x.stream, a, b, ntime0, w, o, x, nframe, run); break;
     }
-    if (x.pfb.hist) {                   // the history for the next gulp, before the tick: the input span's stamp covers the copies
-        XENG_HIP(hipGetLastError());
-        if ((rc = pfb_refresh(x.pfb, x.stream, a, ntime0, b, x.ntime, x.nupchan, (size_t)x.nchan * x.ninput))) return rc;
-    }
+    if ((rc = pfb_after_launch(x, a, ntime0, b))) return rc;
     stream_tick(STREAM_BEAM);
     XENG_HIP(hipGetLastError());
     return XENG_STATUS_SUCCESS;
@@ -123,11 +109,10 @@ static int upchan_initialize(int gpu, int ninput, int nchan, int ntime, int nupc
     std::lock_guard<std::mutex> lk(g_umu);
     upchan_destroy_locked();
     UpchanContext& x = g_u;
-    x.gpu = gpu < 0 ? 0 : gpu;
-    XENG_HIP(hipSetDevice(x.gpu));
-    int rc = get_stream(STREAM_BEAM, &x.stream);
+    int rc = beam_context_open(x, gpu);
     if (rc) return rc;
     x.ninput = ninput; x.nchan = nchan; x.ntime = ntime; x.nupchan = nupchan; x.nbeam = nbeam; x.nframe_sum = nframe_sum;
+    x.pfb_row = (size_t)nchan * ninput;
     x.dual = dual;
     x.live = true;
     return XENG_STATUS_SUCCESS;
@@ -160,15 +145,8 @@ int xengUpchanRunParts(const void* in0_dev, int ntime0, const void* in1_dev, voi
 }
 
 int xengUpchanSetPfb(int ntap, const float* coeffs) {
-    int rc = pfb_check_args("UpchanSetPfb", ntap, coeffs);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_umu);
-    UpchanContext& x = g_u;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized (call xengUpchanInitialize)");
-    if ((rc = pfb_check_sizes("UpchanSetPfb", ntap, coeffs, x.nupchan, x.ntime))) return rc;
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));   // (launches in flight read the coefficients and the history)
-    return pfb_set("UpchanSetPfb", x.pfb, ntap, coeffs, x.nupchan, (size_t)x.nchan * x.ninput);
+    std::unique_lock<std::mutex> lk(g_umu, std::defer_lock);
+    return pfb_configure(lk, g_u, "Upchan", ntap, coeffs);
 }
 
 int xengUpchanReset(void) {
@@ -179,45 +157,10 @@ int xengUpchanReset(void) {
     return XENG_STATUS_SUCCESS;
 }
 
-int xengUpchanMark(unsigned long long* ticket) {
-    if (!ticket) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanMark: null ticket");
-    std::lock_guard<std::mutex> lk(g_umu);
-    UpchanContext& x = g_u;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    return x.tickets.mark(x.stream, STREAM_BEAM, ticket);
-}
-
-int xengUpchanWait(unsigned long long ticket) {
-    hipEvent_t ev = nullptr;
-    int gpu = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_umu);
-        UpchanContext& x = g_u;
-        if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized");
-        if (!(ev = x.tickets.find(ticket))) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanWait: unknown ticket %llu", ticket);
-        gpu = x.gpu;
-    }
-    XENG_HIP(hipSetDevice(gpu));
-    XENG_HIP(hipEventSynchronize(ev));          // (outside the lock)
-    return XENG_STATUS_SUCCESS;
-}
-
-int xengUpchanTicketDone(unsigned long long ticket, int* done) {
-    if (!done) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanTicketDone: null result");
-    std::lock_guard<std::mutex> lk(g_umu);
-    UpchanContext& x = g_u;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Upchan: not initialized");
-    const hipEvent_t ev = x.tickets.find(ticket);
-    if (!ev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanTicketDone: unknown ticket %llu", ticket);
-    XENG_HIP(hipSetDevice(x.gpu));
-    return TicketRing::query(ev, done);
-}
-
-int xengUpchanSync(void) {
-    std::lock_guard<std::mutex> lk(g_umu);
-    return context_sync("Upchan", g_u.live, g_u.gpu, g_u.stream);
-}
+int xengUpchanMark(unsigned long long* ticket) { return beam_context_mark(g_umu, g_u, "Upchan", ticket); }
+int xengUpchanWait(unsigned long long ticket) { return beam_context_wait(g_umu, g_u, "Upchan", ticket); }
+int xengUpchanTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_umu, g_u, "Upchan", ticket, done); }
+int xengUpchanSync(void) { return beam_context_sync(g_umu, g_u, "Upchan"); }
 
 int xengUpchanDestroy(void) {
     std::lock_guard<std::mutex> lk(g_umu);

@@ -9,18 +9,14 @@
 
 namespace xeng {
 
-struct UpchanBeamsContext {
-    bool live = false;
-    int gpu = 0, nchan = 0, nbeam = 0, ntime = 0, nupchan = 0, pair0 = 0, npair = 0, nframe_sum = 0;
+struct UpchanBeamsContext : PfbContext {      // pfb.hist holds both halves of the ping-pong history: pfb_row is two float2 rows
+    int nchan = 0, nbeam = 0, pair0 = 0, npair = 0, nframe_sum = 0;
     int nframe = 0;                     // frames per gulp (F)
     int wf = 0;                         // frames per fp32 chain: min(W, F)
     int gpw = 1;                        // gulps per window (G = W / F when F | W, else 1)
     int pos = 0;                        // gulps of the window in progress already run
     float* acc = nullptr;               // f32[npair][nchan][N][4]: the window in progress when gpw > 1
-    PfbState pfb;                       // xengUpchanSumBeamsSetPfb; hist holds both halves of the ping-pong history
     int cur = 0;                        // the half of pfb.hist the next gulp reads
-    hipStream_t stream = nullptr;
-    TicketRing tickets;                 // xengUpchanSumBeamsMark / Wait / TicketDone
 
     size_t hist_half() const { return (size_t)nchan * 2 * npair * (size_t)(pfb.ntap - 1) * nupchan; }     // float2 per half
 };
@@ -29,10 +25,7 @@ static UpchanBeamsContext g_ub;
 
 static int upchan_beams_destroy_locked() {
     if (!g_ub.live) return XENG_STATUS_SUCCESS;
-    (void)hipSetDevice(g_ub.gpu);
-    if (g_ub.stream) (void)hipStreamSynchronize(g_ub.stream);
-    stream_clocks_forget(g_ub.gpu, STREAM_BEAM);         // (the mark events lent to the stream clock go away below)
-    g_ub.tickets.destroy();
+    beam_context_close(g_ub);
     if (g_ub.acc) (void)hipFree(g_ub.acc);
     g_ub.pfb.release();
     g_ub = UpchanBeamsContext();
@@ -122,12 +115,11 @@ int xengUpchanSumBeamsInitialize(int gpu, int nchan, int nbeam, int ntime, int n
     std::lock_guard<std::mutex> lk(g_ubmu);
     upchan_beams_destroy_locked();
     UpchanBeamsContext& x = g_ub;
-    x.gpu = gpu < 0 ? 0 : gpu;
-    XENG_HIP(hipSetDevice(x.gpu));
-    int rc = get_stream(STREAM_BEAM, &x.stream);
+    int rc = beam_context_open(x, gpu);
     if (rc) return rc;
     x.nchan = nchan; x.nbeam = nbeam; x.ntime = ntime; x.nupchan = nupchan; x.pair0 = pair0; x.npair = npair; x.nframe_sum = nframe_sum;
     x.nframe = nframe;
+    x.pfb_row = 2 * (size_t)nchan * 2 * npair * sizeof(float2);    // a "sample" of history: one float2 per selected (channel, beam) row, twice
     x.wf = nframe_sum < nframe ? nframe_sum : nframe;
     x.gpw = nframe_sum > nframe ? nframe_sum / nframe : 1;
     if (x.gpw > 1 && hipMalloc(&x.acc, (size_t)npair * nchan * nupchan * 4 * sizeof(float)) != hipSuccess) {
@@ -155,18 +147,10 @@ int xengUpchanSumBeamsRun(const void* in_dev, void* out_dev) {
 }
 
 int xengUpchanSumBeamsSetPfb(int ntap, const float* coeffs) {
-    int rc = pfb_check_args("UpchanSumBeamsSetPfb", ntap, coeffs);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_ubmu);
-    UpchanBeamsContext& x = g_ub;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanSumBeams: not initialized (call xengUpchanSumBeamsInitialize)");
-    if ((rc = pfb_check_sizes("UpchanSumBeamsSetPfb", ntap, coeffs, x.nupchan, x.ntime))) return rc;
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));   // (launches in flight read the coefficients and the history)
-    // both halves of the history: a "sample" of pfb_set is one float2 per selected (channel, beam) row, twice
-    if ((rc = pfb_set("UpchanSumBeamsSetPfb", x.pfb, ntap, coeffs, x.nupchan, 2 * (size_t)x.nchan * 2 * x.npair * sizeof(float2)))) return rc;
-    x.cur = 0;
-    return XENG_STATUS_SUCCESS;
+    std::unique_lock<std::mutex> lk(g_ubmu, std::defer_lock);
+    int rc = pfb_configure(lk, g_ub, "UpchanSumBeams", ntap, coeffs);
+    if (!rc) g_ub.cur = 0;
+    return rc;
 }
 
 int xengUpchanSumBeamsPrime(const void* in_dev) {
@@ -198,45 +182,10 @@ int xengUpchanSumBeamsReset(void) {
     return XENG_STATUS_SUCCESS;
 }
 
-int xengUpchanSumBeamsMark(unsigned long long* ticket) {
-    if (!ticket) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanSumBeamsMark: null ticket");
-    std::lock_guard<std::mutex> lk(g_ubmu);
-    UpchanBeamsContext& x = g_ub;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanSumBeams: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    return x.tickets.mark(x.stream, STREAM_BEAM, ticket);
-}
-
-int xengUpchanSumBeamsWait(unsigned long long ticket) {
-    hipEvent_t ev = nullptr;
-    int gpu = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_ubmu);
-        UpchanBeamsContext& x = g_ub;
-        if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanSumBeams: not initialized");
-        if (!(ev = x.tickets.find(ticket))) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanSumBeamsWait: unknown ticket %llu", ticket);
-        gpu = x.gpu;
-    }
-    XENG_HIP(hipSetDevice(gpu));
-    XENG_HIP(hipEventSynchronize(ev));          // (outside the lock)
-    return XENG_STATUS_SUCCESS;
-}
-
-int xengUpchanSumBeamsTicketDone(unsigned long long ticket, int* done) {
-    if (!done) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanSumBeamsTicketDone: null result");
-    std::lock_guard<std::mutex> lk(g_ubmu);
-    UpchanBeamsContext& x = g_ub;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanSumBeams: not initialized");
-    const hipEvent_t ev = x.tickets.find(ticket);
-    if (!ev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanSumBeamsTicketDone: unknown ticket %llu", ticket);
-    XENG_HIP(hipSetDevice(x.gpu));
-    return TicketRing::query(ev, done);
-}
-
-int xengUpchanSumBeamsSync(void) {
-    std::lock_guard<std::mutex> lk(g_ubmu);
-    return context_sync("UpchanSumBeams", g_ub.live, g_ub.gpu, g_ub.stream);
-}
+int xengUpchanSumBeamsMark(unsigned long long* ticket) { return beam_context_mark(g_ubmu, g_ub, "UpchanSumBeams", ticket); }
+int xengUpchanSumBeamsWait(unsigned long long ticket) { return beam_context_wait(g_ubmu, g_ub, "UpchanSumBeams", ticket); }
+int xengUpchanSumBeamsTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_ubmu, g_ub, "UpchanSumBeams", ticket, done); }
+int xengUpchanSumBeamsSync(void) { return beam_context_sync(g_ubmu, g_ub, "UpchanSumBeams"); }
 
 int xengUpchanSumBeamsDestroy(void) {
     std::lock_guard<std::mutex> lk(g_ubmu);

@@ -9,18 +9,14 @@
 
 namespace xeng {
 
-struct UpchanCorrContext {
-    bool live = false;
-    int gpu = 0, ninput = 0, nchan = 0, ntime = 0, nupchan = 0, fine_lo = 0, fine_hi = 0, nstage = 0;
+struct UpchanCorrContext : PfbContext {
+    int ninput = 0, nchan = 0, fine_lo = 0, fine_hi = 0, nstage = 0;
     int nfine = 0, npad = 0, ntile = 0, ntp = 0, nframe = 0, nfp = 0;
     size_t fine_stride = 0;             // float2 per fine channel of the staging buffer: nstage * nfp * npad
     float2* stage = nullptr;            // [nfine][nstage * nfp][npad]
     float* acc = nullptr;               // [nfine][ntp][Re, Im][16][64]
     int staged = 0;                     // gulps staged since the last contraction
     bool fresh = true;                  // nothing contracted since the last dump / reset: the next contraction starts from zero
-    PfbState pfb;                       // xengUpchanCorrSetPfb (ntap 1 without coefficients: the plain FFT)
-    hipStream_t stream = nullptr;
-    TicketRing tickets;                 // xengUpchanCorrMark / Wait / TicketDone
 };
 static std::mutex g_ccmu;
 static UpchanCorrContext g_cc;
@@ -31,10 +27,7 @@ static constexpr int UCC_MAX_STAGE = 8;
 
 static int upchan_corr_destroy_locked() {
     if (!g_cc.live) return XENG_STATUS_SUCCESS;
-    (void)hipSetDevice(g_cc.gpu);
-    if (g_cc.stream) (void)hipStreamSynchronize(g_cc.stream);
-    stream_clocks_forget(g_cc.gpu, STREAM_BEAM);         // (the mark events lent to the stream clock go away below)
-    g_cc.tickets.destroy();
+    beam_context_close(g_cc);
     if (g_cc.stage) (void)hipFree(g_cc.stage);
     if (g_cc.acc) (void)hipFree(g_cc.acc);
     g_cc.pfb.release();
@@ -66,15 +59,10 @@ static void upchan_corr_stage_n(dim3 grid, const UpchanCorrContext& x, const uin
                            x.nframe, x.nfp, x.fine_stride, x.staged * x.nfp, x.fine_lo, x.fine_hi, c_lo);
 }
 
-// Every argument is checked before the context is looked at where it can be (a bad call is told apart from a missing
-// context, and nothing is launched); what depends on the context's sizes is checked right after.
 static int upchan_corr_accumulate(const void* in0_dev, int ntime0, const void* in1_dev) {
-    if (!in0_dev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorr: null input");
-    if (in1_dev && ntime0 <= 0) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorr: first part of %d samples", ntime0);
-    std::lock_guard<std::mutex> lk(g_ccmu);
+    std::unique_lock<std::mutex> lk(g_ccmu, std::defer_lock);
     UpchanCorrContext& x = g_cc;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized (call xengUpchanCorrInitialize)");
-    int rc = gulp_parts("UpchanCorr", in0_dev, &in1_dev, &ntime0, x.ntime, x.nupchan);
+    int rc = gulp_begin(lk, x, "UpchanCorr", "", in0_dev, &in1_dev, &ntime0);
     if (rc) return rc;
     XENG_HIP(hipSetDevice(x.gpu));
     const int c_lo = x.fine_lo / x.nupchan, c_hi = (x.fine_hi - 1) / x.nupchan + 1;
@@ -91,29 +79,10 @@ static int upchan_corr_accumulate(const void* in0_dev, int ntime0, const void* i
     case 32: upchan_corr_stage_n<32>(grid, x, a, b, ntime0, c_lo); break;
     default: upchan_corr_stage_n<64>(grid, x, a, b, ntime0, c_lo); break;
     }
-    if (x.pfb.hist) {                   // the history for the next gulp, before the tick: the input span's stamp covers the copies
-        XENG_HIP(hipGetLastError());
-        if ((rc = pfb_refresh(x.pfb, x.stream, a, ntime0, b, x.ntime, x.nupchan, (size_t)x.nchan * x.ninput))) return rc;
-    }
+    if ((rc = pfb_after_launch(x, a, ntime0, b))) return rc;
     stream_tick(STREAM_BEAM);
     XENG_HIP(hipGetLastError());
     if (++x.staged == x.nstage) return upchan_corr_contract_locked(x);
-    return XENG_STATUS_SUCCESS;
-}
-
-// xengUpchanCorrPrime[Parts]: the history from this gulp's tail, nothing staged
-static int upchan_corr_prime(const void* in0_dev, int ntime0, const void* in1_dev) {
-    if (!in0_dev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrPrime: null input");
-    if (in1_dev && ntime0 <= 0) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrPrime: first part of %d samples", ntime0);
-    std::lock_guard<std::mutex> lk(g_ccmu);
-    UpchanCorrContext& x = g_cc;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized (call xengUpchanCorrInitialize)");
-    int rc = gulp_parts("UpchanCorrPrime", in0_dev, &in1_dev, &ntime0, x.ntime, x.nupchan);
-    if (rc || !x.pfb.hist) return rc;   // (no history without taps before the frame's own)
-    XENG_HIP(hipSetDevice(x.gpu));
-    if ((rc = pfb_refresh(x.pfb, x.stream, (const uint8_t*)in0_dev, ntime0, (const uint8_t*)in1_dev, x.ntime, x.nupchan, (size_t)x.nchan * x.ninput)))
-        return rc;
-    stream_tick(STREAM_BEAM);
     return XENG_STATUS_SUCCESS;
 }
 
@@ -147,13 +116,12 @@ int xengUpchanCorrInitialize(int gpu, int ninput, int nchan, int ntime, int nupc
     std::lock_guard<std::mutex> lk(g_ccmu);
     upchan_corr_destroy_locked();
     UpchanCorrContext& x = g_cc;
-    x.gpu = gpu < 0 ? 0 : gpu;
-    XENG_HIP(hipSetDevice(x.gpu));
-    int rc = get_stream(STREAM_BEAM, &x.stream);
+    int rc = beam_context_open(x, gpu);
     if (rc) return rc;
     x.ninput = ninput; x.nchan = nchan; x.ntime = ntime; x.nupchan = nupchan; x.fine_lo = fine_lo; x.fine_hi = fine_hi; x.nstage = nstage;
     x.nfine = (int)nfine; x.npad = npad; x.ntile = (int)ntile; x.ntp = (int)ntp; x.nframe = nframe; x.nfp = nfp;
     x.fine_stride = (size_t)nstage * nfp * npad;
+    x.pfb_row = (size_t)nchan * ninput;
     if (hipMalloc(&x.stage, (size_t)nfine * x.fine_stride * sizeof(float2)) != hipSuccess ||
         hipMalloc(&x.acc, (size_t)nfine * ntp * 2048 * sizeof(float)) != hipSuccess) {
         (void)hipGetLastError();
@@ -213,65 +181,23 @@ int xengUpchanCorrReset(void) {
 }
 
 int xengUpchanCorrSetPfb(int ntap, const float* coeffs) {
-    int rc = pfb_check_args("UpchanCorrSetPfb", ntap, coeffs);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_ccmu);
-    UpchanCorrContext& x = g_cc;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized (call xengUpchanCorrInitialize)");
-    if ((rc = pfb_check_sizes("UpchanCorrSetPfb", ntap, coeffs, x.nupchan, x.ntime))) return rc;
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));   // (launches in flight read the coefficients and the history)
-    return pfb_set("UpchanCorrSetPfb", x.pfb, ntap, coeffs, x.nupchan, (size_t)x.nchan * x.ninput);
+    std::unique_lock<std::mutex> lk(g_ccmu, std::defer_lock);
+    return pfb_configure(lk, g_cc, "UpchanCorr", ntap, coeffs);
 }
 
 int xengUpchanCorrPrime(const void* in_dev) {
-    return upchan_corr_prime(in_dev, 0, nullptr);
+    return pfb_prime(g_ccmu, g_cc, "UpchanCorr", in_dev, 0, nullptr);
 }
 
 int xengUpchanCorrPrimeParts(const void* in0_dev, int ntime0, const void* in1_dev) {
     if (!in1_dev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrPrime: null second part");
-    return upchan_corr_prime(in0_dev, ntime0, in1_dev);
+    return pfb_prime(g_ccmu, g_cc, "UpchanCorr", in0_dev, ntime0, in1_dev);
 }
 
-int xengUpchanCorrMark(unsigned long long* ticket) {
-    if (!ticket) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrMark: null ticket");
-    std::lock_guard<std::mutex> lk(g_ccmu);
-    UpchanCorrContext& x = g_cc;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    return x.tickets.mark(x.stream, STREAM_BEAM, ticket);
-}
-
-int xengUpchanCorrWait(unsigned long long ticket) {
-    hipEvent_t ev = nullptr;
-    int gpu = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_ccmu);
-        UpchanCorrContext& x = g_cc;
-        if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized");
-        if (!(ev = x.tickets.find(ticket))) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrWait: unknown ticket %llu", ticket);
-        gpu = x.gpu;
-    }
-    XENG_HIP(hipSetDevice(gpu));
-    XENG_HIP(hipEventSynchronize(ev));          // (outside the lock)
-    return XENG_STATUS_SUCCESS;
-}
-
-int xengUpchanCorrTicketDone(unsigned long long ticket, int* done) {
-    if (!done) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrTicketDone: null result");
-    std::lock_guard<std::mutex> lk(g_ccmu);
-    UpchanCorrContext& x = g_cc;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "UpchanCorr: not initialized");
-    const hipEvent_t ev = x.tickets.find(ticket);
-    if (!ev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "UpchanCorrTicketDone: unknown ticket %llu", ticket);
-    XENG_HIP(hipSetDevice(x.gpu));
-    return TicketRing::query(ev, done);
-}
-
-int xengUpchanCorrSync(void) {
-    std::lock_guard<std::mutex> lk(g_ccmu);
-    return context_sync("UpchanCorr", g_cc.live, g_cc.gpu, g_cc.stream);
-}
+int xengUpchanCorrMark(unsigned long long* ticket) { return beam_context_mark(g_ccmu, g_cc, "UpchanCorr", ticket); }
+int xengUpchanCorrWait(unsigned long long ticket) { return beam_context_wait(g_ccmu, g_cc, "UpchanCorr", ticket); }
+int xengUpchanCorrTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_ccmu, g_cc, "UpchanCorr", ticket, done); }
+int xengUpchanCorrSync(void) { return beam_context_sync(g_ccmu, g_cc, "UpchanCorr"); }
 
 int xengUpchanCorrDestroy(void) {
     std::lock_guard<std::mutex> lk(g_ccmu);

@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <string>
 
 #include "../../include/xeng.h"
@@ -73,8 +74,8 @@ void stream_clocks_forget(int dev, StreamId which);                 // the strea
 // an event somebody records on the stream anyway (xengBeamformMark) serves as a clock mark: upto = stream_clock_now() read BEFORE the record
 unsigned long long stream_clock_now(StreamId which);
 void stream_clock_external_mark(StreamId which, hipEvent_t ev, unsigned long long upto);
-// Completion tickets on a library stream (xengBeamformMark / Wait / TicketDone and the Upchan, UpchanCorr ones), so that a block
-// can keep several gulps in flight and let go of each gulp's spans when ITS kernels are done: a ring of events, ticket n ->
+// Completion tickets on a library stream (xengBeamformMark / Wait / TicketDone and those of every BeamStreamContext), so that a
+// block can keep several gulps in flight and let go of each gulp's spans when ITS kernels are done: a ring of events, ticket n ->
 // ev[(n - 1) % NMARK].  A ticket whose slot has been re-recorded is NMARK marks old: the newer record of that slot is later on the
 // same stream, so waiting for it is still right.  The caller holds its context's lock (and waits for an event outside it).
 struct TicketRing {
@@ -87,11 +88,27 @@ struct TicketRing {
     static int query(hipEvent_t e, int* done);                      // never blocks
     void destroy();                                                 // after the stream has been synchronised and its clock forgotten
 };
-// Upchan / UpchanCorr: a gulp in one part (*in1 null: *in1 = in0, *ntime0 = ntime) or two (samples [*ntime0, ntime) at *in1),
-// each part whole frames of nupchan samples; `who` begins the error message
-int gulp_parts(const char* who, const void* in0, const void** in1, int* ntime0, int ntime, int nupchan);
-// xengUpchanSync / xengUpchanCorrSync with the context's lock held
-int context_sync(const char* who, bool live, int gpu, hipStream_t stream);
+// What every engine beside the beamformer on its stream has (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp): each
+// derives its process-global context from this and keeps a mutex of its own.  Its kernels run on STREAM_BEAM and tick that
+// clock, so that rings declared 'beam' and their span stamps cover them unchanged.
+struct BeamStreamContext {
+    bool live = false;
+    int gpu = 0;
+    hipStream_t stream = nullptr;                                   // STREAM_BEAM of gpu
+    TicketRing tickets;                                             // count from 1 after every Initialize
+};
+// Initialize, after the caller has destroyed the old context: the device (gpu < 0: 0) made current, its beam stream looked up
+int beam_context_open(BeamStreamContext& c, int gpu);
+// Destroy of a live context, in this order: the stream synchronised, its clock forgotten, the ticket events (lent to that
+// clock) destroyed.  Only then does the caller free its buffers and reset its struct.
+void beam_context_close(BeamStreamContext& c);
+// xeng<who>Mark / Wait / TicketDone / Sync: `mu` is the context's mutex and `who` begins the error message.  A null pointer is
+// refused before the context is looked at (INVALID_ARGUMENT even without a context), a missing context is INVALID_STATE, an
+// unknown ticket (0, last + 1) INVALID_ARGUMENT.  Wait blocks on the event after it has let go of `mu`.
+int beam_context_mark(std::mutex& mu, BeamStreamContext& c, const char* who, unsigned long long* ticket);
+int beam_context_wait(std::mutex& mu, const BeamStreamContext& c, const char* who, unsigned long long ticket);
+int beam_context_ticket_done(std::mutex& mu, const BeamStreamContext& c, const char* who, unsigned long long ticket, int* done);
+int beam_context_sync(std::mutex& mu, const BeamStreamContext& c, const char* who);
 // X-engine side of a stamp (xcorr.hip)
 void xgpu_pending_launch(unsigned long long* seq, unsigned long long* epoch, unsigned long long* nlaunch, unsigned long long* ctx);
 int xgpu_pending_poll(unsigned long long seq, unsigned long long epoch, bool* done, bool* launched, hipEvent_t* ev, int* gpu);

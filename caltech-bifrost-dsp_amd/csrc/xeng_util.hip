@@ -366,18 +366,56 @@ void TicketRing::destroy() {
         if (ev[k]) (void)hipEventDestroy(ev[k]);
 }
 
-int gulp_parts(const char* who, const void* in0, const void** in1, int* ntime0, int ntime, int nupchan) {
-    if (!*in1) { *in1 = in0; *ntime0 = ntime; }
-    else if (*ntime0 >= ntime || *ntime0 % nupchan)
-        XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "%s: parts of %d + %d samples: both must be positive multiples of nupchan %d", who, *ntime0,
-                  ntime - *ntime0, nupchan);
+int beam_context_open(BeamStreamContext& c, int gpu) {
+    c.gpu = gpu < 0 ? 0 : gpu;
+    XENG_HIP(hipSetDevice(c.gpu));
+    return get_stream(STREAM_BEAM, &c.stream);
+}
+
+void beam_context_close(BeamStreamContext& c) {
+    (void)hipSetDevice(c.gpu);
+    if (c.stream) (void)hipStreamSynchronize(c.stream);
+    stream_clocks_forget(c.gpu, STREAM_BEAM);                       // (the mark events lent to the stream clock go away below)
+    c.tickets.destroy();
+}
+
+int beam_context_mark(std::mutex& mu, BeamStreamContext& c, const char* who, unsigned long long* ticket) {
+    if (!ticket) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "%sMark: null ticket", who);
+    std::lock_guard<std::mutex> lk(mu);
+    if (!c.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "%s: not initialized", who);
+    XENG_HIP(hipSetDevice(c.gpu));
+    return c.tickets.mark(c.stream, STREAM_BEAM, ticket);
+}
+
+int beam_context_wait(std::mutex& mu, const BeamStreamContext& c, const char* who, unsigned long long ticket) {
+    hipEvent_t ev = nullptr;
+    int gpu = 0;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!c.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "%s: not initialized", who);
+        if (!(ev = c.tickets.find(ticket))) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "%sWait: unknown ticket %llu", who, ticket);
+        gpu = c.gpu;
+    }
+    XENG_HIP(hipSetDevice(gpu));
+    XENG_HIP(hipEventSynchronize(ev));                              // (outside the lock: Run and Mark of other threads go on)
     return XENG_STATUS_SUCCESS;
 }
 
-int context_sync(const char* who, bool live, int gpu, hipStream_t stream) {
-    if (!live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "%s: not initialized", who);
-    XENG_HIP(hipSetDevice(gpu));
-    XENG_HIP(hipStreamSynchronize(stream));
+int beam_context_ticket_done(std::mutex& mu, const BeamStreamContext& c, const char* who, unsigned long long ticket, int* done) {
+    if (!done) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "%sTicketDone: null result", who);
+    std::lock_guard<std::mutex> lk(mu);
+    if (!c.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "%s: not initialized", who);
+    const hipEvent_t ev = c.tickets.find(ticket);
+    if (!ev) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "%sTicketDone: unknown ticket %llu", who, ticket);
+    XENG_HIP(hipSetDevice(c.gpu));
+    return TicketRing::query(ev, done);
+}
+
+int beam_context_sync(std::mutex& mu, const BeamStreamContext& c, const char* who) {
+    std::lock_guard<std::mutex> lk(mu);
+    if (!c.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "%s: not initialized", who);
+    XENG_HIP(hipSetDevice(c.gpu));
+    XENG_HIP(hipStreamSynchronize(c.stream));
     return XENG_STATUS_SUCCESS;
 }
 

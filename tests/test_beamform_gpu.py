@@ -299,6 +299,56 @@ def ticket_engine(gpu, name):
         def check(o):
             check_beams(o.download(np.complex64).reshape(expect.shape), expect)
         return run, check, expect.size * 8, ("upchan_mark", "upchan_wait"), (di, dw)
+    if name == "UpchanSumBeams":                    # one gulp per window, two windows per gulp, no PFB: no state between calls
+        from tests.test_upchan_beams_gpu import check as check_power
+        from tests.upchan_beams_ref import upchan_sum_beams
+        nchan, nbeam, nupchan, ntime, pair0, npair, nframe_sum = 3, 4, 8, 64, 0, 2, 4
+        v = (rng.standard_normal((nchan, nbeam, ntime)) + 1j * rng.standard_normal((nchan, nbeam, ntime))).astype(np.complex64)
+        gpu.ffi.call("xengUpchanSumBeamsInitialize", 0, nchan, nbeam, ntime, nupchan, pair0, npair, nframe_sum)
+        di = gpu.ffi.DeviceBuffer(v.nbytes).upload(v)
+        expect = upchan_sum_beams(v, nupchan, nframe_sum, 0, ntime, None, pair0, npair)
+
+        def run(o):
+            gpu.ffi.call("xengUpchanSumBeamsRun", di.ptr, o.ptr)
+
+        def check(o):
+            check_power(o.download(np.float32).reshape(expect.shape), expect)
+        return run, check, expect.size * 4, ("upchan_sum_beams_mark", "upchan_sum_beams_wait"), (di,)
+    if name == "UpchanSpectra":                     # four windows per gulp; |X|^2 <= 512 and S2 <= 2^20: every fp32 operation exact
+        from tests.upchan_spectra_ref import upchan_spectra_int
+        ninput, nchan, nupchan, ntime, nframe_sum = 40, 3, 2, 32, 4
+        vin = rng.integers(0, 256, (ntime, nchan, ninput), dtype=np.uint8)
+        gpu.ffi.call("xengUpchanSpectraInitialize", 0, ninput, nchan, ntime, nupchan, nframe_sum)
+        di = gpu.ffi.DeviceBuffer(vin.size).upload(vin)
+        expect = upchan_spectra_int(vin, nupchan, nframe_sum)
+        assert expect.max() <= 2 ** 24
+
+        def run(o):
+            gpu.ffi.call("xengUpchanSpectraRun", di.ptr, o.ptr)
+
+        def check(o):
+            assert np.array_equal(o.download(np.float32).reshape(expect.shape), expect.astype(np.float32))
+        return run, check, expect.size * 4, ("upchan_spectra_mark", "upchan_spectra_wait"), (di,)
+    if name == "Dedisp":                            # integer data: fp32 is exact, the output equals the int64 restatement
+        import ctypes
+        from tests.dedisp_ref import dedisperse
+        npair, nfine, nwin, ndm, max_delay, nprod = 1, 8, 4, 3, 2, 1
+        x = rng.integers(0, 10, (nwin, npair, nfine, 4)).astype(np.float32)
+        s = rng.integers(0, max_delay + 1, (ndm, nfine)).astype(np.int32)
+        s[-1, 0] = max_delay
+        gpu.ffi.call("xengDedispInitialize", 0, npair, nfine, nwin, ndm, max_delay, nprod)
+        gpu.ffi.call("xengDedispSetDelays", s.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        di = gpu.ffi.DeviceBuffer(x.nbytes).upload(x)
+        expect = dedisperse(x, s, None, nprod, np.int64)
+        assert np.abs(expect).max() < 2 ** 24
+
+        def run(o):                                 # from an empty history each time
+            gpu.ffi.call("xengDedispReset")
+            gpu.ffi.call("xengDedispRun", di.ptr, nwin, o.ptr)
+
+        def check(o):
+            assert np.array_equal(o.download(np.float32).reshape(expect.shape).astype(np.int64), expect)
+        return run, check, expect.size * 4, ("dedisp_mark", "dedisp_wait"), (di,)
     from tests.upchan_corr_ref import upchan_corr_int
     ninput, nchan, nupchan, ntime = 40, 3, 2, 30
     vin = rng.integers(0, 256, (ntime, nchan, ninput), dtype=np.uint8)
@@ -316,9 +366,9 @@ def ticket_engine(gpu, name):
     return run, check, re.size * 8, ("upchan_corr_mark", "upchan_corr_wait"), (di,)
 
 
-@pytest.mark.parametrize("name", ["Beamform", "Upchan", "UpchanCorr"])
+@pytest.mark.parametrize("name", ["Beamform", "Upchan", "UpchanCorr", "UpchanSumBeams", "UpchanSpectra", "Dedisp"])
 def test_completion_tickets_and_their_query(gpu, name):
-    """xeng<engine>Mark / Wait / TicketDone of the three engines on the beamformer's stream: tickets count from 1 after each
+    """xeng<engine>Mark / Wait / TicketDone of the six engines on the beamformer's stream: tickets count from 1 after each
     Initialize; a ticket whose kernels have completed reads done = 1 (and its output is there), every ticket does after Sync;
     unknown tickets (0, last + 1) and null pointers are errors; the query never blocks (it is what the blocks call before a
     blocking Wait)."""
