@@ -426,7 +426,55 @@ class HipBackend:
     def dedisp_sync(self):
         ffi.call("xengDedispSync")
 
-    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp)
+    # ---- boxcar single-pulse search of the dedispersed beams (BeamPulseSearch; include/xeng.h "Boxcar single-pulse search of the
+    # dedispersed beams"): a context of its own, its kernel on the beamformer's stream
+    def pulse_initialize(self, gpu, npair, ndm, nwin, nprod, nwidth, nstat):
+        return self._lib.xengPulseInitialize(int(gpu), int(npair), int(ndm), int(nwin), int(nprod), int(nwidth), int(nstat))
+
+    def pulse_run(self, in_arr, nwin_call, out_arr):
+        """Enqueue only: f32 [nwin_call][npair][ndm][nprod] in, [npair][ndm] records {f32 snr, i32 n_call, i32 iw, f32 B} out;
+        pulse_mark / wait cover it."""
+        return self._enq.xengPulseRun(in_arr.ptr, int(nwin_call), out_arr.ptr)
+
+    def pulse_reset(self):
+        """The next input counts as window 0: no baseline, no boxcar reaches back (host state only)."""
+        ffi.check("xengPulseReset", self._enq.xengPulseReset())
+
+    def pulse_info(self):
+        """(windows taken since the last reset, baseline blocks of them complete)"""
+        n, k = ctypes.c_longlong(), ctypes.c_longlong()
+        ffi.call("xengPulseGetInfo", ctypes.byref(n), ctypes.byref(k))
+        return n.value, k.value
+
+    def pulse_baseline(self, npair, ndm):
+        """Waits for the context's work; (c, m, var) of the last complete block, float32 [npair][ndm] each."""
+        import numpy as np
+        out = [np.empty((npair, ndm), np.float32) for _ in range(3)]
+        ffi.call("xengPulseGetBaseline", *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for a in out])
+        return tuple(out)
+
+    def pulse_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengPulseCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def pulse_mark(self):
+        return self._mark("xengPulseMark")
+
+    def pulse_wait(self, ticket):
+        self._wait("xengPulseTicketDone", "xengPulseWait", ticket)
+
+    def pulse_ticket_done(self, ticket):
+        """Never blocks: whether everything enqueued before the ticket has completed."""
+        d = ctypes.c_int()
+        ffi.check("xengPulseTicketDone", self._enq.xengPulseTicketDone(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
+        return bool(d.value)
+
+    def pulse_sync(self):
+        ffi.call("xengPulseSync")
+
+    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

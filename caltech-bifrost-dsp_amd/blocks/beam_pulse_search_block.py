@@ -1,0 +1,255 @@
+"""BeamPulseSearch: boxcar single-pulse search of the dedispersed beams.
+
+Reads the output ring of BeamDedisperse in device space: spans of
+  f32 [nwin][npair][ndm][nprod]        (nprod = 1: I; nprod = 4: I = XX + YY is formed from the first two words)
+and writes one record plane per input span to a host-space output ring,
+  [npair][ndm] x {f32 snr, i32 n_call, i32 iw, f32 B}      (blocks/pulse_search.py RECORD)
+per series (pair, trial) the best boxcar of the span: a running baseline over blocks of nstat windows, boxcars of 1, 2, 4 ...
+2^(nwidth-1) windows, the score in units of the previous block's sigma (xengPulse*, csrc/pulse_kernels.h; the definition is in
+include/xeng.h).  The baseline and the last windows live on the device across spans.  Once a plane's kernel has completed the
+block thresholds it and groups it over DM (pulse_candidates), adds to each candidate
+  sample = seq0 + (n_seq - dedisp_latency - width + 1) * acc_len,
+the beamformer-clock sample at which the boxcar begins at the top of the band (n_seq: the boxcar's last window counted from the
+beginning of the input sequence), publishes `ncand` and the last span's `candidates` through its stats and calls
+on_candidates(list) when the list is not empty.  No reference counterpart: the reference has no detection stage.
+
+The first dedisp_latency windows of a dedispersed sequence are partial sums: the baseline blocks that hold them sit too low, and
+the block after them is measured against that.  A record whose boxcar begins before window (ceil(dedisp_latency / nstat) + 1) *
+nstat of the sequence -- the first window whose previous block holds whole sums only -- is left out of the candidates (counted in
+`nstartup`); the planes in the output ring are what the kernel wrote.
+
+A new sequence or a gap in the input (spans this reader never saw) resets the context; after a gap the output restarts in a
+sequence of its own (UpchanSumBeams' rule, as in BeamDedisperse).  A `threshold` command takes effect at the next span.
+
+Not built: a robust baseline (a bright pulse in block k raises sigma for block k+1), clustering in time across spans, and a
+trigger writer."""
+import collections
+import json
+import math
+import time
+
+import numpy as np
+
+from ..backend import default_backend
+from ..ndarray import XArray
+from ..proclog import cpu_affinity
+from .block_base import Block, declare_streams, gulp_time, spans_outlive_release
+from .pulse_search import RECORD, as_records, pulse_candidates
+
+
+def _number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+
+
+class BeamPulseSearch(Block):
+    STREAM_DEPTH = 4        # spans whose kernels may be in flight behind the one being enqueued (in-repo rings)
+
+    def __init__(self, log, iring, oring, npair, ndm, nwin, nwidth=8, nstat=256, threshold=8.0, on_candidates=None, guarantee=True, core=-1,
+                 gpu=-1, etcd_client=None, backend=None):
+        super(BeamPulseSearch, self).__init__(log, iring, oring, guarantee, core, etcd_client=etcd_client)
+        who = "BEAM_PULSE_SEARCH"
+        if min(npair, ndm, nwin) <= 0:
+            raise ValueError("%s: sizes npair=%r ndm=%r nwin=%r must be positive" % (who, npair, ndm, nwin))
+        if not 1 <= nwidth <= 8:
+            raise ValueError("%s: nwidth %r not 1 to 8" % (who, nwidth))
+        if not 2 <= nstat <= 1 << 20 or 1 << (nwidth - 1) > nstat:
+            raise ValueError("%s: nstat %r not 2 to 2^20, or below the widest boxcar of %d windows" % (who, nstat, 1 << (nwidth - 1)))
+        if not _number(threshold):
+            raise ValueError("%s: threshold %r is not a finite number" % (who, threshold))
+        if on_candidates is not None and not callable(on_candidates):
+            raise ValueError("%s: on_candidates is not callable" % who)
+        if getattr(oring, 'space', 'system') not in ('system', 'cuda_host'):
+            raise ValueError("%s: the output ring is in space %r: the record planes go to a host-space ring" % (who, oring.space))
+        self.npair, self.ndm, self.nwin, self.nwidth, self.nstat, self.gpu = npair, ndm, nwin, nwidth, nstat, gpu
+        self.widths = [1 << iw for iw in range(nwidth)]
+        self.threshold = float(threshold)
+        self.on_candidates = on_candidates
+        self._bf = backend if backend is not None else default_backend()
+        declare_streams(iring, 'beam')          # (the kernel runs on the beamformer's stream)
+        declare_streams(oring, 'beam', 'copy')  # (the kernel writes the span itself, or a copy does from a device buffer)
+        if self.gpu != -1:
+            self._bf.set_device(self.gpu)
+        self.define_command_key('threshold', type=(int, float), condition=_number)
+        self.update_stats({'nwindow': 0, 'ngap': 0, 'ncand': 0, 'nstartup': 0, 'candidates': [], 'threshold': self.threshold})
+        self._ctx_nprod = None                  # nprod of the live context
+
+    def _initialize(self, nprod):
+        rv = self._bf.pulse_initialize(self.gpu, self.npair, self.ndm, self.nwin, nprod, self.nwidth, self.nstat)
+        if rv != self._bf.BF_STATUS_SUCCESS:
+            raise RuntimeError("xengPulseInitialize returned %d: %s" % (rv, self._bf.last_error()))
+        self._ctx_nprod = nprod
+
+    def _check_header(self, ihdr):
+        """The output of BeamDedisperse only; returns (nprod, acc_len, dedisp_latency, dms)."""
+        who = "BEAM_PULSE_SEARCH"
+        if 'ndm' not in ihdr:
+            raise ValueError("%s: the input carries no 'ndm': it has not been dedispersed" % who)
+        if ihdr.get('ndm') != self.ndm or ihdr.get('nbeam') != self.npair:
+            raise ValueError("%s: %r trials x %r pairs in the header, %d x %d configured" % (who, ihdr.get('ndm'), ihdr.get('nbeam'), self.ndm, self.npair))
+        if ihdr.get('nprod') not in (1, 4):
+            raise ValueError("%s: nprod %r in the header, not 1 or 4" % (who, ihdr.get('nprod')))
+        if not _number(ihdr.get('tsamp')) or not ihdr['tsamp'] > 0:
+            raise ValueError("%s: the header's 'tsamp' is %r" % (who, ihdr.get('tsamp')))
+        dms = ihdr.get('dms')
+        if not isinstance(dms, list) or len(dms) != self.ndm:
+            raise ValueError("%s: the header's 'dms' are not %d trials" % (who, self.ndm))
+        S = ihdr.get('dedisp_latency')
+        if not isinstance(S, int) or isinstance(S, bool) or S < 0:
+            raise ValueError("%s: the header's 'dedisp_latency' is %r" % (who, S))
+        acc_len = ihdr.get('acc_len')
+        if acc_len is None and isinstance(ihdr.get('nframe_sum'), int) and isinstance(ihdr.get('nupchan'), int):
+            acc_len = ihdr['nframe_sum'] * ihdr['nupchan']
+        if not isinstance(acc_len, int) or isinstance(acc_len, bool) or acc_len <= 0:
+            raise ValueError("%s: the header's 'acc_len' is %r: no window length in samples" % (who, acc_len))
+        return ihdr['nprod'], acc_len, S, dms
+
+    def output_header(self, ihdr, start):
+        ohdr = ihdr.copy()
+        ohdr.update(nwidth=self.nwidth, nstat=self.nstat, widths=list(self.widths), threshold=self.threshold, seq0=start)
+        return ohdr
+
+    def _finish(self, osp, meta):
+        """A plane whose kernel (and copy) has completed: threshold it, group it over DM, publish; then commit the span."""
+        try:
+            threshold, n0_seq, seq0, S, acc_len, dms = meta
+            plane = as_records(osp.data.numpy().copy(), self.npair, self.ndm)
+            trust = (-(-S // self.nstat) + 1) * self.nstat          # the first window whose previous block holds whole sums only
+            if n0_seq < trust + self.widths[-1]:
+                early = (plane['n'] >= 0) & (n0_seq + plane['n'] - np.left_shift(1, np.maximum(plane['iw'], 0)) + 1 < trust)
+                plane['n'][early] = -1
+                self.update_stats({'nstartup': self.stats['nstartup'] + int(early.sum())})
+            cands = pulse_candidates(plane, threshold, dms, self.widths)
+            for c in cands:
+                c['sample'] = seq0 + (n0_seq + c['window'] - S - c['width'] + 1) * acc_len
+            self.update_stats({'ncand': self.stats['ncand'] + len(cands), 'candidates': cands})
+            if cands and self.on_candidates is not None:
+                self.on_candidates(cands)
+        finally:
+            osp.close()
+
+    def main(self):
+        cpu_affinity.set_core(self.core)
+        if self.gpu != -1:
+            self._bf.set_device(self.gpu)
+        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
+        ogulp_size = self.npair * self.ndm * RECORD.itemsize
+        self.oring.resize(ogulp_size)
+        # Streaming, tickets and the staged copy into a pinned-host output ring: as BeamDedisperse (beam_dedisperse_block.py)
+        ospace = getattr(self.oring, 'space', 'system')
+        direct = ospace in (self._bf.space_in, 'cuda_host')     # (the kernel can write the span itself)
+        self._staged = spans_outlive_release(self.iring, self.oring) and ospace == 'cuda_host' and hasattr(self._bf, 'copy_async')
+        streaming = spans_outlive_release(self.iring, self.oring) and (direct or self._staged)
+        self._dev = None if streaming else XArray(shape=(ogulp_size,), dtype=np.uint8, space=self._bf.space_in)
+        self._stages_free = []
+        pending = collections.deque()           # (ticket, output span, input kept alive, device buffer or None, meta)
+        copying = collections.deque()           # (stamp of the copy, output span, device buffer, meta)
+
+        def finish_copies(keep):
+            while copying and (len(copying) > keep or self._bf.copy_done(copying[0][0])):
+                stamp, osp, stage, meta = copying.popleft()
+                self._bf.copy_wait(stamp)       # (returns at once when it is done)
+                self._stages_free.append(stage)
+                self._finish(osp, meta)
+
+        def retire(keep):
+            while len(pending) > keep:
+                ticket, osp, _, stage, meta = pending.popleft()
+                self._bf.pulse_wait(ticket)
+                if stage is None:
+                    self._finish(osp, meta)
+                else:
+                    copying.append((self._bf.copy_async(osp.data, stage), osp, stage, meta))
+            finish_copies(2 if keep else 0)
+
+        try:
+            with self.oring.begin_writing() as oring:
+                for iseq in self.iring.read(guarantee=self.guarantee):
+                    self._sequence(iseq, oring, ogulp_size, streaming, pending, retire)
+        finally:
+            # (spans of kernels in flight are not released by an exception before the stream is idle)
+            if pending or copying:
+                try:
+                    self._bf.pulse_sync()
+                    for stamp, _, _, _ in copying:
+                        self._bf.copy_wait(stamp)
+                except Exception:
+                    pass
+                pending.clear()
+                copying.clear()
+
+    def _sequence(self, iseq, oring, ogulp_size, streaming, pending, retire):
+        ihdr = json.loads(iseq.header.tostring())
+        self.sequence_proclog.update(ihdr)
+        nprod, acc_len, S, dms = self._check_header(ihdr)
+        retire(0)
+        if self._ctx_nprod != nprod:
+            self._initialize(nprod)
+        else:
+            self._bf.pulse_reset()              # (a new sequence starts from nothing: no baseline, no boxcar reaches back)
+        seq0 = ihdr['seq0']
+        ntime_span = self.nwin * acc_len        # samples of the beamformer's clock per span
+        igulp_size = self.nwin * self.npair * self.ndm * nprod * 4
+        this_gulp_time = seq0
+        expected = seq0
+        oseq = None
+        try:
+            prev_time = time.time()
+            for ispan in iseq.read(igulp_size):
+                if ispan.size < igulp_size:
+                    continue                    # a short final span is skipped (as the reference's gulp_nframe reader does)
+                this_gulp_time = gulp_time(ispan, seq0, igulp_size, ntime_span, this_gulp_time)
+                if this_gulp_time != expected:
+                    # windows this reader never saw: the baseline and the last windows do not line up with what comes now
+                    self._bf.pulse_reset()
+                    self.update_stats({'ngap': self.stats['ngap'] + 1})
+                    self.log.warning("BEAM_PULSE_SEARCH >> samples [%d, %d) were not read: the baseline starts again" % (expected, this_gulp_time))
+                    if oseq is not None:
+                        retire(0)
+                        oseq.end()
+                        oseq = None
+                expected = this_gulp_time + ntime_span
+                self.update_stats({'curr_sample': this_gulp_time})
+                if self.update_pending:
+                    self.update_command_vals()
+                    if self.command_vals.get('threshold') is not None:
+                        self.threshold = float(self.command_vals['threshold'])
+                held = ispan.data
+                if oseq is None:
+                    oseq = oring.begin_sequence(time_tag=this_gulp_time, header=json.dumps(self.output_header(ihdr, this_gulp_time)))
+                curr_time = time.time()
+                acquire_time = curr_time - prev_time
+                prev_time = curr_time
+                meta = (self.threshold, (this_gulp_time - seq0) // acc_len, seq0, S, acc_len, dms)
+                ospan = oseq.reserve(ogulp_size)
+                stage = None
+                try:
+                    if self._staged:
+                        stage = self._stages_free.pop() if self._stages_free else XArray(shape=(ogulp_size,), dtype=np.uint8, space=self._bf.space_in)
+                    target = stage if stage is not None else (ospan.data if streaming else self._dev)
+                    rv = self._bf.pulse_run(held, self.nwin, target)
+                    if rv != self._bf.BF_STATUS_SUCCESS:
+                        raise RuntimeError("xengPulseRun returned %d: %s" % (rv, self._bf.last_error()))
+                    self.update_stats({'nwindow': self.stats['nwindow'] + self.nwin, 'last_end_sample': this_gulp_time + ntime_span})
+                    osp, ospan = ospan, None
+                    if streaming:
+                        pending.append((self._bf.pulse_mark(), osp, held, stage, meta))
+                        retire(self.STREAM_DEPTH)
+                    else:
+                        self._bf.pulse_sync()
+                        try:
+                            osp.data_view(np.uint8)[...] = self._dev          # (synchronous copy)
+                        except Exception:
+                            osp.close()
+                            raise
+                        self._finish(osp, meta)
+                finally:
+                    if ospan is not None:
+                        ospan.close()
+                curr_time = time.time()
+                process_time = curr_time - prev_time
+                prev_time = curr_time
+                self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
+        finally:
+            retire(0)                           # every call in flight is complete (and every output span committed) first
+            if oseq is not None:
+                oseq.end()

@@ -110,6 +110,11 @@ SYMBOLS = {
     "xengDedispRun": [_vp, _i, _vp], "xengDedispReset": [], "xengDedispGetInfo": [_pi, ctypes.POINTER(ctypes.c_longlong)],
     "xengDedispMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengDedispWait": [ctypes.c_ulonglong], "xengDedispTicketDone": [ctypes.c_ulonglong, _pi],
     "xengDedispSync": [], "xengDedispDestroy": [], "xengDedispCheckGuards": [_pi],
+    "xengPulseInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengPulseRun": [_vp, _i, _vp], "xengPulseReset": [],
+    "xengPulseGetInfo": [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)],
+    "xengPulseGetBaseline": [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)],
+    "xengPulseCheckGuards": [_pi], "xengPulseMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengPulseWait": [ctypes.c_ulonglong],
+    "xengPulseTicketDone": [ctypes.c_ulonglong, _pi], "xengPulseSync": [], "xengPulseDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -158,6 +163,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengUpchanSpectraRun", "xengUpchanSpectraRunParts", "xengUpchanSpectraPrime", "xengUpchanSpectraPrimeParts", "xengUpchanSpectraReset",
                 "xengUpchanSpectraMark", "xengUpchanSpectraTicketDone",
                 "xengDedispRun", "xengDedispReset", "xengDedispMark", "xengDedispTicketDone",
+                "xengPulseRun", "xengPulseReset", "xengPulseMark", "xengPulseTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

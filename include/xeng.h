@@ -679,6 +679,60 @@ int xengDedispTicketDone(unsigned long long ticket, int *done);
 int xengDedispSync(void);
 int xengDedispDestroy(void);
 
+/* ---------------------------------------------------------------- Boxcar single-pulse search of the dedispersed beams
+ * BeamPulseSearch (no reference counterpart: the reference has no detection stage): per series a running baseline, a bank of
+ * boxcar matched filters of widths 1, 2, 4 ... 2^(nwidth-1) windows and the peak per call, streaming across calls with its state
+ * on the device.  A context of its own, independent of all others, whose kernel runs on the beamformer's stream -- rings
+ * declared 'beam' cover it, and xengBeamformSync waits for it too.  One kernel per call (csrc/pulse_kernels.h).
+ *   in       f32[nwin_call][npair][ndm][nprod], the output span of xengDedispRun unchanged; 16-byte aligned; never written.
+ *            1 <= nwin_call <= nwin.  A series is one (p, d).  nprod = 1: z[n] = in[n][p][d][0]; nprod = 4:
+ *            z[n] = fl(in[n][p][d][0] + in[n][p][d][1]), I = XX + YY.  n counts windows since the last reset (xengPulseReset,
+ *            Initialize).
+ * Everything below is fp32 and fl() is one rounding to fp32; no product is contracted into a sum except where fmaf is written.
+ *   baseline   Block k is the windows [k*nstat, (k+1)*nstat).  At its first window c_k = z[k*nstat] and a = q = +0.  Then for
+ *            every window of the block in ascending n, the first included: delta = fl(z[n] - c_k), a = fl(a + delta),
+ *            q = fmaf(delta, delta, q).  After its last window m_k = fl(a*r) with r = 1.0f/(float)nstat formed on the host, and
+ *            v_k = fmaf(-m_k, m_k, fl(q*r)).  The block is VALID iff 0 < v_k < +inf; then g_k = 1/sqrt(v_k) (evaluated as
+ *            fl(1.0f / fl(sqrt(v_k))) with correctly rounded fp32 sqrt and divide; deterministic, but the library's choice and not
+ *            part of the word-for-word contract).  The pivot c_k keeps the one-pass variance well conditioned: a series of summed
+ *            powers has mean/sigma of 55-100, and without a pivot fp32 loses three digits of sigma.
+ *   series   A window n in a block k >= 1 whose block k-1 is valid has y[n] = fl(fl(z[n] - c_{k-1}) - m_{k-1}).  Every other
+ *            window has no y.
+ *   boxcars  Widths w = 2^iw, iw = 0..nwidth-1.  B_1[n] = y[n]; B_{2w}[n] = fl(B_w[n] + B_w[n-w]): a pairwise tree, the newer
+ *            half first, so the order is a function of w alone.
+ *   score    snr_w[n] = fl(fl(B_w[n] * g_{k-1}) * rho_iw), k the block of n and rho_iw = (float)2^(-iw/2) from the host.
+ *            (n, iw) is SCORED iff n - w + 1 >= nstat, every window of the boxcar has a y, and the score is not NaN.
+ *   out      [npair][ndm] records of four 32-bit words {f32 snr, i32 n_call, i32 iw, f32 B}, 16-byte aligned: of the scored
+ *            (n, iw) with n in this call the one with the largest snr, among equal scores the smallest n, then the smallest iw;
+ *            n_call is the window's index within the call and B = B_w[n].  A series with nothing scored in the call gets
+ *            {+0.0f, -1, -1, +0.0f}.  Each record is one 16-byte store; nothing outside npair*ndm*16 bytes is written.
+ *   state    per series c, m, v, g of the last complete block and c, a, q of the running one, and a ring of the last
+ *            2^(nwidth-1) - 1 + nwin values of y (series the fastest axis), all between two guard bands of 64 KiB.
+ * A run gives the same records bit for bit however it is split over calls (merge the calls' records: strictly greater replaces,
+ * in call order), whatever else runs on the GPU.  Exact on integer data while the sums stay below 2^24.
+ * Rejected at Initialize, before any device is touched: a non-positive size, nprod outside {1, 4}, nwidth outside 1..8, nstat
+ * outside 2..2^20, 2^(nwidth-1) > nstat, npair*ndm > 2^24, 2^(nwidth-1) - 1 + 2*nwin > 256 (what one work-group's LDS holds).
+ * Rejected by Run without a launch: a NULL or misaligned pointer, nwin_call outside 1..nwin.  Every call without a context, and
+ * GetBaseline before a block has completed: XENG_STATUS_INVALID_STATE. */
+int xengPulseInitialize(int gpu, int npair, int ndm, int nwin, int nprod, int nwidth, int nstat);
+/* enqueue only: nwin_call windows in, one record per series out */
+int xengPulseRun(const void *in_dev, int nwin_call, void *out_dev);
+/* host state only, nothing is launched and nothing cleared: the next input counts as window 0.  The kernel decides by index
+ * what lies before window 0 or before nstat and never looks at what the buffers still hold. */
+int xengPulseReset(void);
+/* windows taken since the last reset, and how many baseline blocks of them are complete */
+int xengPulseGetInfo(long long *nwindows_since_reset, long long *nblocks_complete);
+/* c, m and v of the last complete block into host f32[npair][ndm] each; waits for the context's work in flight */
+int xengPulseGetBaseline(float *c, float *m, float *var);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengPulseCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengPulseMark(unsigned long long *ticket);
+int xengPulseWait(unsigned long long ticket);
+int xengPulseTicketDone(unsigned long long ticket, int *done);
+int xengPulseSync(void);
+int xengPulseDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */

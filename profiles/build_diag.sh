@@ -10,7 +10,7 @@ for f in xeng_util xcorr corracc beamform ingest slab ring xeng_bfarray; do
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -DXENG_DIAGNOSTICS -c $f.hip -o $B/$f.o &
 done
 # the fine-channel family (complex fp32 FFTs: -fno-slp-vectorize as in csrc/Makefile); XENG_SPECTRA_NSLOT lives in upchan_spectra
-for f in upchan upchan_corr upchan_beams upchan_spectra dedisp; do
+for f in upchan upchan_corr upchan_beams upchan_spectra dedisp pulse; do
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -fno-slp-vectorize -DXENG_DIAGNOSTICS -c $f.hip -o $B/$f.o &
 done
 wait
