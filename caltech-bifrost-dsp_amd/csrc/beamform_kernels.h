@@ -432,7 +432,7 @@ constexpr int BI_XSLOTS = BI_XCHUNK / 1024 / 4;     // voltage pieces issued per
 constexpr int BI_RING = BI_RING_STAGES;
 constexpr int BI_QMAX = 127 * (255 * 255 + 255 + 1);
 
-// ---- precision of the fixed-point weights (what keeps the int8 route inside the 1e-5 bar for ANY weights) --------
+// ---- precision of the fixed-point weights (what keeps the int8 route inside the 1e-5 bar; exact condition below) --
 // A row scale taken from the row maximum makes the quantisation step of every weight 1.2e-7 of the LARGEST one.  A few
 // dominant weights (a huge calibration gain on a dead or quiet input) would then cost the ordinary weights their
 // significant bits while contributing nothing to the output.  So per (channel, beam) row:
@@ -441,15 +441,30 @@ constexpr int BI_QMAX = 127 * (255 * 255 + 255 + 1);
 //     bf_src/cublas_beamform.cu:248-276).  Rule: E = the smallest fp32 exponent such that at most BI_ROW_OUT entries
 //     have a larger exponent of max(|re|, |im|) and none of those lies within BI_GAP_BINADES binades (they stand
 //     out: the top of a smooth distribution is not an outlier); the row scale is the exact maximum of the rest.
-//   * if the largest remaining entry is still more than BI_GUARD_BINADES binades above the row's MEDIAN non-zero entry
-//     (a heavy tail rather than a few outliers: the output may be made by weights that are small against the row
-//     scale), or a beam tile collects more than BI_TILE_OUT distinct outlier inputs, the (channel, beam tile) is
-//     routed to the bf16x3 kernel (every weight exact to 24 bits on its own scale); decided on the device:
-//     route[c][tile] = 1.  Inside the guard the step is < 2^-23 * 2^(BI_GUARD_BINADES+1) of the median weight.
+//   * the guard.  Among the row's non-zero entries ("non-zero" = a non-zero fp32 exponent field of max(|re|, |im|): zeros
+//     and denormals do not count) take the MEDIAN and the LOWER-EIGHTH entry: the largest exponent bucket with at
+//     least 1/2, respectively BI_LOW_NUM/BI_LOW_DEN = 7/8, of them at or above it.  If the largest remaining entry is
+//     more than BI_GUARD_BINADES binades above the median (a heavy tail rather than a few outliers: the output may be
+//     made by weights that are small against the row scale), or the median is more than BI_SPREAD_BINADES binades
+//     above the lower-eighth entry (the upper half of the row is itself dominant: gains on MOST of the inputs), or a
+//     beam tile collects more than BI_TILE_OUT distinct outlier inputs, the (channel, beam tile) is routed to the
+//     bf16x3 kernel (every weight exact to 24 bits on its own scale); decided on the device: route[c][tile] = 1.
+// What this guarantees.  The step of every weight on the digits is m * 2^-23 (m: the inlier maximum), an rms error of
+// 4.9e-8 m per complex weight.  For voltages of random phase a row's error is 4.9e-8 * m / (rms of the weights on LIVE
+// inputs) of the row's output RMS, and its maximum over a gulp some four times that: inside the 1e-5 bar while
+//     m <= 50 * (rms of the weights on live inputs).
+// An unrouted row has m < 2^(BI_GUARD_BINADES+1) = 32 times its median and its median < 2^(BI_SPREAD_BINADES+1) = 16 times
+// its lower-eighth entry.  That secures the condition when the weights that make the output lie within a binade or two
+// of one another (as calibrated weights do) and are MORE THAN ONE EIGHTH of the row's non-zero entries: up to 7/8 of a
+// row's non-zero weights may be dominant ones on dead or quiet inputs.  NOT for "any" weights: with more than 7/8 of the
+// non-zero entries dominant and dead both quantiles sit among them and nothing is routed.  (Measurements: DESIGN.md 4.5;
+// numpy restatement of the rule: tests/beam_route_ref.py.)
 constexpr int BI_ROW_OUT = 8;
 constexpr int BI_TILE_OUT = 32;
 constexpr int BI_GUARD_BINADES = 4;
 constexpr int BI_GAP_BINADES = 3;
+constexpr int BI_SPREAD_BINADES = 3;
+constexpr int BI_LOW_NUM = 7, BI_LOW_DEN = 8;
 
 // pass 1a, grid (8 * nbtile, nchan), 256 threads = 4 waves = 4 rows.  Outputs per row: scale (with the 1/16 of the
 // voltage scaling folded in), wmax (inlier maximum, for pass 2), row_out[BI_ROW_OUT] (outlier inputs, -1 = none);
@@ -461,12 +476,12 @@ __global__ __launch_bounds__(256) void beam_weights_rowstat_kernel(const float* 
     // (reductions go through LDS memory and LDS atomics, not through ds_bpermute: see beam_integrate_kernel)
     __shared__ int hist[4][256];
     __shared__ int lanetot[4][64];
-    __shared__ int red[4][4];                                // per wave: E (min), Emed (max), inlier maximum (max, float bits), bucket 0
+    __shared__ int red[4][5];                                // per wave: E (min), Emed (max), inlier maximum (max, float bits), bucket 0, Elow (max)
     const int c = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + wave;                  // beam index within the padded tiles
     const bool live = row < nbeam;
     for (int k = lane; k < 256; k += 64) hist[wave][k] = 0;
-    if (lane == 0) { red[wave][0] = 1 << 30; red[wave][1] = 0; red[wave][2] = 0; }
+    if (lane == 0) { red[wave][0] = 1 << 30; red[wave][1] = 0; red[wave][2] = 0; red[wave][4] = 0; }
     __syncthreads();
     const float* wrow = w + ((size_t)c * nbeam + (live ? row : 0)) * ninput * 2;
     if (live)
@@ -487,14 +502,16 @@ __global__ __launch_bounds__(256) void beam_weights_rowstat_kernel(const float* 
     for (int l = lane; l < 64; l++) suf += lanetot[wave][l];
     int all = suf;
     for (int l = 0; l < lane; l++) all += lanetot[wave][l];
-    // ... and the bucket of the median non-zero entry: the largest bucket b >= 1 with at least half of them at or above it
+    // ... and the buckets of the median and of the lower-eighth non-zero entry: the largest bucket b >= 1 with at least 1/2,
+    // respectively 7/8, of them at or above it
     const int n_nz = all - red[wave][3];
-    int above = suf - tot, Emed = 0;
+    int above = suf - tot, Emed = 0, Elow = 0;
 #pragma unroll
     for (int q = 3; q >= 0; q--) {
         hist[wave][4 * lane + q] = above;                    // entries strictly above bucket 4*lane+q (own buckets: no race)
         above += cnt[q];                                     // now: entries at or above it
         if (2 * above >= n_nz && 4 * lane + q >= 1) Emed = max(Emed, 4 * lane + q);
+        if (BI_LOW_DEN * above >= BI_LOW_NUM * n_nz && 4 * lane + q >= 1) Elow = max(Elow, 4 * lane + q);
     }
     __syncthreads();
     int E = 1 << 30;
@@ -505,9 +522,11 @@ __global__ __launch_bounds__(256) void beam_weights_rowstat_kernel(const float* 
     }
     if (E < (1 << 30)) atomicMin(&red[wave][0], E);
     if (Emed > 0) atomicMax(&red[wave][1], Emed);
+    if (Elow > 0) atomicMax(&red[wave][4], Elow);
     __syncthreads();
     E = red[wave][0];
     Emed = red[wave][1];
+    Elow = red[wave][4];
     // second sweep: inlier maximum / sum of squares, outlier list (wave-level compaction)
     float m = 0.f;
     int nout = 0;
@@ -533,7 +552,7 @@ __global__ __launch_bounds__(256) void beam_weights_rowstat_kernel(const float* 
     if (lane == 0) {
         scale[(size_t)c * nbtile * 32 + row] = m > 0.f ? m / (float)BI_QMAX / 16.f : 0.f;
         wmax[(size_t)c * nbtile * 32 + row] = m;
-        if (n_nz > 0 && (int)((__float_as_uint(m) >> 23) & 0xFF) - Emed > BI_GUARD_BINADES) {
+        if (n_nz > 0 && ((int)((__float_as_uint(m) >> 23) & 0xFF) - Emed > BI_GUARD_BINADES || Emed - Elow > BI_SPREAD_BINADES)) {
             route[c * nbtile + (row >> 5)] = 1;
             route[nchan * nbtile] = 1;
         }

@@ -9,8 +9,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import xeng_oracle as orc  # noqa: E402
-
-BEAM_RTOL = 1e-5   # BASELINE.json north_star: "beamformer fp32 within 1e-5 rel"
+from tests.beam_route_cases import block_weights  # noqa: E402
+from tests.beam_route_ref import BEAM_RTOL, check_beams_rows, check_power_rows  # noqa: E402  (BASELINE.json north_star: 1e-5 rel)
 
 
 @pytest.fixture(scope="module")
@@ -127,20 +127,6 @@ def test_beamform_golden(gpu, golden_dir, tag):
     gpu.ffi.call("xengBeamformDestroy")
 
 
-def block_weights(nchan, nbeam, ninput, sfreq=50e6, chan_bw=23925.78125, seed=0xaabbccdd):
-    """Weights as the Beamform block builds them (beamform_block.py:343-350) from the test's
-    random delays / amps / cal gains (beamformer_test.py:131-139)."""
-    rng = np.random.default_rng(seed)
-    freqs = sfreq + np.arange(nchan) * chan_bw
-    w = np.zeros((nchan, nbeam, ninput), np.complex64)
-    for b in range(nbeam):
-        delays_ns = rng.uniform(0, 12, ninput)
-        amps = rng.uniform(10, 17, ninput)
-        cal = (rng.uniform(-1, 1, (nchan, ninput)) + 1j * rng.uniform(-1, 1, (nchan, ninput))).astype(np.complex64)
-        w[:, b, :] = amps * np.exp(1j * 2 * np.pi * freqs[:, None] * delays_ns * 1e-9) * cal
-    return w
-
-
 @pytest.mark.parametrize("ntime,nchan,ninput,nbeam", [
     (32, 2, 64, 32),
     (100, 3, 40, 5),        # ragged: time not /32, inputs not /64, beams not /32
@@ -152,7 +138,9 @@ def test_beamform_vs_oracle(gpu, ntime, nchan, ninput, nbeam):
     vin = rng.integers(0, 256, (ntime, nchan, ninput), dtype=np.uint8)
     w = block_weights(nchan, nbeam, ninput)
     got, _ = run_beamform(gpu, vin, w, ntime, nchan, ninput, nbeam)
-    check_beams(got, orc.beamform(vin, w, ntime, nchan, ninput, nbeam))
+    exp = orc.beamform(vin, w, ntime, nchan, ninput, nbeam)
+    check_beams(got, exp)
+    check_beams_rows(got, exp)                      # ... and every (channel, beam) row against its own RMS
     gpu.ffi.call("xengBeamformDestroy")
 
 
@@ -164,7 +152,9 @@ def test_config4_full_size(gpu):
     vin = rng.integers(0, 256, (ntime, nchan, ninput), dtype=np.uint8)
     w = block_weights(nchan, nbeam, ninput)
     got, dout = run_beamform(gpu, vin, w, ntime, nchan, ninput, nbeam)
-    check_beams(got, orc.beamform(vin, w, ntime, nchan, ninput, nbeam))      # every channel, float64 oracle
+    exp_v = orc.beamform(vin, w, ntime, nchan, ninput, nbeam)
+    check_beams(got, exp_v)      # every channel, float64 oracle
+    check_beams_rows(got, exp_v)
     # linearity: beams(2w) == 2*beams(w) exactly in fp32 (power-of-two scaling)
     got2, _ = run_beamform(gpu, vin, (2 * w).astype(np.complex64), ntime, nchan, ninput, nbeam)
     assert np.array_equal(got2, 2 * got)
@@ -174,6 +164,7 @@ def test_config4_full_size(gpu):
     gp = dp.download(np.float32).reshape(nbeam // 2, ntime // ns, nchan, 4)
     exp = orc.beamform_integrate(got, ns)
     assert np.all(np.isclose(gp, exp, rtol=1e-5, atol=1e-5 * np.abs(exp).max()))
+    check_power_rows(gp, got, ns, 0.0)              # per (pair, block, channel): the summation bound on the device's own voltages
     gpu.ffi.call("xengBeamformDestroy")
 
 
@@ -191,8 +182,10 @@ def test_integrated_mode(gpu):
     gpu.ffi.call("xengBeamformRun", di.ptr, do.ptr, dw.ptr)
     gpu.ffi.call("xengBeamformSync")
     got = do.download(np.float32).reshape(nbeam // 2, nblk, nchan, 4)
-    exp = orc.beamform_integrate(orc.beamform(vin, w, ntime, nchan, ninput, nbeam), ntime // nblk)
+    exp_v = orc.beamform(vin, w, ntime, nchan, ninput, nbeam)
+    exp = orc.beamform_integrate(exp_v, ntime // nblk)
     assert np.all(np.isclose(got, exp, rtol=1e-5, atol=1e-5 * np.abs(exp).max()))
+    check_power_rows(got, exp_v, ntime // nblk, BEAM_RTOL)     # per (pair, block, channel): the voltage bar, propagated
     gpu.ffi.call("xengBeamformDestroy")
 
 
@@ -215,7 +208,8 @@ def test_integrated_mode_fused_epilogue(gpu, ntime, nchan, ninput, nbeam, nblk):
     di = gpu.ffi.DeviceBuffer(vin.size).upload(vin)
     dw = gpu.ffi.DeviceBuffer(w.nbytes).upload(w)
     do = gpu.ffi.DeviceBuffer((nbeam // 2) * nblk * nchan * 16)
-    exp = orc.beamform_integrate(orc.beamform(vin, w, ntime, nchan, ninput, nbeam), ntime // nblk)
+    exp_v = orc.beamform(vin, w, ntime, nchan, ninput, nbeam)
+    exp = orc.beamform_integrate(exp_v, ntime // nblk)
     tm, cn = (ctypes.c_double * 2)(), (ctypes.c_int * 2)()
     gpu.ffi.call("xengBeamformSetProfiling", 1)
     gpu.ffi.call("xengBeamformGetTimes", tm, cn)
@@ -226,6 +220,7 @@ def test_integrated_mode_fused_epilogue(gpu, ntime, nchan, ninput, nbeam, nblk):
         gpu.ffi.call("xengBeamformSync")
         outs.append(do.download(np.float32).reshape(nbeam // 2, nblk, nchan, 4))
         assert np.all(np.isclose(outs[-1], exp, rtol=1e-5, atol=1e-5 * np.abs(exp).max())), k
+        check_power_rows(outs[-1], exp_v, ntime // nblk, BEAM_RTOL)
     gpu.ffi.call("xengBeamformGetTimes", tm, cn)
     gpu.ffi.call("xengBeamformSetProfiling", 0)
     if os.environ.get("XENG_BEAM", "int8x3") == "int8x3" and not os.environ.get("XENG_BEAM_F32"):
@@ -464,7 +459,9 @@ def test_beamform_kernel_routes(gpu, ntime, nchan, ninput, nbeam, kind, mode):
     os.environ["XENG_BEAM"] = mode
     try:
         got, _ = run_beamform(gpu, vin, w, ntime, nchan, ninput, nbeam)
-        err = check_beams(got, orc.beamform(vin, w, ntime, nchan, ninput, nbeam))
+        exp = orc.beamform(vin, w, ntime, nchan, ninput, nbeam)
+        err = check_beams(got, exp)
+        check_beams_rows(got, exp)
         if mode == "int8x3":
             # the precision control took the expected route (beamform_kernels.h): a few dominant weights are added in
             # fp32 by the int8x3 kernel itself; too many of them send the (channel, beam tile) to the bf16x3 kernel
@@ -524,10 +521,12 @@ def test_two_part_gulp_equals_the_contiguous_gulp(gpu, mode, ninput, nchan, ntim
     ffi.call("xengBeamformSync")
     a, b = o1.download(np.uint32), o2.download(np.uint32)
     assert np.array_equal(a, b)
-    # (values: against the oracle on two channels with ordinary weight rows -- channel 0's rows span ten decades, which is a
-    # routing test case, test_beamform_kernel_routes, not an accuracy one)
-    exp = orc.beamform(np.ascontiguousarray(vin[:, 1:3]), np.ascontiguousarray(w[1:3]), ntime, 2, ninput, nbeam)
-    check_beams(o2.download(np.complex64).reshape(nchan, nbeam, ntime)[1:3], exp)
+    # (values: against the oracle; globally on two channels with rows of one scale, per row on channel 0 too, whose rows span
+    # ten decades)
+    got = o2.download(np.complex64).reshape(nchan, nbeam, ntime)
+    exp = orc.beamform(np.ascontiguousarray(vin[:, 0:3]), np.ascontiguousarray(w[0:3]), ntime, 3, ninput, nbeam)
+    check_beams(got[1:3], exp[1:3])
+    check_beams_rows(got[0:3], exp)
     with pytest.raises(ffi.XengError):
         ffi.call("xengBeamformRunParts", dparts.ptr + p0_off, ntime, dparts.ptr + p1_off, o2.ptr, dw.ptr, 1)     # first part = the whole gulp
     assert row * ntime0 % 4 == 0 or True
