@@ -1,8 +1,8 @@
-"""UpchanSumBeams on the MI355X: xengUpchanSumBeams* against the float64 restatement (tests/upchan_beams_ref.py) for every
-nupchan, PFB taps 1..8 with random asymmetric coefficients, windows within a gulp and spanning gulps, pair subsets, and at the
-live size; bytes past the output untouched; bit identity from run to run and beside an X-engine contraction; the sign of
-Im(XY*); the cross-path equality with UpchanBeamform's dual-pol mode on the same 4-bit input; and the block on device rings
-beside BeamformSumBeams.  No wall-clock assertions."""
+"""UpchanSumBeams on the MI355X: xengUpchanSumBeams* against the float64 restatement (tests/upchan_beams_ref.py; the whole
+output and every row of it) for every nupchan, PFB taps 1..8 with random asymmetric coefficients, windows within a gulp and
+spanning gulps, pair subsets, and at the live size; bytes past the output untouched; bit identity from run to run and beside
+an X-engine contraction; the sign of Im(XY*); the cross-path equality with UpchanBeamform's dual-pol mode on the same 4-bit
+input; and the block on device rings beside BeamformSumBeams.  No wall-clock assertions."""
 import ctypes
 
 import numpy as np
@@ -18,6 +18,7 @@ from tests.gpu_util import Xgpu, synth_voltages  # noqa: E402
 from tests.pipeline_util import LOG, Sink, Source, run_blocks, source_header  # noqa: E402
 from tests.test_blocks_cpu import _beam_cmds  # noqa: E402
 from tests.upchan_beams_ref import beam_channelise, sum_beams, upchan_sum_beams  # noqa: E402
+from tests.upchan_local_ref import check_rows, row_ratios  # noqa: E402
 from tests.upchan_pfb_ref import upchan_beamform_pfb  # noqa: E402
 
 POISON = 0xA5
@@ -29,10 +30,16 @@ def _fp(h):
     return None if h is None else h.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 
 
-def check(got, exp, bar=1e-5):
+def check(got, exp, bar=1e-5, rows=True):
+    """Within `bar` of the output's RMS, and every row within `bar` of its own scale (tests/upchan_local_ref.py check_rows);
+    rows=False (the live size): the worst row's figure is printed, not asserted."""
     rms = np.sqrt(np.mean(np.abs(exp) ** 2))
     err = np.max(np.abs(got.astype(np.float64) - exp))
     assert rms > 0 and err <= bar * rms, "max |err| %.3g = %.3g of RMS %.3g" % (err, err / rms, rms)
+    if rows:
+        check_rows(got, exp, bar)
+    else:
+        print("live size %s: max |err| = %.3g of the RMS, worst row %.3g of its own" % (got.shape, err / rms, np.max(row_ratios(got, exp))))
 
 
 def _info():
@@ -127,7 +134,7 @@ def test_live_size_long_window(P):
             V = beam_channelise(s, N, h, s.shape[-1] - ntime, ntime)
             exp = exp + sum_beams(V, ntime // N)
             prev = gulp
-        check(ub.result(), exp)
+        check(ub.result(), exp, rows=False)
     ffi.call("xengUpchanSumBeamsDestroy")
 
 

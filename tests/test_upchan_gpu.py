@@ -1,7 +1,7 @@
 """xengUpchan* and UpchanBeamform on the MI355X: the fused FFT + beamform kernel against the float64 restatement of the
-reference's chain (tests/upchan_ref.py) at 1e-5 of the output's RMS, in both modes and for every nupchan; a tone that pins
-sign, shift and order of the fine channels; bytes past the output untouched; two-part gulps, weight versions, run-to-run and
-beside-the-X-engine bit identity; and the blocks on device rings.  No wall-clock assertions."""
+reference's chain (tests/upchan_ref.py) at 1e-5 of the output's RMS and of every row's own, in both modes and for every
+nupchan; a tone that pins sign, shift and order of the fine channels; bytes past the output untouched; two-part gulps,
+weight versions, run-to-run and beside-the-X-engine bit identity; and the blocks on device rings.  No wall-clock assertions."""
 import json
 import os
 import struct
@@ -20,6 +20,7 @@ from tests.gpu_util import Xgpu, synth_voltages  # noqa: E402
 from tests.pipeline_util import LOG, Sink, Source, run_blocks, source_header  # noqa: E402
 from tests.test_blocks_cpu import _beam_cmds  # noqa: E402
 from tests.upchan_ref import upchan_beamform  # noqa: E402
+from tests.upchan_local_ref import check_rows, row_ratios  # noqa: E402
 
 POISON = 0xA5
 GUARD = 4096
@@ -79,10 +80,16 @@ def upchan():
         u.close()
 
 
-def check(got, exp):
+def check(got, exp, rows=True):
+    """Within 1e-5 of the output's RMS, and every row within 1e-5 of its own (tests/upchan_local_ref.py check_rows); rows=False
+    (the full-size point): the worst row's figure is printed, not asserted."""
     rms = np.sqrt(np.mean(np.abs(exp) ** 2))
     err = np.max(np.abs(got.astype(exp.dtype) - exp))
     assert rms > 0 and err <= 1e-5 * rms, "max |err| %.3g = %.3g of RMS %.3g" % (err, err / rms, rms)
+    if rows:
+        check_rows(got, exp)
+    else:
+        print("full size %s: max |err| = %.3g of the RMS, worst row %.3g of its own" % (got.shape, err / rms, np.max(row_ratios(got, exp))))
 
 
 @pytest.mark.parametrize("nupchan", [8, 16, 32, 64])
@@ -110,7 +117,7 @@ def test_full_size_against_restatement(upchan, nbeam, nframe_sum):
     vin = rng.integers(0, 256, (ntime, nchan, ninput), dtype=np.uint8)
     w = rand_weights(rng, nchan, N, nbeam, ninput)
     u = upchan(ninput, nchan, ntime, N, nbeam, nframe_sum)
-    check(u.run(vin, w, version=7), upchan_beamform(vin, w, N, nbeam, nframe_sum))
+    check(u.run(vin, w, version=7), upchan_beamform(vin, w, N, nbeam, nframe_sum), rows=False)
 
 
 @pytest.mark.parametrize("nupchan", [8, 32, 64])

@@ -1,8 +1,8 @@
 """The PFB front end of xengUpchan* / xengUpchanCorr* on the MI355X: the kernels against the float64 restatement
-(tests/upchan_pfb_ref.py) over consecutive gulps with random asymmetric coefficients (so that a reversed tap or sample index
-cannot pass), bit identity (parts, repeats, nstage, Reset, SetPfb(1, NULL), Prime), bytes past the output untouched, the
-leakage of a quantised tone, the argument checks that need a context, and both blocks on device rings with a gap and two
-sequences.  No wall-clock assertions."""
+(tests/upchan_pfb_ref.py; the whole output and every row of it) over consecutive gulps with random asymmetric coefficients
+(so that a reversed tap or sample index cannot pass), bit identity (parts, repeats, nstage, Reset, SetPfb(1, NULL), Prime),
+bytes past the output untouched, the leakage of a quantised tone, the argument checks that need a context, and both blocks
+on device rings with a gap and two sequences.  No wall-clock assertions."""
 import ctypes
 import json
 import types
@@ -18,6 +18,7 @@ from caltech_bifrost_dsp_amd.blocks import UpchanBeamform, UpchanCorr  # noqa: E
 from caltech_bifrost_dsp_amd.blocks.pfb import pfb_coeffs  # noqa: E402
 from caltech_bifrost_dsp_amd.ring import Ring  # noqa: E402
 from tests.pipeline_util import LOG, Sink, source_header  # noqa: E402
+from tests.upchan_local_ref import check_rows  # noqa: E402
 from tests.upchan_pfb_ref import pfb_fine_select, upchan_beamform_pfb, upchan_corr_pfb  # noqa: E402
 
 POISON = 0xA5
@@ -35,9 +36,11 @@ def set_pfb(name, ntap, h):
 
 
 def check(got, exp):
+    """Within 1e-5 of the output's RMS, and every row within 1e-5 of its own (tests/upchan_local_ref.py check_rows)."""
     rms = np.sqrt(np.mean(np.abs(exp) ** 2))
     err = np.max(np.abs(got.astype(exp.dtype) - exp))
     assert rms > 0 and err <= 1e-5 * rms, "max |err| %.3g = %.3g of RMS %.3g" % (err, err / rms, rms)
+    check_rows(got, exp)
 
 
 class UP:

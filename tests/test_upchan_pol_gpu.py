@@ -1,8 +1,8 @@
 """UpchanBeamform's dual-pol mode on the MI355X (xengUpchanInitializeDualPol): [XX, YY, Re(XY*), Im(XY*)] per pair of beams
-against the float64 restatement (tests/upchan_pol_ref.py) at 1e-5 of the output's RMS for every nupchan; bytes past the output
-untouched; XX / YY bit-identical to the power mode; the sign of Im(XY*) pinned by Y = -iX; two-part gulps, repeats and
-beside-the-X-engine bit identity; the power mode again after a dual-pol context; the block on device rings.  No wall-clock
-assertions."""
+against the float64 restatement (tests/upchan_pol_ref.py) at 1e-5 of the output's RMS and of every row's own for every
+nupchan; bytes past the output untouched; XX / YY bit-identical to the power mode; the sign of Im(XY*) pinned by Y = -iX;
+two-part gulps, repeats and beside-the-X-engine bit identity; the power mode again after a dual-pol context; the block on
+device rings.  No wall-clock assertions."""
 import json
 import os
 import struct
@@ -20,6 +20,7 @@ from caltech_bifrost_dsp_amd.ring import Ring  # noqa: E402
 from tests.gpu_util import Xgpu, synth_voltages  # noqa: E402
 from tests.pipeline_util import LOG, Sink, Source, run_blocks, source_header  # noqa: E402
 from tests.upchan_pol_ref import upchan_dual_pol  # noqa: E402
+from tests.upchan_local_ref import check_rows, row_ratios  # noqa: E402
 from tests.upchan_ref import upchan_beamform  # noqa: E402
 
 POISON = 0xA5
@@ -72,10 +73,16 @@ def upchan():
     ffi.call("xengUpchanDestroy")
 
 
-def check(got, exp):
+def check(got, exp, rows=True):
+    """Within 1e-5 of the output's RMS, and every row within 1e-5 of its own (tests/upchan_local_ref.py check_rows); rows=False
+    (the full-size point): the worst row's figure is printed, not asserted."""
     rms = np.sqrt(np.mean(np.abs(exp) ** 2))
     err = np.max(np.abs(got.astype(exp.dtype) - exp))
     assert rms > 0 and err <= 1e-5 * rms, "max |err| %.3g = %.3g of RMS %.3g" % (err, err / rms, rms)
+    if rows:
+        check_rows(got, exp)
+    else:
+        print("full size %s: max |err| = %.3g of the RMS, worst row %.3g of its own" % (got.shape, err / rms, np.max(row_ratios(got, exp))))
 
 
 def _parity_points():
@@ -108,7 +115,7 @@ def test_full_size_against_restatement(upchan):
     vin = rng.integers(0, 256, (ntime, nchan, ninput), dtype=np.uint8)
     w = rand_weights(rng, nchan, N, nbeam, ninput)
     u = upchan(ninput, nchan, ntime, N, nbeam, ns)
-    check(u.run(vin, w, version=3), upchan_dual_pol(vin, w, N, nbeam, ns))
+    check(u.run(vin, w, version=3), upchan_dual_pol(vin, w, N, nbeam, ns), rows=False)
 
 
 @pytest.mark.parametrize("nupchan", [8, 16, 32, 64])
