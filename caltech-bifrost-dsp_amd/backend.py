@@ -474,7 +474,62 @@ class HipBackend:
     def pulse_sync(self):
         ffi.call("xengPulseSync")
 
-    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse)
+    # ---- phase-folded profiles of the fine-channel power beams (BeamFold; include/xeng.h "Phase-folded profiles of the
+    # fine-channel power beams"): a context of its own, its kernels on the beamformer's stream
+    def fold_initialize(self, gpu, npair, nfine, nwin, nbin, nprod):
+        return self._lib.xengFoldInitialize(int(gpu), int(npair), int(nfine), int(nwin), int(nbin), int(nprod))
+
+    def fold_set_phase(self, phi0, dphi, ddphi, active, n_ref):
+        """Host arrays of npair entries: uint64 phi0 and dphi, int64 ddphi (turns * 2^64 per window, per window^2), uint8 active;
+        n_ref the window at which the oscillators have m = 0.  Waits for the context's work in flight; clears nothing."""
+        return self._lib.xengFoldSetPhase(phi0.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)), dphi.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)),
+                                          ddphi.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), active.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)),
+                                          int(n_ref))
+
+    def fold_set_rotations(self, rot):
+        """rot: host int32 [npair][nfine], C-contiguous, each in [0, nbin), or None (all zeros).  Waits; acts on dumps only."""
+        return self._lib.xengFoldSetRotations(None if rot is None else rot.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+
+    def fold_set_weights(self, weights):
+        """weights: host float32 [nfine] or None (all ones).  Waits; acts on dumps only."""
+        return self._lib.xengFoldSetWeights(_host_floats(weights))
+
+    def fold_run(self, in_arr, nwin_call):
+        """Enqueue only: f32 [nwin_call][npair][nfine][4] folded into the profile on the device; fold_mark / wait cover it."""
+        return self._enq.xengFoldRun(in_arr.ptr, int(nwin_call))
+
+    def fold_dump(self, out_arr, hits, nfscr, normalise, clear):
+        """out_arr: f32 [npair][nprod][nfine/nfscr][nbin] on the device; hits: host uint32 [npair][nbin] (filled on return) or
+        None.  May wait for the context's work in flight; the dump itself is enqueued (fold_sync / mark cover it)."""
+        return self._lib.xengFoldDump(out_arr.ptr, None if hits is None else hits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), int(nfscr),
+                                      int(bool(normalise)), int(bool(clear)))
+
+    def fold_reset(self):
+        """The count back to 0, hits and profile cleared (one enqueued launch)."""
+        ffi.check("xengFoldReset", self._enq.xengFoldReset())
+
+    def fold_info(self):
+        """(windows taken since the last reset, windows folded since the last clear)"""
+        n, f = ctypes.c_longlong(), ctypes.c_longlong()
+        ffi.call("xengFoldGetInfo", ctypes.byref(n), ctypes.byref(f))
+        return n.value, f.value
+
+    def fold_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the profile hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengFoldCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def fold_mark(self):
+        return self._mark("xengFoldMark")
+
+    def fold_wait(self, ticket):
+        self._wait("xengFoldTicketDone", "xengFoldWait", ticket)
+
+    def fold_sync(self):
+        ffi.call("xengFoldSync")
+
+    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

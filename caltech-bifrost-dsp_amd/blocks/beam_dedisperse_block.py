@@ -30,6 +30,24 @@ from .dedisp import dm_delays
 STOKES = {'I': 1, 'full': 4}
 
 
+def check_power_beam_header(who, ihdr, npair, nchan, nupchan):
+    """The header of the dual-pol fine-channel power beams of UpchanSumBeams / UpchanBeamform(dual_pol=True), as every reader of
+    that ring (BeamDedisperse, BeamFold) checks it; returns acc_len, the samples per window."""
+    if ihdr.get('nchan') != nchan or ihdr.get('nbeam') != npair:
+        raise ValueError("%s: %r channels x %r pairs in the header, %d x %d configured" % (who, ihdr.get('nchan'), ihdr.get('nbeam'), nchan, npair))
+    if ihdr.get('npol') != 2 or ihdr.get('nbit') != 32:
+        raise ValueError("%s: the input is not dual-pol f32 power beams (npol %r, nbit %r)" % (who, ihdr.get('npol'), ihdr.get('nbit')))
+    if ihdr.get('nupchan') != nupchan:
+        raise ValueError("%s: nupchan %r in the header, %d configured" % (who, ihdr.get('nupchan'), nupchan))
+    for k in ('nframe_sum', 'fine_sfreq', 'fine_bw_hz', 'bw_hz'):
+        if not isinstance(ihdr.get(k), (int, float)) or isinstance(ihdr.get(k), bool) or (k != 'fine_sfreq' and not ihdr[k] > 0):
+            raise ValueError("%s: the header's '%s' is %r: not fine-channel power beams summed over windows" % (who, k, ihdr.get(k)))
+    acc_len = ihdr['nframe_sum'] * nupchan
+    if ihdr.get('acc_len', acc_len) != acc_len:
+        raise ValueError("%s: acc_len %r in the header is not nframe_sum x nupchan = %d" % (who, ihdr.get('acc_len'), acc_len))
+    return acc_len
+
+
 class BeamDedisperse(Block):
     STREAM_DEPTH = 4        # spans whose kernels may be in flight behind the one being enqueued (in-repo rings)
 
@@ -88,22 +106,9 @@ class BeamDedisperse(Block):
 
     def _check_header(self, ihdr):
         """The dual-pol fine-channel power beams of UpchanSumBeams / UpchanBeamform(dual_pol=True) only."""
-        who = "BEAM_DEDISPERSE"
-        if ihdr.get('nchan') != self.nchan or ihdr.get('nbeam') != self.npair:
-            raise ValueError("%s: %r channels x %r pairs in the header, %d x %d configured" % (who, ihdr.get('nchan'), ihdr.get('nbeam'), self.nchan,
-                                                                                              self.npair))
-        if ihdr.get('npol') != 2 or ihdr.get('nbit') != 32:
-            raise ValueError("%s: the input is not dual-pol f32 power beams (npol %r, nbit %r)" % (who, ihdr.get('npol'), ihdr.get('nbit')))
-        if ihdr.get('nupchan') != self.nupchan:
-            raise ValueError("%s: nupchan %r in the header, %d configured" % (who, ihdr.get('nupchan'), self.nupchan))
-        for k in ('nframe_sum', 'fine_sfreq', 'fine_bw_hz', 'bw_hz'):
-            if not isinstance(ihdr.get(k), (int, float)) or isinstance(ihdr.get(k), bool) or (k != 'fine_sfreq' and not ihdr[k] > 0):
-                raise ValueError("%s: the header's '%s' is %r: not fine-channel power beams summed over windows" % (who, k, ihdr.get(k)))
+        acc_len = check_power_beam_header("BEAM_DEDISPERSE", ihdr, self.npair, self.nchan, self.nupchan)
         if 'ndm' in ihdr:
-            raise ValueError("%s: the input carries 'ndm': it has been dedispersed already" % who)
-        acc_len = ihdr['nframe_sum'] * self.nupchan
-        if ihdr.get('acc_len', acc_len) != acc_len:
-            raise ValueError("%s: acc_len %r in the header is not nframe_sum x nupchan = %d" % (who, ihdr.get('acc_len'), acc_len))
+            raise ValueError("BEAM_DEDISPERSE: the input carries 'ndm': it has been dedispersed already")
         return acc_len
 
     def delays(self, ihdr, acc_len):

@@ -88,7 +88,8 @@ struct TicketRing {
     static int query(hipEvent_t e, int* done);                      // never blocks
     void destroy();                                                 // after the stream has been synchronised and its clock forgotten
 };
-// What every engine beside the beamformer on its stream has (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp): each
+// What every engine beside the beamformer on its stream has (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp,
+// Pulse, Fold): each
 // derives its process-global context from this and keeps a mutex of its own.  Its kernels run on STREAM_BEAM and tick that
 // clock, so that rings declared 'beam' and their span stamps cover them unchanged.
 struct BeamStreamContext {

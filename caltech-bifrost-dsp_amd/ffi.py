@@ -115,6 +115,12 @@ SYMBOLS = {
     "xengPulseGetBaseline": [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)],
     "xengPulseCheckGuards": [_pi], "xengPulseMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengPulseWait": [ctypes.c_ulonglong],
     "xengPulseTicketDone": [ctypes.c_ulonglong, _pi], "xengPulseSync": [], "xengPulseDestroy": [],
+    "xengFoldInitialize": [_i, _i, _i, _i, _i, _i],
+    "xengFoldSetPhase": [ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong), _pll, ctypes.POINTER(ctypes.c_ubyte), _ll],
+    "xengFoldSetRotations": [_pi], "xengFoldSetWeights": [ctypes.POINTER(ctypes.c_float)], "xengFoldRun": [_vp, _i],
+    "xengFoldDump": [_vp, ctypes.POINTER(ctypes.c_uint), _i, _i, _i], "xengFoldReset": [], "xengFoldGetInfo": [_pll, _pll],
+    "xengFoldCheckGuards": [_pi], "xengFoldMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengFoldWait": [ctypes.c_ulonglong],
+    "xengFoldTicketDone": [ctypes.c_ulonglong, _pi], "xengFoldSync": [], "xengFoldDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -164,6 +170,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengUpchanSpectraMark", "xengUpchanSpectraTicketDone",
                 "xengDedispRun", "xengDedispReset", "xengDedispMark", "xengDedispTicketDone",
                 "xengPulseRun", "xengPulseReset", "xengPulseMark", "xengPulseTicketDone",
+                "xengFoldRun", "xengFoldReset", "xengFoldMark", "xengFoldTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

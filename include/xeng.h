@@ -733,6 +733,76 @@ int xengPulseTicketDone(unsigned long long ticket, int *done);
 int xengPulseSync(void);
 int xengPulseDestroy(void);
 
+/* ---------------------------------------------------------------- Phase-folded profiles of the fine-channel power beams
+ * BeamFold (no reference counterpart: the reference ships its power beams to external pulsar backends): every window of every
+ * pair, fine channel and product is added into the bin of a pulse profile that an integer phase oscillator names; a dump rotates
+ * the channels against each other (dispersion, inside a fold, is a rotation of each channel's profile), weights and sums them.
+ * A context of its own, independent of all others, whose kernels run on the beamformer's stream -- rings declared 'beam' cover
+ * them, and xengBeamformSync waits for them too.  One kernel per call (csrc/fold_kernels.h).  The library knows nothing of
+ * pulsars, of time or of the dispersion constant: the caller supplies oscillators and rotations as integers.
+ *   in       f32[nwin_call][npair][nfine][4] = [XX, YY, Re XY*, Im XY*], as xengDedispRun takes it; 16-byte aligned; never
+ *            written.  1 <= nwin_call <= nwin.
+ *   products nprod = 1 folds I = fl(XX + YY); nprod = 4 folds the four words, each by itself.
+ *   phase    n counts windows since the last reset (xengFoldReset, Initialize).  xengFoldSetPhase(phi0, dphi, ddphi, active, n_ref)
+ *            takes host arrays of npair entries (uint64 phi0, uint64 dphi, int64 ddphi, uint8 active) and 0 <= n_ref <= the
+ *            windows taken so far.  With m = n - n_ref the phase of pair p at window n, in turns * 2^64 and in wrapping 64-bit
+ *            arithmetic, is
+ *              Phi_p(n) = phi0 + dphi*m + ddphi*(m(m-1)/2)          (m(m-1)/2 formed exactly; Run refuses a call whose last m
+ *                                                                     would reach 2^31)
+ *              bin_p(n) = ((Phi_p(n) >> 32) * nbin) >> 32
+ *            A pair with active = 0 is left out.  A new SetPhase acts from the next Run on and clears nothing: a caller
+ *            re-tunes at a sub-integration boundary with n_ref = the current count.
+ *   state    prof[p][b][q][k], f32[npair][nbin][nfine][nprod], +0 after Initialize, Reset or a clearing dump.  xengFoldRun, for
+ *            every window of the call in ascending n:   prof[p][bin_p(n)][q][k] = fl(prof[p][bin_p(n)][q][k] + x[n][p][q][k]).
+ *            Each word is ONE strictly sequential chain of fp32 adds over the windows that fall in its bin: no atomics, no
+ *            partial sums added later.  So the result does not depend on nwin_call, on how a run is split over calls, or on
+ *            what else runs on the GPU; a NaN in one channel never reaches another channel; the result is exact on integer
+ *            data below 2^24; and any float32 restatement that adds in window order reproduces it bit for bit.
+ *   hits     hits[p][b]: the windows folded into bin b of pair p since the last clear -- exact integers from the phase model,
+ *            kept on the host side of the library (nothing on the device is needed to count them).
+ *   dump     xengFoldDump(out_dev, hits_host, nfscr, normalise, clear): out is f32[npair][nprod][nfine/nfscr][nbin], the bin the
+ *            fastest axis, 16-byte aligned; nothing past it is written.  nfscr divides nfine (1: the full cube; nfine: the
+ *            dedispersed profile).  With rotations rot[p][q] in [0, nbin) (xengFoldSetRotations) and weights w[q]
+ *            (xengFoldSetWeights):
+ *              out[p][k][g][b] = sum over q = g*nfscr .. (g+1)*nfscr - 1, ascending, of w[q] * prof[p][(b + rot[p][q]) mod nbin][q][k]
+ *            one chain from +0 of fmaf(w[q], x, sum).  A channel of weight exactly 0 is left out (a select, not a multiply:
+ *            a NaN there never arrives).  normalise = 1 divides each term's prof word by (float)hits[p][(b + rot[p][q]) mod nbin]
+ *            (correctly rounded fp32 division) before the fmaf; a bin with 0 hits then contributes +0.  An inactive pair's
+ *            plane is +0.  hits_host, uint32[npair][nbin] on the host, unrotated, may be NULL; it is filled on return.
+ *            clear = 1 zeroes the profile and the hits as part of the same launch: each profile word is read by exactly one
+ *            thread, which then writes it.  A dump may wait for the context's work in flight the way the setters do (a
+ *            normalising one does, to upload the hits): it runs once per sub-integration.
+ * Rejected at Initialize, before any device is touched: a non-positive size, nprod outside {1, 4}, nbin > 65536, npair > 65535,
+ * a profile above XENG_FOLD_MAX_PROFILE_BYTES (the live shape, 16 x 3072 x 4 at 1024 bins, is 805 MB).  Rejected by the setters,
+ * Run and Dump without a launch: a NULL (Run, Dump's output, SetPhase) or misaligned pointer, nwin_call outside 1..nwin, a
+ * rotation outside [0, nbin), a non-finite weight, nfscr not dividing nfine, n_ref out of range.  Run before SetPhase, Dump
+ * before SetRotations and every call without a context: XENG_STATUS_INVALID_STATE. */
+#define XENG_FOLD_MAX_PROFILE_BYTES (1LL << 32)
+int xengFoldInitialize(int gpu, int npair, int nfine, int nwin, int nbin, int nprod);
+/* The three setters wait for the context's work in flight (as xengDedispSetWeights does) and upload from the host; none of them
+ * clears anything.  SetRotations: int32[npair][nfine], NULL means all zeros.  SetWeights: f32[nfine], finite; NULL or never
+ * set means all ones.  Rotations and weights act on dumps only. */
+int xengFoldSetPhase(const unsigned long long *phi0, const unsigned long long *dphi, const long long *ddphi, const unsigned char *active,
+                     long long n_ref);
+int xengFoldSetRotations(const int *rot);
+int xengFoldSetWeights(const float *weights);
+/* enqueue only: nwin_call windows folded into the profile */
+int xengFoldRun(const void *in_dev, int nwin_call);
+int xengFoldDump(void *out_dev, unsigned int *hits_host, int nfscr, int normalise, int clear);
+/* enqueue only: the count back to 0, the hits cleared, the profile cleared by one clearing launch on the stream.  The
+ * oscillators stay and their reference moves with the count: the next window has m = 0. */
+int xengFoldReset(void);
+/* windows taken since the last reset, and windows folded since the last clear (Reset, a clearing dump, Initialize) */
+int xengFoldGetInfo(long long *nwindows_since_reset, long long *nwindows_folded);
+/* The profile is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengFoldCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengFoldMark(unsigned long long *ticket);
+int xengFoldWait(unsigned long long ticket);
+int xengFoldTicketDone(unsigned long long ticket, int *done);
+int xengFoldSync(void);
+int xengFoldDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
