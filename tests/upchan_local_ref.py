@@ -191,9 +191,10 @@ def _bitrev(N):
     return np.array([int(format(n, '0%db' % bits)[::-1], 2) for n in range(N)])
 
 
-def emu_fft(yr, yi):
+def emu_fft(yr, yi, exact_units=False):
     """uc_fft on float32 [...][N] in natural order, every operation rounded to float32 (no fma), the twiddles rounded from
-    float64; returns the fine-channel order j = (k + N/2) mod N."""
+    float64; returns the fine-channel order j = (k + N/2) mod N.  exact_units: ucc_fft, which applies the twiddles 1 and -i
+    as a copy and a swap instead of reading them from the table."""
     N = yr.shape[-1]
     rev = _bitrev(N)
     vr, vi = np.ascontiguousarray(yr[..., rev]), np.ascontiguousarray(yi[..., rev])
@@ -201,10 +202,16 @@ def emu_fft(yr, yi):
     while ln <= N:
         half = ln // 2
         for k in range(half):
-            tr, ti = _TW[0][k * (64 // ln)], _TW[1][k * (64 // ln)]
+            k64 = k * (64 // ln)
+            tr, ti = _TW[0][k64], _TW[1][k64]
             a, b = slice(k, None, ln), slice(k + half, None, ln)
-            br = vr[..., b] * tr - vi[..., b] * ti
-            bi = vr[..., b] * ti + vi[..., b] * tr
+            if exact_units and k64 == 0:
+                br, bi = vr[..., b].copy(), vi[..., b].copy()
+            elif exact_units and k64 == 16:
+                br, bi = vi[..., b].copy(), -vr[..., b]
+            else:
+                br = vr[..., b] * tr - vi[..., b] * ti
+                bi = vr[..., b] * ti + vi[..., b] * tr
             ar, ai = vr[..., a].copy(), vi[..., a].copy()
             vr[..., a], vi[..., a] = ar + br, ai + bi
             vr[..., b], vi[..., b] = ar - br, ai - bi
