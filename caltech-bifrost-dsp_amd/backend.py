@@ -529,7 +529,64 @@ class HipBackend:
     def fold_sync(self):
         ffi.call("xengFoldSync")
 
-    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold)
+    # ---- FFT periodicity search of the dedispersed beams (BeamPeriodSearch; include/xeng.h "FFT periodicity search of the
+    # dedispersed beams"): a context of its own, its kernels on the beamformer's stream
+    def period_initialize(self, gpu, npair, ndm, nwin, nprod, nt, nstack, nlevel, nwhite, kmin):
+        return self._lib.xengPeriodInitialize(int(gpu), int(npair), int(ndm), int(nwin), int(nprod), int(nt), int(nstack), int(nlevel), int(nwhite),
+                                              int(kmin))
+
+    def period_set_mask(self, keep):
+        """keep: host uint8 [nt/2], 0 = zapped, or None (all kept).  Waits for the context's work in flight; holds from the next
+        segment to complete."""
+        return self._lib.xengPeriodSetMask(None if keep is None else keep.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
+
+    def period_run(self, in_arr, nwin_call, out_arr):
+        """Enqueue only: f32 [nwin_call][npair][ndm][nprod] in; (status, completed).  out_arr, [npair][ndm][nlevel] records
+        {f32 H, i32 k}, is written only when the call completes a stack (completed = 1) and may be None on every other call;
+        period_mark / wait cover it."""
+        done = ctypes.c_int(0)
+        rv = self._enq.xengPeriodRun(in_arr.ptr, int(nwin_call), None if out_arr is None else out_arr.ptr, ctypes.byref(done))
+        return rv, done.value
+
+    def period_reset(self):
+        """The next input counts as window 0 of a new stack (host state only)."""
+        ffi.check("xengPeriodReset", self._enq.xengPeriodReset())
+
+    def period_info(self):
+        """(windows taken since the last reset, complete segments of the stack in progress, stacks completed since the reset)"""
+        n, s, k = ctypes.c_longlong(), ctypes.c_int(), ctypes.c_longlong()
+        ffi.call("xengPeriodGetInfo", ctypes.byref(n), ctypes.byref(s), ctypes.byref(k))
+        return n.value, s.value, k.value
+
+    def period_spectrum(self, npair, ndm, nt):
+        """Waits for the context's work; (A, nseg): the stack as it stands, float32 [npair][ndm][nt/2], and the segments in it."""
+        import numpy as np
+        A, nseg = np.empty((npair, ndm, nt // 2), np.float32), ctypes.c_int()
+        ffi.call("xengPeriodGetSpectrum", A.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(nseg))
+        return A, nseg.value
+
+    def period_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengPeriodCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def period_mark(self):
+        return self._mark("xengPeriodMark")
+
+    def period_wait(self, ticket):
+        self._wait("xengPeriodTicketDone", "xengPeriodWait", ticket)
+
+    def period_ticket_done(self, ticket):
+        """Never blocks: whether everything enqueued before the ticket has completed."""
+        d = ctypes.c_int()
+        ffi.check("xengPeriodTicketDone", self._enq.xengPeriodTicketDone(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
+        return bool(d.value)
+
+    def period_sync(self):
+        ffi.call("xengPeriodSync")
+
+    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold, Period)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

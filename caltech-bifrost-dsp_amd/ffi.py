@@ -121,6 +121,11 @@ SYMBOLS = {
     "xengFoldDump": [_vp, ctypes.POINTER(ctypes.c_uint), _i, _i, _i], "xengFoldReset": [], "xengFoldGetInfo": [_pll, _pll],
     "xengFoldCheckGuards": [_pi], "xengFoldMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengFoldWait": [ctypes.c_ulonglong],
     "xengFoldTicketDone": [ctypes.c_ulonglong, _pi], "xengFoldSync": [], "xengFoldDestroy": [],
+    "xengPeriodInitialize": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i], "xengPeriodSetMask": [ctypes.POINTER(ctypes.c_ubyte)],
+    "xengPeriodRun": [_vp, _i, _vp, _pi], "xengPeriodReset": [], "xengPeriodGetInfo": [_pll, _pi, _pll],
+    "xengPeriodGetSpectrum": [ctypes.POINTER(ctypes.c_float), _pi], "xengPeriodCheckGuards": [_pi],
+    "xengPeriodMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengPeriodWait": [ctypes.c_ulonglong],
+    "xengPeriodTicketDone": [ctypes.c_ulonglong, _pi], "xengPeriodSync": [], "xengPeriodDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -171,6 +176,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengDedispRun", "xengDedispReset", "xengDedispMark", "xengDedispTicketDone",
                 "xengPulseRun", "xengPulseReset", "xengPulseMark", "xengPulseTicketDone",
                 "xengFoldRun", "xengFoldReset", "xengFoldMark", "xengFoldTicketDone",
+                "xengPeriodRun", "xengPeriodReset", "xengPeriodMark", "xengPeriodTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

@@ -803,6 +803,78 @@ int xengFoldTicketDone(unsigned long long ticket, int *done);
 int xengFoldSync(void);
 int xengFoldDestroy(void);
 
+/* ---------------------------------------------------------------- FFT periodicity search of the dedispersed beams
+ * BeamPeriodSearch (no reference counterpart: the reference has no detection stage): per series a long real FFT per segment of
+ * NT windows, the power spectrum whitened by block means, nstack such spectra stacked incoherently, harmonic sums of the stack and
+ * one peak record per series and harmonic level.  A context of its own, independent of all others, whose kernels run on the
+ * beamformer's stream -- rings declared 'beam' cover them, and xengBeamformSync waits for them too.  An ingest kernel per call
+ * and a spectrum kernel per completed segment (csrc/period_kernels.h).
+ *   in       f32[nwin_call][npair][ndm][nprod], the output span of xengDedispRun unchanged; 16-byte aligned; never written.
+ *            1 <= nwin_call <= nwin <= NT, so that a call completes at most one segment.  A series is one (p, d), nser =
+ *            npair*ndm.  nprod = 1: z[n] = in[n][p][d][0]; nprod = 4: z[n] = fl(in[n][p][d][0] + in[n][p][d][1]), I = XX + YY.
+ *            n counts windows since the last reset (xengPeriodReset, Initialize).
+ *   sizes    NT = nt, the segment length: a power of two, 2^8 <= NT <= 2^14 (the FFT's NT/2 complex points are at most 64 KiB of
+ *            LDS).  nstack >= 1 segments per stack.  nlevel = 1..5 harmonic levels, h = 1, 2, 4, 8, 16.  nwhite = B, the
+ *            whitening block: a power of two, 8 <= B <= NT/2.  kmin, the lowest fundamental bin: 1 <= kmin < NT/32.
+ *   segment  Segment s of a stack is the NT windows [(s0 + s)*NT, (s0 + s + 1)*NT).  The call that brings its last window
+ *            transforms it, per series:
+ *              1. x = z - mean(z).  The summation order is the library's: everything up to A is held to a tolerance.
+ *              2. the NT-point real DFT  X[k] = sum_n x[n] * exp(-2 pi i n k / NT).
+ *              3. P[k] = |X[k]|^2 for 1 <= k < NT/2.  DC and Nyquist are dropped.
+ *              4. whitening.  Block b is the bins [b*B, (b+1)*B).  mu_b is the mean of P over the block's bins with k >= 1 and
+ *                 keep[k] != 0.  If the block has no such bin, or mu_b is not finite and positive, S[k] = 1.0f for the whole
+ *                 block (a dead series, all zeros, comes out as pure expectation); otherwise S[k] = P[k] / mu_b.
+ *              5. the mask: a zapped bin (keep[k] = 0) gets S[k] = 1.0f; S[0] = +0.
+ *              6. a segment whose mean(z) is not finite -- it held a NaN or an Inf sample -- has no spectrum: S[k] = NaN for
+ *                 every k >= 1, zapped bins included, so that the series stays NaN in A to the end of its stack.
+ *   stack    A[k] = ((S_1 + S_2) + S_3) + ... in segment order, fp32, one owner per word and no atomics.  The first segment of
+ *            a stack STORES, so nothing is ever cleared.  A is f32[npair][ndm][NT/2] on the device.
+ *   sums     When segment nstack of a stack completes: for h = 2^l, l < nlevel, and h*kmin <= k < NT/2
+ *              H_h[k] = sum_{j=1..h} A[(j*k + h/2) div h]
+ *            j ascending, plain fp32 adds starting from A of j = 1, no contraction.  k indexes the TOP harmonic: the
+ *            fundamental is k/h bins, k / (h * NT * tsamp) Hz.  The index arithmetic is integer: which words are summed is
+ *            exact, and any float32 restatement that adds in this order reproduces H bit for bit from the same A.
+ *   out      [npair][ndm][nlevel] records of two 32-bit words {f32 H, i32 k}, each one 8-byte store, out_dev 16-byte aligned;
+ *            nothing past npair*ndm*nlevel*8 bytes is written.  The record is the largest H_h[k], among equal sums the smallest
+ *            k.  A NaN is never a maximum; if nothing qualifies the record is {+0.0f, -1}.  A series that held a non-finite
+ *            sample anywhere in the stack therefore reads {+0.0f, -1} at every level, and disturbs no neighbour.
+ *   state    between two guard bands of 64 KiB: the time buffer f32[nser][NT] (time the fastest axis, window n at slot
+ *            n mod NT), A, the mask with the counts of its blocks, and the twiddle tables exp(-2 pi i k / NT) (float64 on the
+ *            host, rounded once).  xengPeriodReset moves only the host's counts: the partial segment and the partial stack are
+ *            dropped by index, and nothing is cleared.
+ * A and the records are a fixed function of the series and the mask: bit-identical however a run is split over calls, whatever
+ * nwin_call, after a Reset as in a fresh context, and whatever else runs on the GPU.  The sums are exact on integer-valued A
+ * below 2^24.
+ * Rejected at Initialize, before any device is touched: a non-positive size, nprod outside {1, 4}, nt not a power of two in
+ * 2^8..2^14, nstack < 1, nlevel outside 1..5, nwhite not a power of two in 8..nt/2, kmin outside 1..nt/32 - 1, nwin > nt,
+ * npair*ndm > 2^24, a state above XENG_PERIOD_MAX_STATE_BYTES.  Rejected by Run without a launch: a NULL input or result, a
+ * misaligned pointer, nwin_call outside 1..nwin, a NULL output on the call that completes a stack.  Every call without a context,
+ * and GetSpectrum before a segment has completed: XENG_STATUS_INVALID_STATE. */
+#define XENG_PERIOD_MAX_STATE_BYTES (1LL << 32)
+int xengPeriodInitialize(int gpu, int npair, int ndm, int nwin, int nprod, int nt, int nstack, int nlevel, int nwhite, int kmin);
+/* keep: u8[nt/2] on the host, 0 = zapped; NULL: all kept (as after Initialize).  Waits for the context's work in flight (as
+ * xengDedispSetWeights does); holds from the next segment to complete. */
+int xengPeriodSetMask(const unsigned char *keep);
+/* enqueue only.  out_dev is written only by a call that completes a stack (*completed = 1); the host's window count decides that
+ * before anything is enqueued.  Such a call with out_dev NULL is INVALID_ARGUMENT and enqueues nothing; on every other call
+ * out_dev may be NULL and is not touched. */
+int xengPeriodRun(const void *in_dev, int nwin_call, void *out_dev, int *completed);
+/* host state only, nothing is launched and nothing cleared: the next input counts as window 0 of segment 0 of a new stack */
+int xengPeriodReset(void);
+/* windows taken since the last reset, complete segments of the stack in progress, stacks completed since the last reset */
+int xengPeriodGetInfo(long long *nwindows_since_reset, int *nseg_in_stack, long long *nstacks_complete);
+/* waits for the context's work in flight; the stack as it stands into host f32[npair][ndm][nt/2] and the segments it holds
+ * (nstack after the call that completed a stack): the diagnostic plot, and what the exact test of the records reads */
+int xengPeriodGetSpectrum(float *A_host, int *nseg);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengPeriodCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengPeriodMark(unsigned long long *ticket);
+int xengPeriodWait(unsigned long long ticket);
+int xengPeriodTicketDone(unsigned long long ticket, int *done);
+int xengPeriodSync(void);
+int xengPeriodDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
