@@ -586,7 +586,53 @@ class HipBackend:
     def period_sync(self):
         ffi.call("xengPeriodSync")
 
-    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold, Period)
+    # ---- coherent dedispersion of the voltage beams (BeamCoherentDedisperse; include/xeng.h "Coherent dedispersion of the voltage
+    # beams"): a context of its own, its kernels on the beamformer's stream
+    def cdedisp_initialize(self, gpu, nchan, nbeam, ntime, pair0, npair, nfft, overlap):
+        return self._lib.xengCdedispInitialize(int(gpu), int(nchan), int(nbeam), int(ntime), int(pair0), int(npair), int(nfft), int(overlap))
+
+    def cdedisp_set_chirp(self, table):
+        """table: host complex64 [npair][nchan][nfft], C-contiguous, natural DFT order, 1/nfft included.  Waits for the context's
+        work in flight; holds from the next block to complete."""
+        import numpy as np
+        if not (isinstance(table, np.ndarray) and table.dtype == np.complex64 and table.flags['C_CONTIGUOUS']):
+            raise TypeError("cdedisp_set_chirp: the table must be a C-contiguous complex64 array")
+        return self._lib.xengCdedispSetChirp(table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+
+    def cdedisp_run(self, in_arr, out_arr):
+        """Enqueue only: cf32 [nchan][nbeam][ntime] in; (status, nblocks).  out_arr gets cf32 [nblocks][nchan][2 npair][L] and may be
+        None on a call that completes no block; cdedisp_mark / wait cover it."""
+        n = ctypes.c_int(0)
+        rv = self._enq.xengCdedispRun(in_arr.ptr, None if out_arr is None else out_arr.ptr, ctypes.byref(n))
+        return rv, n.value
+
+    def cdedisp_reset(self):
+        """The next input sample counts as sample 0 (host state only)."""
+        ffi.check("xengCdedispReset", self._enq.xengCdedispReset())
+
+    def cdedisp_info(self):
+        """(the step L, the most blocks a call completes, samples taken since the last reset, blocks completed since the reset)"""
+        s, m, n, b = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong()
+        ffi.call("xengCdedispGetInfo", ctypes.byref(s), ctypes.byref(m), ctypes.byref(n), ctypes.byref(b))
+        return s.value, m.value, n.value, b.value
+
+    def cdedisp_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengCdedispCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def cdedisp_mark(self):
+        return self._mark("xengCdedispMark")
+
+    def cdedisp_wait(self, ticket):
+        self._wait("xengCdedispTicketDone", "xengCdedispWait", ticket)
+
+    def cdedisp_sync(self):
+        ffi.call("xengCdedispSync")
+
+    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold, Period,
+    # Cdedisp)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

@@ -23,8 +23,10 @@ from .pulse_search import pulse_candidates
 from .beam_period_search_block import BeamPeriodSearch
 from .period_search import period_candidates, period_pfa
 from .beam_fold_block import BeamFold
-from .fold import fold_phase, fold_rotations, profile_snr
+from .fold import fold_phase, fold_rotations, fold_rotations_coherent, profile_snr
+from .beam_coherent_dedisperse_block import BeamCoherentDedisperse
+from .coherent_dedisp import cdedisp_plan, chirp_table, smear_samples
 from .spectral_kurtosis import incoherent_beam, sk_flags, sk_limits, spectral_kurtosis
 
-__all__ = ["Block", "Corr", "CorrAcc", "Beamform", "BeamformSumBeams", "Copy", "CorrSubsel", "CorrOutputFull", "Snap2Ingest", "BeamformOutput", "CorrOutputPart", "BeamformVlbiOutput", "UpchanBeamform", "TbfSource", "UpchanCorr", "UpchanSumBeams", "UpchanSpectra", "BeamDedisperse", "dm_delays", "BeamPulseSearch", "pulse_candidates", "BeamPeriodSearch", "period_candidates", "period_pfa", "BeamFold", "fold_phase", "fold_rotations", "profile_snr", "spectral_kurtosis", "sk_limits", "sk_flags", "incoherent_beam", "regtile_index", "tri_index",
+__all__ = ["Block", "Corr", "CorrAcc", "Beamform", "BeamformSumBeams", "Copy", "CorrSubsel", "CorrOutputFull", "Snap2Ingest", "BeamformOutput", "CorrOutputPart", "BeamformVlbiOutput", "UpchanBeamform", "TbfSource", "UpchanCorr", "UpchanSumBeams", "UpchanSpectra", "BeamDedisperse", "dm_delays", "BeamPulseSearch", "pulse_candidates", "BeamPeriodSearch", "period_candidates", "period_pfa", "BeamFold", "fold_phase", "fold_rotations", "fold_rotations_coherent", "profile_snr", "BeamCoherentDedisperse", "chirp_table", "smear_samples", "cdedisp_plan", "spectral_kurtosis", "sk_limits", "sk_flags", "incoherent_beam", "regtile_index", "tri_index",
            "COMMAND_OK", "COMMAND_NOT_RECOGNIZED", "COMMAND_WRONG_TYPE", "COMMAND_INVALID"]

@@ -36,7 +36,7 @@ from ..ndarray import XArray, copy_array
 from ..proclog import cpu_affinity
 from .beam_dedisperse_block import STOKES, check_power_beam_header
 from .block_base import Block, InFlight, declare_streams, gulp_time, spans_outlive_release
-from .fold import fold_phase, fold_rotations
+from .fold import fold_phase, fold_rotations, fold_rotations_coherent
 
 WHO = "BEAM_FOLD"
 
@@ -123,12 +123,25 @@ class BeamFold(Block):
 
     # ---- what the library is told, from the header and the pulsar list
     def rotations(self, ihdr):
-        """int32 [npair][nfine]: fold_rotations of each pair's DM and f0 at the header's fine-channel centres (0 for a pair left out)."""
+        """int32 [npair][nfine]: fold_rotations of each pair's DM and f0 at the header's fine-channel centres (0 for a pair left out).
+        Where the header carries `cdedisp_dm` -- the beams have passed BeamCoherentDedisperse, which has aligned the fine channels of
+        a coarse channel to its centre already -- fold_rotations_coherent with that pair's coherent DM instead: pair p of this
+        block is entry pair0 + p of the list, pair0 being what the upchanneliser behind that block selected."""
         freqs = ihdr['fine_sfreq'] + ihdr['fine_bw_hz'] * np.arange(self.nfine)
+        dm_coh = ihdr.get('cdedisp_dm')
+        if dm_coh is not None:
+            first = int(ihdr.get('pair0', 0))
+            if not isinstance(dm_coh, list) or first < 0 or first + self.npair > len(dm_coh):
+                raise ValueError("%s: the header's 'cdedisp_dm' %r does not cover the pairs [%d, %d)" % (WHO, dm_coh, first, first + self.npair))
+            coarse = ihdr['fine_sfreq'] + ihdr['fine_bw_hz'] * self.nupchan * (np.arange(self.nfine) // self.nupchan + 0.5)
         rot = np.zeros((self.npair, self.nfine), np.int32)
         for p, e in enumerate(self.pulsars):
-            if e is not None:
+            if e is None:
+                continue
+            if dm_coh is None:
                 rot[p] = fold_rotations(freqs, e['dm'], e['f0'], self.nbin)
+            else:
+                rot[p] = fold_rotations_coherent(freqs, coarse, e['dm'], float(dm_coh[first + p]), e['f0'], self.nbin)
         return rot
 
     def phase(self, ihdr, acc_len, sample):

@@ -55,6 +55,28 @@ def fold_rotations(freqs_hz, dm, f_spin, nbin, f_ref_hz=None):
     return np.mod(r, int(nbin)).astype(np.int32)
 
 
+def fold_rotations_coherent(freqs_hz, coarse_freqs_hz, dm, dm_coh, f_spin, nbin, f_ref_hz=None):
+    """fold_rotations behind BeamCoherentDedisperse, which has aligned the fine channels of a coarse channel to its centre at the DM
+    dm_coh already: int32 [nfine],
+        rint(KDM * (dm * (f_c**-2 - f_ref**-2) + (dm - dm_coh) * (f**-2 - f_c**-2)) * f_spin * nbin) mod nbin
+    in float64, f the fine channel (freqs_hz), f_c the centre of its coarse channel (coarse_freqs_hz, one per fine channel), f_ref
+    the highest fine channel by default.  dm_coh = dm leaves the delays between the coarse channels only; dm_coh = 0 is
+    fold_rotations to within the rounding of one sum."""
+    f = np.asarray(freqs_hz, np.float64).reshape(-1) * 1e-6
+    fc = np.asarray(coarse_freqs_hz, np.float64).reshape(-1) * 1e-6
+    if f.size == 0 or fc.shape != f.shape or not (np.all(np.isfinite(f)) and np.all(f > 0) and np.all(np.isfinite(fc)) and np.all(fc > 0)):
+        raise ValueError("fold_rotations_coherent: frequencies must be positive and finite, one coarse centre per fine channel")
+    if not (np.isfinite(dm) and np.isfinite(dm_coh) and np.isfinite(f_spin) and f_spin > 0):
+        raise ValueError("fold_rotations_coherent: DMs %r, %r must be finite and the spin frequency %r positive" % (dm, dm_coh, f_spin))
+    if not (isinstance(nbin, (int, np.integer)) and nbin > 0):
+        raise ValueError("fold_rotations_coherent: nbin %r is not a positive integer" % (nbin,))
+    f_ref = f.max() if f_ref_hz is None else float(f_ref_hz) * 1e-6
+    if not (np.isfinite(f_ref) and f_ref > 0):
+        raise ValueError("fold_rotations_coherent: reference frequency %r is not positive" % (f_ref_hz,))
+    r = np.rint((KDM * float(dm) * (fc ** -2 - f_ref ** -2) + KDM * (float(dm) - float(dm_coh)) * (f ** -2 - fc ** -2)) * float(f_spin) * int(nbin))
+    return np.mod(r, int(nbin)).astype(np.int32)
+
+
 def profile_snr(profile):
     """Of a profile [nbin]: dict(mean, sigma, peak, bin, snr).  mean and sigma (population) come from the quietest half of the
     bins: the window of nbin // 2 consecutive bins, cyclically, with the smallest sum (the first such window).  peak is the

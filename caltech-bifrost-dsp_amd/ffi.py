@@ -126,6 +126,10 @@ SYMBOLS = {
     "xengPeriodGetSpectrum": [ctypes.POINTER(ctypes.c_float), _pi], "xengPeriodCheckGuards": [_pi],
     "xengPeriodMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengPeriodWait": [ctypes.c_ulonglong],
     "xengPeriodTicketDone": [ctypes.c_ulonglong, _pi], "xengPeriodSync": [], "xengPeriodDestroy": [],
+    "xengCdedispInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdedispSetChirp": [ctypes.POINTER(ctypes.c_float)],
+    "xengCdedispRun": [_vp, _vp, _pi], "xengCdedispReset": [], "xengCdedispGetInfo": [_pi, _pi, _pll, _pll], "xengCdedispCheckGuards": [_pi],
+    "xengCdedispMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCdedispWait": [ctypes.c_ulonglong],
+    "xengCdedispTicketDone": [ctypes.c_ulonglong, _pi], "xengCdedispSync": [], "xengCdedispDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -177,6 +181,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengPulseRun", "xengPulseReset", "xengPulseMark", "xengPulseTicketDone",
                 "xengFoldRun", "xengFoldReset", "xengFoldMark", "xengFoldTicketDone",
                 "xengPeriodRun", "xengPeriodReset", "xengPeriodMark", "xengPeriodTicketDone",
+                "xengCdedispRun", "xengCdedispReset", "xengCdedispMark", "xengCdedispTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

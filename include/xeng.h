@@ -875,6 +875,59 @@ int xengPeriodTicketDone(unsigned long long ticket, int *done);
 int xengPeriodSync(void);
 int xengPeriodDestroy(void);
 
+/* ---------------------------------------------------------------- Coherent dedispersion of the voltage beams
+ * BeamCoherentDedisperse (no reference counterpart): every (coarse channel, selected beam) row of the voltage beams is filtered by
+ * overlap-save with a table given in the frequency domain, and comes out in the format it came in.  The library knows nothing of
+ * the dispersion constant: blocks/coherent_dedisp.py builds the table.  A context of its own, independent of all others, whose
+ * kernels run on the beamformer's stream -- rings declared 'beam' cover them, and xengBeamformSync waits for them too.  An ingest
+ * kernel per call (one more where a call straddles a block boundary) and a filter kernel per completed block
+ * (csrc/cdedisp_kernels.h).
+ *   in       cf32[nchan][nbeam][ntime], the output of xengBeamformRun unchanged; 16-byte aligned; never written.  ntime is fixed
+ *            per context.  The selected beams are 2*pair0 .. 2*(pair0 + npair) - 1; a row is one (c, selected beam b),
+ *            nrow = nchan * 2*npair.  Samples are counted from the last reset (xengCdedispReset, Initialize).
+ *   sizes    NFFT = nfft, a power of two, 2^8 <= NFFT <= 2^13 (64 KiB of LDS at 2^13).  M = overlap: even, 0 <= M <= NFFT/2.
+ *            L = NFFT - M, the step.
+ *   block    Block j covers the input samples [j*L, j*L + NFFT) and runs in the call that brings its last sample.  Per row:
+ *              X[k] = sum_n x[n] * exp(-2 pi i k n / NFFT),  Y[k] = X[k] * T[p][c][k],  y[n] = sum_k Y[k] * exp(+2 pi i k n / NFFT)
+ *            with p = b div 2 (both beams of a pair share a filter) and nothing else scaled: the table carries the 1/NFFT.  The
+ *            block's output is y[M/2 .. M/2 + L): output sample i of the stream is input sample i + M/2, and the blocks tile the
+ *            time axis without a gap.  fp32, held to a tolerance; no atomics, one owner per word.
+ *   out      cf32[nblk][nchan][2*npair][L], one unit per block the call completes, 16-byte aligned; nothing past nblk units is
+ *            written.  A call completes at most ceil(ntime / L) blocks (xengCdedispGetInfo).
+ *   table    cf32[npair][nchan][NFFT] on the host in natural DFT order: bin k is the offset k*D/NFFT from the channel's centre for
+ *            k < NFFT/2 and (k - NFFT)*D/NFFT above, D the channel width.  After Initialize it is 1/NFFT everywhere: a pure latency
+ *            of M/2 samples.
+ *   state    between two guard bands of 64 KiB: the time buffer cf32[nrow][NFFT], the table (in the kernel's order) and the
+ *            twiddles exp(-2 pi i k / NFFT) (float64 on the host, rounded once).  xengCdedispReset moves only the host's counts.
+ * The output is a fixed function of the sample stream and the table: bit-identical whatever ntime, however the stream falls on
+ * calls, after a Reset as in a fresh context, and whatever else runs on the GPU.  A non-finite input sample makes the blocks of
+ * its own row that contain it non-finite and changes no other word.
+ * Rejected at Initialize, before any device is touched: a non-positive size, pairs outside [0, nbeam/2), nfft not a power of two
+ * in 2^8..2^13, overlap odd, negative or above nfft/2, nchan*2*npair > 65535, an input or a state above
+ * XENG_CDEDISP_MAX_STATE_BYTES; after the device is known, an LDS need above what a work-group may take.  Rejected by SetChirp: a
+ * NULL table, a non-finite word.  Rejected by Run without a launch: a NULL input or result, a misaligned pointer, a NULL output on
+ * a call that completes a block.  Every call without a context: XENG_STATUS_INVALID_STATE. */
+#define XENG_CDEDISP_MAX_STATE_BYTES (1LL << 32)
+int xengCdedispInitialize(int gpu, int nchan, int nbeam, int ntime, int pair0, int npair, int nfft, int overlap);
+/* table: cf32[npair][nchan][nfft] on the host (see above).  Waits for the context's work in flight, uploads the table and does not
+ * touch the time buffer: it holds from the next block to complete. */
+int xengCdedispSetChirp(const float *table);
+/* enqueue only.  *nblocks is the number of blocks the call completes; the host's sample count decides it before anything is
+ * enqueued, and out_dev is written for those blocks only.  out_dev may be NULL on a call that completes none. */
+int xengCdedispRun(const void *in_dev, void *out_dev, int *nblocks);
+/* host state only, nothing is launched and nothing cleared: the next input sample counts as sample 0 */
+int xengCdedispReset(void);
+/* the step L, the most blocks one call completes, samples taken and blocks completed since the last reset */
+int xengCdedispGetInfo(int *step, int *max_blocks_per_call, long long *nsamples_since_reset, long long *nblocks_since_reset);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengCdedispCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengCdedispMark(unsigned long long *ticket);
+int xengCdedispWait(unsigned long long ticket);
+int xengCdedispTicketDone(unsigned long long ticket, int *done);
+int xengCdedispSync(void);
+int xengCdedispDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
