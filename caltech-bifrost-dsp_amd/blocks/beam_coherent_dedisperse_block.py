@@ -25,7 +25,6 @@ a sequence of its own there too, so that every sequence's cdedisp_dm is the DM i
 
 Not built: a bandpass taper, transforms above 2^13 points (the sweep below about 28 MHz at DM 10 needs them), barycentring.
 BeamDedisperse's single delay table cannot express a coherent DM per pair: behind this block it is right for one DM only."""
-import collections
 import json
 import math
 import time
@@ -34,8 +33,7 @@ import numpy as np
 
 from ..backend import default_backend
 from ..ndarray import XArray, copy_array
-from ..proclog import cpu_affinity
-from .block_base import Block, declare_streams, gulp_time, spans_outlive_release
+from .block_base import Block, InFlight, declare_streams, gulp_time, spans_outlive_release
 from .coherent_dedisp import NFFT_MAX, NFFT_MIN, cdedisp_plan, chirp_table, smear_samples
 
 WHO = "BEAM_COHERENT_DEDISPERSE"
@@ -91,11 +89,6 @@ class BeamCoherentDedisperse(Block):
         if (nfft - overlap) % multiple_of:
             raise ValueError("%s: the step %d is not a multiple of %d" % (WHO, nfft - overlap, multiple_of))
 
-    def _call(self, name, *args):
-        rv = getattr(self._bf, name)(*args)
-        if rv != self._bf.BF_STATUS_SUCCESS:
-            raise RuntimeError("%s returned %d: %s" % (name, rv, self._bf.last_error()))
-
     def _initialize(self):
         self._call('cdedisp_initialize', self.gpu, self.nchan, self.nbeam, self.ntime_gulp, self.pair0, self.npair, self.nfft, self.overlap)
         self.step = self.nfft - self.overlap
@@ -141,70 +134,31 @@ class BeamCoherentDedisperse(Block):
                 raise ValueError("%s: the header's '%s' is %r: the chirp needs the band" % (WHO, k, v))
 
     def main(self):
-        cpu_affinity.set_core(self.core)
-        if self.gpu != -1:
-            self._bf.set_device(self.gpu)
-        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
-        # Streaming, tickets and the staged copy: as UpchanSumBeams (upchan_sum_beams_block.py).  A call that completes ONE block
-        # writes its span itself; one that completes several writes them side by side into a device buffer, and the copy stream
-        # moves each into a span of its own (so does every call when the output ring is pinned host memory).
+        self.bind()
+        # Streaming, tickets and the staged copy: InFlight (block_base.py).  A call that completes ONE block writes its span
+        # itself; one that completes several writes them side by side into a device buffer, and the copy stream moves each into
+        # a span of its own (so does every call when the output ring is pinned host memory).
         streaming = spans_outlive_release(self.iring, self.oring)
         can_copy = hasattr(self._bf, 'copy_async')
         self._staged = streaming and self.oring.space == 'cuda_host' and can_copy
         self._dev = None
-        self._stages_free = []
-        pending = collections.deque()           # (ticket, output spans, input kept alive, device buffer or None)
-        copying = collections.deque()           # (stamp of the copy, output span, device buffer to give back or None)
+        with InFlight(self._bf.cdedisp_wait, self._bf.cdedisp_sync, self._bf, outstanding=lambda: 2 * self.max_blocks) as inflight, \
+                self.oring.begin_writing() as oring:
+            for iseq in self.iring.read(guarantee=self.guarantee):
+                self._sequence(iseq, oring, streaming, can_copy, inflight)
 
-        def finish_copies(keep):
-            while copying and (len(copying) > keep or self._bf.copy_done(copying[0][0])):
-                stamp, osp, stage = copying.popleft()
-                self._bf.copy_wait(stamp)       # (returns at once when it is done)
-                osp.close()
-                if stage is not None:
-                    self._stages_free.append(stage)
-
-        def retire(keep):
-            while len(pending) > keep:
-                ticket, osps, _, stage = pending.popleft()
-                self._bf.cdedisp_wait(ticket)
-                for k, osp in enumerate(osps):
-                    if stage is None:
-                        finish_copies(0)        # (spans are committed in order: the copies of earlier calls first)
-                        osp.close()
-                    else:
-                        piece = stage.byte_slice(k * self._unit, self._unit)
-                        copying.append((self._bf.copy_async(osp.data, piece), osp, stage if k == len(osps) - 1 else None))
-            finish_copies(2 * self.max_blocks if keep and self._live else 0)
-
-        try:
-            with self.oring.begin_writing() as oring:
-                for iseq in self.iring.read(guarantee=self.guarantee):
-                    self._sequence(iseq, oring, streaming, can_copy, pending, retire)
-        finally:
-            # (spans of kernels in flight are not released by an exception before the stream is idle)
-            if pending or copying:
-                try:
-                    self._bf.cdedisp_sync()
-                    for stamp, _, _ in copying:
-                        self._bf.copy_wait(stamp)
-                except Exception:
-                    pass
-                pending.clear()
-                copying.clear()
-
-    def _sequence(self, iseq, oring, streaming, can_copy, pending, retire):
+    def _sequence(self, iseq, oring, streaming, can_copy, inflight):
         ihdr = json.loads(iseq.header.tostring())
         self.sequence_proclog.update(ihdr)
         self._check_header(ihdr)
-        retire(0)
+        inflight.retire(0)
         if self.nfft is None:
             freqs, chan_bw = self._freqs(ihdr)
             self.nfft, self.overlap = cdedisp_plan(freqs, chan_bw, max(abs(d) for d in self.dms), self.multiple_of)
             self.log.info("%s >> planned nfft %d, overlap %d" % (WHO, self.nfft, self.overlap))
         if not self._live:
             self._initialize()
-        unit = self._unit = self.nchan * 2 * self.npair * self.step * 8
+        unit = self.nchan * 2 * self.npair * self.step * 8
         self.oring.resize(unit)
         seq0 = ihdr['seq0']
         igulp_size = self.nchan * self.nbeam * self.ntime_gulp * 8
@@ -236,7 +190,7 @@ class BeamCoherentDedisperse(Block):
                         self.update_stats({'dms': self.dms})
                         restart = True
                 if restart and oseq is not None:
-                    retire(0)
+                    inflight.retire(0)
                     oseq.end()
                     oseq = None
                 expected = this_gulp_time + self.ntime_gulp
@@ -261,7 +215,7 @@ class BeamCoherentDedisperse(Block):
                     if direct:
                         target = ospans[0].data
                     elif staged:
-                        stage = self._stages_free.pop() if self._stages_free else XArray(shape=(self.max_blocks * unit,), dtype=np.uint8, space=self._bf.space_in)
+                        stage = inflight.take_stage(self.max_blocks * unit)
                         target = stage
                     elif nb:
                         if self._dev is None or self._dev.nbytes != self.max_blocks * unit:
@@ -277,10 +231,10 @@ class BeamCoherentDedisperse(Block):
                         self.update_stats({'nblock': self.stats['nblock'] + nb, 'last_end_sample': self._first + self._nblocks * self.step + self.overlap // 2})
                     if direct or staged or (streaming and nb == 0):
                         osps, ospans = ospans, []
-                        pending.append((self._bf.cdedisp_mark(), osps, held, stage))
-                        retire(self.STREAM_DEPTH)
+                        inflight.push(self._bf.cdedisp_mark(), osps, held, stage)
+                        inflight.retire(self.STREAM_DEPTH)
                     else:
-                        retire(0)               # (spans are committed in order)
+                        inflight.retire(0)      # (spans are committed in order)
                         self._bf.cdedisp_sync()
                         while ospans:
                             k = nb - len(ospans)
@@ -294,6 +248,6 @@ class BeamCoherentDedisperse(Block):
                 prev_time = curr_time
                 self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
         finally:
-            retire(0)                           # every call in flight is complete (and every output span committed) first
+            inflight.retire(0)                  # every call in flight is complete (and every output span committed) first
             if oseq is not None:
                 oseq.end()

@@ -15,16 +15,15 @@ A new sequence or a gap in the input (spans this reader never saw) resets the co
 sequence of its own (UpchanSumBeams' rule).  A `weights` command (a list of nfine finite numbers; 0 leaves a channel out, e.g.
 one flagged by UpchanSpectra's spectral kurtosis) takes effect at the next span, on the history already held too.
 """
-import collections
 import json
+import math
 import time
 
 import numpy as np
 
 from ..backend import default_backend
 from ..ndarray import XArray
-from ..proclog import cpu_affinity
-from .block_base import Block, declare_streams, gulp_time, spans_outlive_release
+from .block_base import Block, InFlight, declare_streams, gulp_time, spans_outlive_release
 from .dedisp import dm_delays
 
 STOKES = {'I': 1, 'full': 4}
@@ -46,6 +45,50 @@ def check_power_beam_header(who, ihdr, npair, nchan, nupchan):
     if ihdr.get('acc_len', acc_len) != acc_len:
         raise ValueError("%s: acc_len %r in the header is not nframe_sum x nupchan = %d" % (who, ihdr.get('acc_len'), acc_len))
     return acc_len
+
+
+def _number(v):
+    """A finite int or float (a bool is neither)."""
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+
+
+def check_dedispersed_header(who, ihdr, npair, ndm):
+    """The header of BeamDedisperse's output, as every reader of that ring (BeamPulseSearch, BeamPeriodSearch) checks it; returns
+    (nprod, acc_len, dedisp_latency, dms, tsamp)."""
+    if 'ndm' not in ihdr:
+        raise ValueError("%s: the input carries no 'ndm': it has not been dedispersed" % who)
+    if ihdr.get('ndm') != ndm or ihdr.get('nbeam') != npair:
+        raise ValueError("%s: %r trials x %r pairs in the header, %d x %d configured" % (who, ihdr.get('ndm'), ihdr.get('nbeam'), ndm, npair))
+    if ihdr.get('nprod') not in (1, 4):
+        raise ValueError("%s: nprod %r in the header, not 1 or 4" % (who, ihdr.get('nprod')))
+    if not _number(ihdr.get('tsamp')) or not ihdr['tsamp'] > 0:
+        raise ValueError("%s: the header's 'tsamp' is %r" % (who, ihdr.get('tsamp')))
+    dms = ihdr.get('dms')
+    if not isinstance(dms, list) or len(dms) != ndm:
+        raise ValueError("%s: the header's 'dms' are not %d trials" % (who, ndm))
+    S = ihdr.get('dedisp_latency')
+    if not isinstance(S, int) or isinstance(S, bool) or S < 0:
+        raise ValueError("%s: the header's 'dedisp_latency' is %r" % (who, S))
+    acc_len = ihdr.get('acc_len')
+    if acc_len is None and isinstance(ihdr.get('nframe_sum'), int) and isinstance(ihdr.get('nupchan'), int):
+        acc_len = ihdr['nframe_sum'] * ihdr['nupchan']
+    if not isinstance(acc_len, int) or isinstance(acc_len, bool) or acc_len <= 0:
+        raise ValueError("%s: the header's 'acc_len' is %r: no window length in samples" % (who, acc_len))
+    return ihdr['nprod'], acc_len, S, dms, float(ihdr['tsamp'])
+
+
+def checked_fine_weights(who, w, nfine, quiet=False):
+    """The per-fine-channel weights as the library takes them, f32 [nfine]; not `nfine` finite numbers: ValueError, or None if `quiet`."""
+    try:
+        a = np.ascontiguousarray(w, np.float32).reshape(-1)
+        ok = a.size == nfine and bool(np.all(np.isfinite(a)))
+    except (TypeError, ValueError):
+        a, ok = None, False
+    if ok:
+        return a
+    if quiet:
+        return None
+    raise ValueError("%s: the weights must be %d finite numbers" % (who, nfine))
 
 
 class BeamDedisperse(Block):
@@ -80,16 +123,7 @@ class BeamDedisperse(Block):
             self._initialize(max_delay)
 
     def _checked_weights(self, w, quiet=False):
-        try:
-            a = np.ascontiguousarray(w, np.float32).reshape(-1)
-            ok = a.size == self.nfine and bool(np.all(np.isfinite(a)))
-        except (TypeError, ValueError):
-            a, ok = None, False
-        if ok:
-            return a
-        if quiet:
-            return None
-        raise ValueError("BEAM_DEDISPERSE: the weights must be %d finite numbers" % self.nfine)
+        return checked_fine_weights("BEAM_DEDISPERSE", w, self.nfine, quiet)
 
     def _initialize(self, max_delay):
         rv = self._bf.dedisp_initialize(self.gpu, self.npair, self.nfine, self.nwin, self.ndm, max_delay, self.nprod)
@@ -123,53 +157,17 @@ class BeamDedisperse(Block):
         return ohdr
 
     def main(self):
-        cpu_affinity.set_core(self.core)
-        if self.gpu != -1:
-            self._bf.set_device(self.gpu)
-        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
+        self.bind()
         self._oshape = (self.nwin, self.npair, self.ndm, self.nprod)
         ogulp_size = int(np.prod(self._oshape)) * 4
         self.oring.resize(ogulp_size)
-        # Streaming, tickets and the staged copy into a pinned-host output ring: as UpchanSumBeams (upchan_sum_beams_block.py)
+        # Streaming, tickets and the staged copy into a pinned-host output ring: InFlight (block_base.py)
         streaming = spans_outlive_release(self.iring, self.oring)
         self._staged = streaming and self.oring.space == 'cuda_host' and hasattr(self._bf, 'copy_async')
         self._dev = None if streaming else XArray(shape=self._oshape, dtype=np.float32, space=self._bf.space_in)
-        self._stages_free = []
-        pending = collections.deque()           # (ticket, output span, input kept alive, device buffer or None)
-        copying = collections.deque()           # (stamp of the copy, output span, device buffer)
-
-        def finish_copies(keep):
-            while copying and (len(copying) > keep or self._bf.copy_done(copying[0][0])):
-                stamp, osp, stage = copying.popleft()
-                self._bf.copy_wait(stamp)       # (returns at once when it is done)
-                osp.close()
-                self._stages_free.append(stage)
-
-        def retire(keep):
-            while len(pending) > keep:
-                ticket, osp, _, stage = pending.popleft()
-                self._bf.dedisp_wait(ticket)
-                if stage is None:
-                    osp.close()
-                else:
-                    copying.append((self._bf.copy_async(osp.data, stage), osp, stage))
-            finish_copies(2 if keep else 0)
-
-        try:
-            with self.oring.begin_writing() as oring:
-                for iseq in self.iring.read(guarantee=self.guarantee):
-                    self._sequence(iseq, oring, ogulp_size, streaming, pending, retire)
-        finally:
-            # (spans of kernels in flight are not released by an exception before the stream is idle)
-            if pending or copying:
-                try:
-                    self._bf.dedisp_sync()
-                    for stamp, _, _ in copying:
-                        self._bf.copy_wait(stamp)
-                except Exception:
-                    pass
-                pending.clear()
-                copying.clear()
+        with InFlight(self._bf.dedisp_wait, self._bf.dedisp_sync, self._bf) as inflight, self.oring.begin_writing() as oring:
+            for iseq in self.iring.read(guarantee=self.guarantee):
+                self._sequence(iseq, oring, ogulp_size, streaming, inflight)
 
     def _load_pending_weights(self):
         """A `weights` command: on the device before the next span is enqueued (SetWeights waits for the spans in flight)."""
@@ -179,7 +177,7 @@ class BeamDedisperse(Block):
             self._weights = self._checked_weights(w)
             self._set_weights()
 
-    def _sequence(self, iseq, oring, ogulp_size, streaming, pending, retire):
+    def _sequence(self, iseq, oring, ogulp_size, streaming, inflight):
         ihdr = json.loads(iseq.header.tostring())
         self.sequence_proclog.update(ihdr)
         acc_len = self._check_header(ihdr)
@@ -187,7 +185,7 @@ class BeamDedisperse(Block):
         S = int(table.max())
         if self.max_delay is not None and S > self.max_delay:
             raise ValueError("BEAM_DEDISPERSE: DM %g needs a delay of %d windows of %g s, max_delay is %d" % (self.dms.max(), S, tsamp, self.max_delay))
-        retire(0)
+        inflight.retire(0)
         if self.max_delay is None and self._ctx_delay != S:
             self._initialize(S)                 # (a history as long as this sequence's table needs)
         rv = self._bf.dedisp_set_delays(table)  # (clears the history and the window count: a new sequence starts from nothing)
@@ -212,7 +210,7 @@ class BeamDedisperse(Block):
                     self.update_stats({'ngap': self.stats['ngap'] + 1})
                     self.log.warning("BEAM_DEDISPERSE >> samples [%d, %d) were not read: the history starts again" % (expected, this_gulp_time))
                     if oseq is not None:
-                        retire(0)
+                        inflight.retire(0)
                         oseq.end()
                         oseq = None
                 expected = this_gulp_time + ntime_span
@@ -229,7 +227,7 @@ class BeamDedisperse(Block):
                 stage = None
                 try:
                     if self._staged:
-                        stage = self._stages_free.pop() if self._stages_free else XArray(shape=(ogulp_size,), dtype=np.uint8, space=self._bf.space_in)
+                        stage = inflight.take_stage(ogulp_size)
                     target = stage if stage is not None else (ospan.data if streaming else self._dev)
                     rv = self._bf.dedisp_run(held, self.nwin, target)
                     if rv != self._bf.BF_STATUS_SUCCESS:
@@ -237,8 +235,8 @@ class BeamDedisperse(Block):
                     self.update_stats({'nwindow': self.stats['nwindow'] + self.nwin, 'last_end_sample': this_gulp_time + ntime_span})
                     osp, ospan = ospan, None
                     if streaming:
-                        pending.append((self._bf.dedisp_mark(), osp, held, stage))
-                        retire(self.STREAM_DEPTH)
+                        inflight.push(self._bf.dedisp_mark(), osp, held, stage)
+                        inflight.retire(self.STREAM_DEPTH)
                     else:
                         self._bf.dedisp_sync()
                         try:
@@ -253,6 +251,6 @@ class BeamDedisperse(Block):
                 prev_time = curr_time
                 self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
         finally:
-            retire(0)                           # every call in flight is complete (and every output span committed) first
+            inflight.retire(0)                  # every call in flight is complete (and every output span committed) first
             if oseq is not None:
                 oseq.end()

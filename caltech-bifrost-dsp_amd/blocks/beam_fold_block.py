@@ -33,8 +33,7 @@ import numpy as np
 
 from ..backend import default_backend
 from ..ndarray import XArray, copy_array
-from ..proclog import cpu_affinity
-from .beam_dedisperse_block import STOKES, check_power_beam_header
+from .beam_dedisperse_block import STOKES, check_power_beam_header, checked_fine_weights
 from .block_base import Block, InFlight, declare_streams, gulp_time, spans_outlive_release
 from .fold import fold_phase, fold_rotations, fold_rotations_coherent
 
@@ -105,21 +104,7 @@ class BeamFold(Block):
             return False
 
     def _checked_weights(self, w, quiet=False):
-        try:
-            a = np.ascontiguousarray(w, np.float32).reshape(-1)
-            ok = a.size == self.nfine and bool(np.all(np.isfinite(a)))
-        except (TypeError, ValueError):
-            a, ok = None, False
-        if ok:
-            return a
-        if quiet:
-            return None
-        raise ValueError("%s: the weights must be %d finite numbers" % (WHO, self.nfine))
-
-    def _call(self, name, *args):
-        rv = getattr(self._bf, name)(*args)
-        if rv != self._bf.BF_STATUS_SUCCESS:
-            raise RuntimeError("%s returned %d: %s" % (name, rv, self._bf.last_error()))
+        return checked_fine_weights(WHO, w, self.nfine, quiet)
 
     # ---- what the library is told, from the header and the pulsar list
     def rotations(self, ihdr):
@@ -164,10 +149,7 @@ class BeamFold(Block):
         return ohdr
 
     def main(self):
-        cpu_affinity.set_core(self.core)
-        if self.gpu != -1:
-            self._bf.set_device(self.gpu)
-        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
+        self.bind()
         self._oshape = (self.npair, self.nprod, self.nfine // self.nfscr, self.nbin)
         ogulp_size = int(np.prod(self._oshape)) * 4
         self.oring.resize(ogulp_size)

@@ -23,22 +23,16 @@ sequence of its own (UpchanSumBeams' rule, as in BeamDedisperse).  A `threshold`
 
 Not built: a robust baseline (a bright pulse in block k raises sigma for block k+1), clustering in time across spans, and a
 trigger writer."""
-import collections
 import json
-import math
 import time
 
 import numpy as np
 
 from ..backend import default_backend
 from ..ndarray import XArray
-from ..proclog import cpu_affinity
-from .block_base import Block, declare_streams, gulp_time, spans_outlive_release
+from .beam_dedisperse_block import _number, check_dedispersed_header
+from .block_base import Block, InFlight, declare_streams, gulp_time, spans_outlive_release
 from .pulse_search import RECORD, as_records, pulse_candidates
-
-
-def _number(v):
-    return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
 
 
 class BeamPulseSearch(Block):
@@ -79,30 +73,6 @@ class BeamPulseSearch(Block):
             raise RuntimeError("xengPulseInitialize returned %d: %s" % (rv, self._bf.last_error()))
         self._ctx_nprod = nprod
 
-    def _check_header(self, ihdr):
-        """The output of BeamDedisperse only; returns (nprod, acc_len, dedisp_latency, dms)."""
-        who = "BEAM_PULSE_SEARCH"
-        if 'ndm' not in ihdr:
-            raise ValueError("%s: the input carries no 'ndm': it has not been dedispersed" % who)
-        if ihdr.get('ndm') != self.ndm or ihdr.get('nbeam') != self.npair:
-            raise ValueError("%s: %r trials x %r pairs in the header, %d x %d configured" % (who, ihdr.get('ndm'), ihdr.get('nbeam'), self.ndm, self.npair))
-        if ihdr.get('nprod') not in (1, 4):
-            raise ValueError("%s: nprod %r in the header, not 1 or 4" % (who, ihdr.get('nprod')))
-        if not _number(ihdr.get('tsamp')) or not ihdr['tsamp'] > 0:
-            raise ValueError("%s: the header's 'tsamp' is %r" % (who, ihdr.get('tsamp')))
-        dms = ihdr.get('dms')
-        if not isinstance(dms, list) or len(dms) != self.ndm:
-            raise ValueError("%s: the header's 'dms' are not %d trials" % (who, self.ndm))
-        S = ihdr.get('dedisp_latency')
-        if not isinstance(S, int) or isinstance(S, bool) or S < 0:
-            raise ValueError("%s: the header's 'dedisp_latency' is %r" % (who, S))
-        acc_len = ihdr.get('acc_len')
-        if acc_len is None and isinstance(ihdr.get('nframe_sum'), int) and isinstance(ihdr.get('nupchan'), int):
-            acc_len = ihdr['nframe_sum'] * ihdr['nupchan']
-        if not isinstance(acc_len, int) or isinstance(acc_len, bool) or acc_len <= 0:
-            raise ValueError("%s: the header's 'acc_len' is %r: no window length in samples" % (who, acc_len))
-        return ihdr['nprod'], acc_len, S, dms
-
     def output_header(self, ihdr, start):
         ohdr = ihdr.copy()
         ohdr.update(nwidth=self.nwidth, nstat=self.nstat, widths=list(self.widths), threshold=self.threshold, seq0=start)
@@ -128,60 +98,24 @@ class BeamPulseSearch(Block):
             osp.close()
 
     def main(self):
-        cpu_affinity.set_core(self.core)
-        if self.gpu != -1:
-            self._bf.set_device(self.gpu)
-        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
+        self.bind()
         ogulp_size = self.npair * self.ndm * RECORD.itemsize
         self.oring.resize(ogulp_size)
-        # Streaming, tickets and the staged copy into a pinned-host output ring: as BeamDedisperse (beam_dedisperse_block.py)
+        # Streaming, tickets and the staged copy into a pinned-host output ring: InFlight (block_base.py)
         ospace = getattr(self.oring, 'space', 'system')
         direct = ospace in (self._bf.space_in, 'cuda_host')     # (the kernel can write the span itself)
         self._staged = spans_outlive_release(self.iring, self.oring) and ospace == 'cuda_host' and hasattr(self._bf, 'copy_async')
         streaming = spans_outlive_release(self.iring, self.oring) and (direct or self._staged)
         self._dev = None if streaming else XArray(shape=(ogulp_size,), dtype=np.uint8, space=self._bf.space_in)
-        self._stages_free = []
-        pending = collections.deque()           # (ticket, output span, input kept alive, device buffer or None, meta)
-        copying = collections.deque()           # (stamp of the copy, output span, device buffer, meta)
+        with InFlight(self._bf.pulse_wait, self._bf.pulse_sync, self._bf, finish=self._finish) as inflight, self.oring.begin_writing() as oring:
+            for iseq in self.iring.read(guarantee=self.guarantee):
+                self._sequence(iseq, oring, ogulp_size, streaming, inflight)
 
-        def finish_copies(keep):
-            while copying and (len(copying) > keep or self._bf.copy_done(copying[0][0])):
-                stamp, osp, stage, meta = copying.popleft()
-                self._bf.copy_wait(stamp)       # (returns at once when it is done)
-                self._stages_free.append(stage)
-                self._finish(osp, meta)
-
-        def retire(keep):
-            while len(pending) > keep:
-                ticket, osp, _, stage, meta = pending.popleft()
-                self._bf.pulse_wait(ticket)
-                if stage is None:
-                    self._finish(osp, meta)
-                else:
-                    copying.append((self._bf.copy_async(osp.data, stage), osp, stage, meta))
-            finish_copies(2 if keep else 0)
-
-        try:
-            with self.oring.begin_writing() as oring:
-                for iseq in self.iring.read(guarantee=self.guarantee):
-                    self._sequence(iseq, oring, ogulp_size, streaming, pending, retire)
-        finally:
-            # (spans of kernels in flight are not released by an exception before the stream is idle)
-            if pending or copying:
-                try:
-                    self._bf.pulse_sync()
-                    for stamp, _, _, _ in copying:
-                        self._bf.copy_wait(stamp)
-                except Exception:
-                    pass
-                pending.clear()
-                copying.clear()
-
-    def _sequence(self, iseq, oring, ogulp_size, streaming, pending, retire):
+    def _sequence(self, iseq, oring, ogulp_size, streaming, inflight):
         ihdr = json.loads(iseq.header.tostring())
         self.sequence_proclog.update(ihdr)
-        nprod, acc_len, S, dms = self._check_header(ihdr)
-        retire(0)
+        nprod, acc_len, S, dms, _ = check_dedispersed_header("BEAM_PULSE_SEARCH", ihdr, self.npair, self.ndm)
+        inflight.retire(0)
         if self._ctx_nprod != nprod:
             self._initialize(nprod)
         else:
@@ -204,7 +138,7 @@ class BeamPulseSearch(Block):
                     self.update_stats({'ngap': self.stats['ngap'] + 1})
                     self.log.warning("BEAM_PULSE_SEARCH >> samples [%d, %d) were not read: the baseline starts again" % (expected, this_gulp_time))
                     if oseq is not None:
-                        retire(0)
+                        inflight.retire(0)
                         oseq.end()
                         oseq = None
                 expected = this_gulp_time + ntime_span
@@ -224,7 +158,7 @@ class BeamPulseSearch(Block):
                 stage = None
                 try:
                     if self._staged:
-                        stage = self._stages_free.pop() if self._stages_free else XArray(shape=(ogulp_size,), dtype=np.uint8, space=self._bf.space_in)
+                        stage = inflight.take_stage(ogulp_size)
                     target = stage if stage is not None else (ospan.data if streaming else self._dev)
                     rv = self._bf.pulse_run(held, self.nwin, target)
                     if rv != self._bf.BF_STATUS_SUCCESS:
@@ -232,8 +166,8 @@ class BeamPulseSearch(Block):
                     self.update_stats({'nwindow': self.stats['nwindow'] + self.nwin, 'last_end_sample': this_gulp_time + ntime_span})
                     osp, ospan = ospan, None
                     if streaming:
-                        pending.append((self._bf.pulse_mark(), osp, held, stage, meta))
-                        retire(self.STREAM_DEPTH)
+                        inflight.push(self._bf.pulse_mark(), osp, held, stage, meta)
+                        inflight.retire(self.STREAM_DEPTH)
                     else:
                         self._bf.pulse_sync()
                         try:
@@ -250,6 +184,6 @@ class BeamPulseSearch(Block):
                 prev_time = curr_time
                 self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
         finally:
-            retire(0)                           # every call in flight is complete (and every output span committed) first
+            inflight.retire(0)                  # every call in flight is complete (and every output span committed) first
             if oseq is not None:
                 oseq.end()

@@ -130,11 +130,7 @@ class Beamform(Block):
             self.update_stats({'cal_gains%d' % b: self.stats['cal_gains%d' % b] for b in range(self.nbeam)})
 
     def main(self):
-        cpu_affinity.set_core(self.core)
-        if self.gpu != -1:
-            self._bf.set_device(self.gpu)
-        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1,
-                                  'gpu0': self._bf.get_device()})
+        self.bind()
         igulp_size = self.ntime_gulp * self.nchan * self.ninput           # 4+4 bit
         ogulp_size = self.ntime_blocks * self.nchan * self.nbeam * 8      # complex64
         self.oring.resize(ogulp_size)

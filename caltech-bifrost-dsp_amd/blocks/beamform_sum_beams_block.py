@@ -6,7 +6,6 @@ samples it emits [XX, YY, Re(XY*), Im(XY*)] per channel, f32 [nbeam/2, ntime/nti
 (:220-222; math beamformer_sum_test.py:64-77).  The beamformer context is the process-global
 one the Beamform block created (:186-187): this block does not initialise it.
 """
-import collections
 import json
 import time
 
@@ -14,8 +13,7 @@ import numpy as np
 
 from ..backend import default_backend
 from ..ndarray import XArray
-from ..proclog import cpu_affinity
-from .block_base import Block, declare_streams
+from .block_base import Block, InFlight, declare_streams
 
 
 class BeamformSumBeams(Block):
@@ -38,11 +36,7 @@ class BeamformSumBeams(Block):
             self._bf.set_device(self.gpu)
 
     def main(self):
-        cpu_affinity.set_core(self.core)
-        if self.gpu != -1:
-            self._bf.set_device(self.gpu)
-        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1,
-                                  'gpu0': self._bf.get_device()})
+        self.bind()
         # Streaming (in-repo rings): up to STREAM_DEPTH gulps in flight; a span is committed when its own kernel (and copy) has
         # completed.  On a bifrost ring: the reference's Integrate -> wait -> copy (:243-250).
         # Where the sums go: the pipeline's output ring is pinned host memory (lwa352-pipeline.py:155).  Round 3 let the kernel
@@ -50,46 +44,15 @@ class BeamformSumBeams(Block):
         # the stream the beamformer kernels queue on, 2.5 times per integration (profiles/r04/blocks_kernel_time.txt).  So
         # (round 4) the kernel writes a device buffer, and once ITS ticket is done the buffer goes to the pinned span on the
         # copy stream; the span is committed when that copy has completed.  A device output ring still takes the sums directly.
+        # The calls and copies in flight are InFlight's (block_base.py).
         streaming = (getattr(self.iring, 'span_memory_outlives_release', False) and getattr(self.oring, 'span_memory_outlives_release', False)
                      and hasattr(self._bf, 'beam_mark')
                      and (self.oring.space in ('cuda', 'cuda_host') or self.oring.space == self._bf.space_in))      # (the kernel writes the span)
-        staged = streaming and self.oring.space == 'cuda_host' and hasattr(self._bf, 'copy_async')
-        pending = collections.deque()           # (ticket, output span, input kept alive, device buffer or None)
-        copying = collections.deque()           # (stamp of the copy, output span, device buffer)
-        self._stages_free = []
+        self._staged = streaming and self.oring.space == 'cuda_host' and hasattr(self._bf, 'copy_async')
+        with InFlight(getattr(self._bf, 'beam_wait', None), self._bf.beam_sync, self._bf) as inflight:
+            self._main_loop(streaming, inflight)
 
-        def finish_copies(keep):
-            while copying and (len(copying) > keep or self._bf.copy_done(copying[0][0])):
-                stamp, osp, stage = copying.popleft()
-                self._bf.copy_wait(stamp)       # (returns at once when it is done)
-                osp.close()
-                self._stages_free.append(stage)
-
-        def retire(keep):
-            while len(pending) > keep:
-                ticket, osp, _, stage = pending.popleft()
-                self._bf.beam_wait(ticket)
-                if stage is None:
-                    osp.close()
-                else:
-                    copying.append((self._bf.copy_async(osp.data, stage), osp, stage))
-            finish_copies(2 if keep else 0)
-        self._staged = staged
-        try:
-            self._main_loop(streaming, pending, retire)
-        finally:
-            # (as in Beamform: spans of kernels in flight are not released by an exception before the stream is idle)
-            if pending or copying:
-                try:
-                    self._bf.beam_sync()
-                    for stamp, _, _ in copying:
-                        self._bf.copy_wait(stamp)
-                except Exception:
-                    pass
-                pending.clear()
-                copying.clear()
-
-    def _main_loop(self, streaming, pending, retire):
+    def _main_loop(self, streaming, inflight):
         with self.oring.begin_writing() as oring:
             for iseq in self.iring.read(guarantee=self.guarantee):
                 ihdr = json.loads(iseq.header.tostring())
@@ -143,19 +106,15 @@ class BeamformSumBeams(Block):
                             reserve_time = curr_time - prev_time
                             prev_time = curr_time
                             # (streaming: the kernel writes into the span itself; the call only needs addresses, so no typed views)
-                            stage = None
-                            if self._staged:
-                                stage = self._stages_free.pop() if self._stages_free else None
-                                if stage is None or stage.nbytes != ogulp_size:
-                                    stage = XArray(shape=(ogulp_size,), dtype=np.uint8, space=self._bf.space_in)
+                            stage = inflight.take_stage(ogulp_size) if self._staged else None
                             target = stage if stage is not None else (ospan.data if streaming else self.bf_output)
                             rv = self._bf.bfBeamformIntegrate(ispan.data.as_BFarray(), target.as_BFarray(), self.ntime_sum)
                             if rv != self._bf.BF_STATUS_SUCCESS:
                                 raise RuntimeError("bfBeamformIntegrate returned %d: %s" % (rv, self._bf.last_error()))
                             if streaming:
-                                pending.append((self._bf.beam_mark(), ospan, ispan.data, stage))
+                                inflight.push(self._bf.beam_mark(), ospan, ispan.data, stage)
                                 ospan = None
-                                retire(self.STREAM_DEPTH)
+                                inflight.retire(self.STREAM_DEPTH)
                             else:
                                 self._bf.beam_sync()
                                 ospan.data_view(np.float32).reshape(self.bf_output.shape)[...] = self.bf_output       # (synchronous copy)
@@ -168,4 +127,4 @@ class BeamformSumBeams(Block):
                         self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': reserve_time,
                                                   'process_time': process_time,
                                                   'gbps': 8 * igulp_size / max(process_time, 1e-9) / 1e9})
-                    retire(0)
+                    inflight.retire(0)

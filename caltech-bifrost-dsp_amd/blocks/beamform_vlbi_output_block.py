@@ -107,10 +107,7 @@ class BeamformVlbiOutput(Block):
             self.log.error("VLBI OUTPUT >> Sending error: %s" % str(e))
 
     def main(self):
-        cpu_affinity.set_core(self.core)
-        if self.gpu != -1:
-            self._bf.set_device(self.gpu)
-        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
+        self.bind()
         # Streaming (in-repo rings): a gulp's input is kept until ITS kernel is done, its packets go to pinned memory on the copy
         # stream, and they are sent while the next gulp's kernel runs.  A bifrost ring: the synchronous form.
         streaming = (getattr(self.iring, 'span_memory_outlives_release', False) and hasattr(self._bf, 'beam_mark')
@@ -121,7 +118,7 @@ class BeamformVlbiOutput(Block):
         try:
             self._main_loop(streaming, inflight)
         finally:
-            # (as in Beamform / BeamformSumBeams: nothing a kernel or copy in flight still touches is let go before the stream is idle)
+            # (as InFlight does, block_base.py: nothing a kernel or copy in flight still touches is let go before the stream is idle)
             if inflight:
                 try:
                     self._bf.beam_sync()

@@ -10,6 +10,9 @@ import socket
 import time
 from threading import Lock
 
+import numpy as np
+
+from ..ndarray import XArray
 from ..proclog import ProcLog, cpu_affinity
 
 COMMAND_OK = 0
@@ -43,36 +46,80 @@ def spans_outlive_release(iring, oring):
 
 
 class InFlight(object):
-    """The calls of a streaming block whose kernels may still run, oldest first: (ticket, output span or None, input kept alive).
-    `wait(ticket)` / `sync()` are the backend's ticket wait and stream sync.  Used as a context manager: a block that leaves
-    with calls in flight (an exception) waits for the stream before it drops their spans, uncommitted -- released under a
-    running kernel, their memory would go back to the ring, to be handed out again or freed."""
+    """The calls of a streaming block whose kernels may still run, oldest first, and the copies of their outputs that may:
+    everything that keeps span memory from going back to a ring under a running kernel or copy.
 
-    def __init__(self, wait, sync):
-        self._wait, self._sync = wait, sync
-        self._calls = collections.deque()
+    `wait(ticket)` / `sync()` are the backend's ticket wait and stream sync.  A call is pushed with the ticket that follows its
+    kernels, its output span(s) (none: only the input is held) and the input it reads.  Its kernel wrote either the span itself,
+    or a `stage` from take_stage(): a device buffer that the copy stream (`backend`: copy_async / copy_done / copy_wait,
+    space_in) moves into the span(s) once the ticket is done -- a kernel that stores into a pinned-host span holds its stream
+    for the length of the transfer.  A span is handed to `finish(ospan, meta)` (default: close it) when its kernel and its copy
+    have completed, always in the order pushed.  `outstanding` (a number, or a callable that gives it): the copies a retire
+    that keeps calls may leave running.
 
-    def push(self, ticket, ospan, held):
-        self._calls.append((ticket, ospan, held))
+    Used as a context manager: a block that leaves with calls or copies in flight (an exception) waits for the stream and the
+    copies before it drops their spans, uncommitted -- released under a running kernel, their memory would go back to the
+    ring, to be handed out again or freed."""
+
+    def __init__(self, wait, sync, backend=None, finish=None, outstanding=2):
+        self._wait, self._sync, self._bf, self._outstanding = wait, sync, backend, outstanding
+        self._finish = finish if finish is not None else lambda ospan, meta: ospan.close()
+        self._calls = collections.deque()       # (ticket, output spans, input kept alive, stage or None, meta)
+        self._copies = collections.deque()      # (stamp, output span, stage to give back after this copy or None, meta)
+        self._stages = []
+
+    def take_stage(self, nbytes):
+        """A device buffer of `nbytes` for a kernel to write: a pooled one, or a new one when there is none of that size."""
+        stage = self._stages.pop() if self._stages else None
+        if stage is None or stage.nbytes != nbytes:
+            stage = XArray(shape=(nbytes,), dtype=np.uint8, space=self._bf.space_in)
+        return stage
+
+    def push(self, ticket, ospans, held, stage=None, meta=None):
+        if ospans is None:
+            ospans = ()
+        elif not isinstance(ospans, (list, tuple)):
+            ospans = (ospans,)
+        self._calls.append((ticket, ospans, held, stage, meta))
+
+    def _finish_copies(self, keep):
+        """Complete the oldest copies: those beyond the newest `keep`, and those that are done."""
+        while self._copies and (len(self._copies) > keep or self._bf.copy_done(self._copies[0][0])):
+            stamp, ospan, stage, meta = self._copies.popleft()
+            self._bf.copy_wait(stamp)           # (returns at once when it is done)
+            if stage is not None:
+                self._stages.append(stage)
+            self._finish(ospan, meta)
 
     def retire(self, keep):
-        """Wait for all but the newest `keep` calls, committing their output spans."""
+        """Wait for all but the newest `keep` calls; finish their output spans, or start the copies that fill them."""
         while len(self._calls) > keep:
-            ticket, ospan, _ = self._calls.popleft()
+            ticket, ospans, _, stage, meta = self._calls.popleft()
             self._wait(ticket)
-            if ospan is not None:
-                ospan.close()
+            for k, ospan in enumerate(ospans):
+                if stage is None:
+                    self._finish_copies(0)      # (spans are committed in order: the copies of earlier calls first)
+                    self._finish(ospan, meta)
+                    continue
+                dst = ospan.data
+                piece = stage if stage.nbytes == dst.nbytes else stage.byte_slice(k * dst.nbytes, dst.nbytes)
+                self._copies.append((self._bf.copy_async(dst, piece), ospan, stage if k == len(ospans) - 1 else None, meta))
+        if self._copies:
+            self._finish_copies((self._outstanding() if callable(self._outstanding) else self._outstanding) if keep else 0)
 
     def __enter__(self):
         return self
 
     def __exit__(self, *exc):
-        if self._calls:
+        if self._calls or self._copies:
             try:
                 self._sync()
+                for copy in self._copies:
+                    self._bf.copy_wait(copy[0])
             except Exception:
                 pass
             self._calls.clear()
+            self._copies.clear()
 
 
 def gulp_time(ispan, seq0, igulp_size, ntime_gulp, prev):
@@ -148,6 +195,19 @@ class Block(object):
         self._command_types = {}
         self._command_conditions = {}
         self._etcd_sets_pending = True
+
+    def bind(self):
+        """The first lines of a GPU block's main(): this thread on the block's core, the block's device current, both logged."""
+        cpu_affinity.set_core(self.core)
+        if self.gpu != -1:
+            self._bf.set_device(self.gpu)
+        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
+
+    def _call(self, name, *args):
+        """A call of the block's backend that returns a status: anything but success raises."""
+        rv = getattr(self._bf, name)(*args)
+        if rv != self._bf.BF_STATUS_SUCCESS:
+            raise RuntimeError("%s returned %d: %s" % (name, rv, self._bf.last_error()))
 
     # ------------------------------------------------------------------ command keys
     def define_command_key(self, name, type=None, condition=None, initial_val=None):

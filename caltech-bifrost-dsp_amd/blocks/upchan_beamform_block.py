@@ -176,10 +176,7 @@ class UpchanBeamform(Block):
         return ohdr
 
     def main(self):
-        cpu_affinity.set_core(self.core)
-        if self.gpu != -1:
-            self._bf.set_device(self.gpu)
-        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
+        self.bind()
         nout = self.nframe // self.nframe_sum if self.nframe_sum else self.nframe
         if self.dual_pol:
             ogulp_size = nout * (self.nbeam // 2) * self.nchan * self.nupchan * 16

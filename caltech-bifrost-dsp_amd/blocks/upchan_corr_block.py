@@ -26,7 +26,6 @@ import json
 import time
 
 from ..backend import default_backend
-from ..proclog import cpu_affinity
 from .block_base import Block, InFlight, declare_streams, gulp_time, split_frames, spans_outlive_release
 from .pfb import pfb_config
 
@@ -83,10 +82,7 @@ class UpchanCorr(Block):
         return ohdr
 
     def main(self):
-        cpu_affinity.set_core(self.core)
-        if self.gpu != -1:
-            self._bf.set_device(self.gpu)
-        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
+        self.bind()
         ogulp_size = self.nfine * self.ninput * self.ninput * 8
         self.oring.resize(ogulp_size)
         # In-repo rings keep a span's memory alive while it is referenced: several calls in flight, each input span held until

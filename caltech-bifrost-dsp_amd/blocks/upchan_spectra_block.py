@@ -24,7 +24,6 @@ import json
 import time
 
 from ..backend import default_backend
-from ..proclog import cpu_affinity
 from .block_base import Block, InFlight, declare_streams, gulp_time, split_frames, spans_outlive_release
 from .pfb import pfb_config
 
@@ -81,10 +80,7 @@ class UpchanSpectra(Block):
         return ohdr
 
     def main(self):
-        cpu_affinity.set_core(self.core)
-        if self.gpu != -1:
-            self._bf.set_device(self.gpu)
-        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
+        self.bind()
         ogulp_size = self.windows_per_gulp * 2 * self.nchan * self.nupchan * self.ninput * 4
         self.oring.resize(ogulp_size)
         # In-repo rings keep a span's memory alive while it is referenced: several gulps in flight, each input span held until

@@ -19,7 +19,6 @@ Input: Beamform's voltage spans, cf32 [nchan][nbeam][ntime_gulp], whole gulps.  
 the layout of UpchanBeamform's dual-pol output.  Fine channel j of coarse channel c is centred at
 sfreq + c*d + (j - nupchan/2)*d/nupchan, d = bw_hz / nchan.
 """
-import collections
 import json
 import time
 
@@ -27,8 +26,7 @@ import numpy as np
 
 from ..backend import default_backend
 from ..ndarray import XArray
-from ..proclog import cpu_affinity
-from .block_base import Block, declare_streams, gulp_time, spans_outlive_release
+from .block_base import Block, InFlight, declare_streams, gulp_time, spans_outlive_release
 from .pfb import pfb_config
 
 NUPCHAN = (8, 16, 32, 64)
@@ -98,59 +96,21 @@ class UpchanSumBeams(Block):
                 raise ValueError("UPCHAN_SUM_BEAMS: the input carries '%s': integrated or channelised products, not voltage beams" % k)
 
     def main(self):
-        cpu_affinity.set_core(self.core)
-        if self.gpu != -1:
-            self._bf.set_device(self.gpu)
-        self.bind_proclog.update({'ncore': 1, 'core0': cpu_affinity.get_core(), 'ngpu': 1, 'gpu0': self._bf.get_device()})
+        self.bind()
         self._oshape = (self.windows_per_gulp, self.npair, self.nchan, self.nupchan, 4)
         ogulp_size = int(np.prod(self._oshape)) * 4
         self.oring.resize(ogulp_size)
         # Streaming (in-repo rings): up to STREAM_DEPTH gulps in flight, each input held until ITS kernel has completed, each
         # output committed when its kernel (and copy) has.  On a bifrost ring: wait for the kernel after every gulp.
         # A pinned-host output ring (as the live power beams' is): the kernel writes a device buffer and the copy stream moves it
-        # once the kernel's ticket is done, as BeamformSumBeams does -- a kernel that stores across PCIe holds the beamformer's
-        # stream for the length of the transfer.
+        # once the kernel's ticket is done -- a kernel that stores across PCIe holds the beamformer's stream for the length of
+        # the transfer.  The calls and copies in flight are InFlight's (block_base.py).
         streaming = spans_outlive_release(self.iring, self.oring)
         self._staged = streaming and self.oring.space == 'cuda_host' and hasattr(self._bf, 'copy_async')
         self._dev = None if streaming else XArray(shape=self._oshape, dtype=np.float32, space=self._bf.space_in)
-        self._stages_free = []
-        pending = collections.deque()           # (ticket, output span or None, input kept alive, device buffer or None)
-        copying = collections.deque()           # (stamp of the copy, output span, device buffer)
-
-        def finish_copies(keep):
-            while copying and (len(copying) > keep or self._bf.copy_done(copying[0][0])):
-                stamp, osp, stage = copying.popleft()
-                self._bf.copy_wait(stamp)       # (returns at once when it is done)
-                osp.close()
-                self._stages_free.append(stage)
-
-        def retire(keep):
-            while len(pending) > keep:
-                ticket, osp, _, stage = pending.popleft()
-                self._bf.upchan_sum_beams_wait(ticket)
-                if osp is None:
-                    continue
-                if stage is None:
-                    osp.close()
-                else:
-                    copying.append((self._bf.copy_async(osp.data, stage), osp, stage))
-            finish_copies(2 if keep else 0)
-
-        try:
-            with self.oring.begin_writing() as oring:
-                for iseq in self.iring.read(guarantee=self.guarantee):
-                    self._sequence(iseq, oring, ogulp_size, streaming, pending, retire)
-        finally:
-            # (spans of kernels in flight are not released by an exception before the stream is idle)
-            if pending or copying:
-                try:
-                    self._bf.upchan_sum_beams_sync()
-                    for stamp, _, _ in copying:
-                        self._bf.copy_wait(stamp)
-                except Exception:
-                    pass
-                pending.clear()
-                copying.clear()
+        with InFlight(self._bf.upchan_sum_beams_wait, self._bf.upchan_sum_beams_sync, self._bf) as inflight, self.oring.begin_writing() as oring:
+            for iseq in self.iring.read(guarantee=self.guarantee):
+                self._sequence(iseq, oring, ogulp_size, streaming, inflight)
 
     def _drop(self, nlost, why):
         """Windows lost to gulps that were not read; the one in progress and the PFB history go with them."""
@@ -158,11 +118,11 @@ class UpchanSumBeams(Block):
         self.update_stats({'ndropped': self.stats['ndropped'] + nlost})
         self.log.warning("UPCHAN_SUM_BEAMS >> %d window(s) dropped: %s" % (nlost, why))
 
-    def _enqueued(self, streaming, pending, retire, ospan, held, stage):
+    def _enqueued(self, streaming, inflight, ospan, held, stage):
         """After a launch: keep the gulp in flight, or wait for it and hand the output over."""
         if streaming:
-            pending.append((self._bf.upchan_sum_beams_mark(), ospan, held, stage))
-            retire(self.STREAM_DEPTH)
+            inflight.push(self._bf.upchan_sum_beams_mark(), ospan, held, stage)
+            inflight.retire(self.STREAM_DEPTH)
             return
         self._bf.upchan_sum_beams_sync()
         if ospan is not None:
@@ -171,7 +131,7 @@ class UpchanSumBeams(Block):
             finally:
                 ospan.close()
 
-    def _sequence(self, iseq, oring, ogulp_size, streaming, pending, retire):
+    def _sequence(self, iseq, oring, ogulp_size, streaming, inflight):
         ihdr = json.loads(iseq.header.tostring())
         self.sequence_proclog.update(ihdr)
         self._check_header(ihdr)
@@ -196,7 +156,7 @@ class UpchanSumBeams(Block):
                     self._drop(max(0, k_hi - k_lo + 1), "samples [%d, %d) were not read" % (expected, this_gulp_time))
                     pos = None
                     if oseq is not None:
-                        retire(0)
+                        inflight.retire(0)
                         oseq.end()
                         oseq = None
                 expected = this_gulp_time + self.ntime_gulp
@@ -210,7 +170,7 @@ class UpchanSumBeams(Block):
                             rv = self._bf.upchan_sum_beams_prime(held)
                             if rv != self._bf.BF_STATUS_SUCCESS:
                                 raise RuntimeError("xengUpchanSumBeamsPrime returned %d: %s" % (rv, self._bf.last_error()))
-                            self._enqueued(streaming, pending, retire, None, held, None)
+                            self._enqueued(streaming, inflight, None, held, None)
                         continue                # (waiting for a window boundary)
                     pos = 0
                 if oseq is None:
@@ -224,7 +184,7 @@ class UpchanSumBeams(Block):
                     if pos == gpw - 1:          # this gulp completes a window (or F / W of them)
                         ospan = oseq.reserve(ogulp_size)
                         if self._staged:
-                            stage = self._stages_free.pop() if self._stages_free else XArray(shape=(ogulp_size,), dtype=np.uint8, space=self._bf.space_in)
+                            stage = inflight.take_stage(ogulp_size)
                         target = stage if stage is not None else (ospan.data if streaming else self._dev)
                     rv = self._bf.upchan_sum_beams_run(held, target)
                     if rv != self._bf.BF_STATUS_SUCCESS:
@@ -234,7 +194,7 @@ class UpchanSumBeams(Block):
                         self.update_stats({'nwindow': self.stats['nwindow'] + self.windows_per_gulp,
                                            'last_end_sample': this_gulp_time + self.ntime_gulp})
                     osp, ospan = ospan, None
-                    self._enqueued(streaming, pending, retire, osp, held, stage)
+                    self._enqueued(streaming, inflight, osp, held, stage)
                 finally:
                     if ospan is not None:
                         ospan.close()
@@ -243,6 +203,6 @@ class UpchanSumBeams(Block):
                 prev_time = curr_time
                 self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
         finally:
-            retire(0)                           # every call in flight is complete (and every output span committed) first
+            inflight.retire(0)                  # every call in flight is complete (and every output span committed) first
             if oseq is not None:
                 oseq.end()
