@@ -631,8 +631,55 @@ class HipBackend:
     def cdedisp_sync(self):
         ffi.call("xengCdedispSync")
 
+    # ---- dirty images of the fine-channel visibilities (UpchanImage; include/xeng.h "Dirty images of the fine-channel
+    # visibilities"): a context of its own, its kernel on the beamformer's stream
+    def image_initialize(self, gpu, nstand, nfine, nfavg, npix):
+        return self._lib.xengImageInitialize(int(gpu), int(nstand), int(nfine), int(nfavg), int(npix))
+
+    def image_set_geometry(self, tau, freq):
+        """tau: host float64 [npix][nstand] seconds, freq: host float64 [nfine] Hz, both C-contiguous.  Waits for the context's work
+        in flight."""
+        import numpy as np
+        for a in (tau, freq):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags['C_CONTIGUOUS']):
+                raise TypeError("image_set_geometry: the tables must be C-contiguous float64 arrays")
+        pd = ctypes.POINTER(ctypes.c_double)
+        return self._lib.xengImageSetGeometry(tau.ctypes.data_as(pd), freq.ctypes.data_as(pd))
+
+    def image_set_weights(self, weights, autos):
+        """weights: host float32 [nstand], finite and >= 0.  Waits for the context's work in flight; holds from the next run."""
+        import numpy as np
+        if not (isinstance(weights, np.ndarray) and weights.dtype == np.float32 and weights.flags['C_CONTIGUOUS']):
+            raise TypeError("image_set_weights: the weights must be a C-contiguous float32 array")
+        return self._lib.xengImageSetWeights(_host_floats(weights), int(bool(autos)))
+
+    def image_run(self, vis_arr, out_arr):
+        """Enqueue only: cf32 [nfine][nstand][2][nstand][2] in, f32 [nfine / nfavg][4][npix] out; image_mark / wait cover it."""
+        return self._enq.xengImageRun(vis_arr.ptr, out_arr.ptr)
+
+    def image_info(self):
+        """(channel groups, pixels per work-group, LDS bytes per work-group, norm)"""
+        g, t, l, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+        ffi.call("xengImageGetInfo", ctypes.byref(g), ctypes.byref(t), ctypes.byref(l), ctypes.byref(n))
+        return g.value, t.value, l.value, n.value
+
+    def image_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengImageCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def image_mark(self):
+        return self._mark("xengImageMark")
+
+    def image_wait(self, ticket):
+        self._wait("xengImageTicketDone", "xengImageWait", ticket)
+
+    def image_sync(self):
+        ffi.call("xengImageSync")
+
     # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold, Period,
-    # Cdedisp)
+    # Cdedisp, Image)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

@@ -130,6 +130,10 @@ SYMBOLS = {
     "xengCdedispRun": [_vp, _vp, _pi], "xengCdedispReset": [], "xengCdedispGetInfo": [_pi, _pi, _pll, _pll], "xengCdedispCheckGuards": [_pi],
     "xengCdedispMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCdedispWait": [ctypes.c_ulonglong],
     "xengCdedispTicketDone": [ctypes.c_ulonglong, _pi], "xengCdedispSync": [], "xengCdedispDestroy": [],
+    "xengImageInitialize": [_i, _i, _i, _i, _i], "xengImageGetInfo": [_pi, _pi, _pi, ctypes.POINTER(ctypes.c_double)],
+    "xengImageSetGeometry": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], "xengImageSetWeights": [ctypes.POINTER(ctypes.c_float), _i],
+    "xengImageRun": [_vp, _vp], "xengImageCheckGuards": [_pi], "xengImageMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengImageWait": [ctypes.c_ulonglong],
+    "xengImageTicketDone": [ctypes.c_ulonglong, _pi], "xengImageSync": [], "xengImageDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -182,6 +186,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengFoldRun", "xengFoldReset", "xengFoldMark", "xengFoldTicketDone",
                 "xengPeriodRun", "xengPeriodReset", "xengPeriodMark", "xengPeriodTicketDone",
                 "xengCdedispRun", "xengCdedispReset", "xengCdedispMark", "xengCdedispTicketDone",
+                "xengImageRun", "xengImageMark", "xengImageTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

@@ -928,6 +928,63 @@ int xengCdedispTicketDone(unsigned long long ticket, int *done);
 int xengCdedispSync(void);
 int xengCdedispDestroy(void);
 
+/* ---------------------------------------------------------------- Dirty images of the fine-channel visibilities
+ * UpchanImage (no reference counterpart: the reference writes its visibilities to disk): the direct Fourier sum of UpchanCorr's
+ * matrix over a list of directions -- the matrix beamformed onto every pixel, exact for a non-coplanar array, no grid and no FFT.
+ * The library knows nothing of the array or the sky: blocks/imaging.py builds the delays.  A context of its own, independent of
+ * all others, whose kernel runs on the beamformer's stream -- rings declared 'beam' cover it, and xengBeamformSync waits for it
+ * too.  One kernel per call (csrc/image_kernels.h).
+ *   vis      cf32[nfine][nstand][2][nstand][2], the output of xengUpchanCorrDump unchanged (the full Hermitian matrix, two
+ *            polarisations per stand), V[c][s p][t q]; 16-byte aligned; never written
+ *   freq     f64[nfine], Hz;  tau f64[npix][nstand], seconds;  w f32[nstand], finite and >= 0 (after Initialize: all 1);  autos
+ *            (after Initialize: 0);  nfavg, which divides nfine: channel group g is the channels [g*nfavg, (g+1)*nfavg)
+ *   out      f32[nfine/nfavg][4][npix], the words [XX, YY, Re(XY), Im(XY)] (the four-word convention of the power beams);
+ *            16-byte aligned; nothing past it is written
+ *              I_pq[g][x] = norm * sum_{c in group g, ascending} sum_{s,t} conj(b_s(c,x)) * V[c][s p][t q] * b_t(c,x)
+ *              b_s(c,x)   = w_s * exp(-2 pi i * frac(freq[c] * tau[x][s]))
+ *            XX = Re I_00, YY = Re I_11 (their imaginary parts are rounding noise and are dropped), XY = I_01.
+ *   phase    freq*tau and its reduction to a fraction of a turn in [-1/2, 1/2] (the product rounded, minus its nearest integer)
+ *            are fp64 on the device; the sine and cosine of the fraction and everything after them are fp32.
+ *   autos    with autos = 0 the 2x2 blocks s = t read as zero: an exact omission, not a subtraction.
+ *   flags    a stand with w_s = 0 is NOT READ: its rows and columns count as zero even where they hold NaN or Inf (a select on
+ *            the load, not a multiply).
+ *   norm     1 / (nfavg * sum_{s,t} w_s w_t), over s != t with autos = 0: float64 on the host, rounded once and applied as one
+ *            final multiply.  A unit point source at a pixel (V = a a^H, a_s = exp(-2 pi i freq tau[x0][s]), both
+ *            polarisations) reads 1 there.
+ * Every output word is a fixed function of vis and the tables: no atomics, one owner per word, one summation order (the stands s
+ * in ascending order on f32-input MFMAs, two per instruction; the stands t in tiles of 32, a wave's tiles in ascending order,
+ * the channels of the group in ascending order; one fixed tree over the 32 columns of a tile; the four waves in order).  It
+ * does not depend on what else runs on the GPU, nor on which other pixels are in the list: the image of a sub-list equals the
+ * corresponding words of the full image bit for bit.  A NaN in the visibilities of a stand that is read stays within its channel
+ * group.
+ * The state (freq, tau, w) sits between two guard bands of 64 KiB.  SetGeometry and SetWeights wait for the context's work in
+ * flight: a call between two Runs applies to the later one only.
+ * Rejected at Initialize, before any device is touched: a non-positive size, nfavg not dividing nfine, nstand >
+ * XENG_IMAGE_MAX_NSTAND (the steering tile of 32 pixels lives in LDS), more than 65535 channel groups, npix > 2^24, a delay table
+ * above XENG_IMAGE_MAX_STATE_BYTES.  Rejected by SetGeometry: NULL, a non-finite word.  Rejected by SetWeights: NULL, a negative
+ * or non-finite weight, weights that leave no pair (all zero; with autos = 0, fewer than two stands).  Rejected by Run without a
+ * launch: NULL or misaligned pointers (INVALID_ARGUMENT); no geometry yet, or a single stand with the initial autos = 0
+ * (INVALID_STATE).  Every call without a context: XENG_STATUS_INVALID_STATE. */
+#define XENG_IMAGE_MAX_NSTAND 512
+#define XENG_IMAGE_MAX_STATE_BYTES (1LL << 31)
+int xengImageInitialize(int gpu, int nstand, int nfine, int nfavg, int npix);
+/* the live context's number of channel groups, the pixels per work-group, the LDS bytes of a work-group and norm (float64) */
+int xengImageGetInfo(int *ngroup, int *pixel_tile, int *lds_bytes, double *norm);
+/* tau: f64[npix][nstand] seconds, freq: f64[nfine] Hz, on the host.  Waits for the context's work in flight, uploads both. */
+int xengImageSetGeometry(const double *tau, const double *freq);
+/* w: f32[nstand] on the host.  Waits for the context's work in flight; holds from the next Run. */
+int xengImageSetWeights(const float *w, int autos);
+/* enqueue only: one integration */
+int xengImageRun(const void *vis_dev, void *out_dev);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengImageCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengImageMark(unsigned long long *ticket);
+int xengImageWait(unsigned long long ticket);
+int xengImageTicketDone(unsigned long long ticket, int *done);
+int xengImageSync(void);
+int xengImageDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
