@@ -678,8 +678,60 @@ class HipBackend:
     def image_sync(self):
         ffi.call("xengImageSync")
 
+    # ---- per-stand gains from the fine-channel visibilities (UpchanGainCal; include/xeng.h "Per-stand gains from the fine-channel
+    # visibilities"): a context of its own, its kernel on the beamformer's stream
+    def gaincal_initialize(self, gpu, nstand, nfine, nsrc):
+        return self._lib.xengGaincalInitialize(int(gpu), int(nstand), int(nfine), int(nsrc))
+
+    def gaincal_set_model(self, tau, freq, flux):
+        """tau: host float64 [nsrc][nstand] seconds, freq: host float64 [nfine] Hz, flux: host float32 [nfine][nsrc], all
+        C-contiguous.  Waits for the context's work in flight; forgets the warm start."""
+        import numpy as np
+        for a, t in ((tau, np.float64), (freq, np.float64), (flux, np.float32)):
+            if not (isinstance(a, np.ndarray) and a.dtype == t and a.flags['C_CONTIGUOUS']):
+                raise TypeError("gaincal_set_model: the tables must be C-contiguous float64, float64 and float32 arrays")
+        pd = ctypes.POINTER(ctypes.c_double)
+        return self._lib.xengGaincalSetModel(tau.ctypes.data_as(pd), freq.ctypes.data_as(pd), _host_floats(flux))
+
+    def gaincal_set_weights(self, weights, refant):
+        """weights: host float32 [nstand], finite and >= 0, that of `refant` > 0.  Waits for the context's work in flight; holds from
+        the next run; forgets the warm start."""
+        import numpy as np
+        if not (isinstance(weights, np.ndarray) and weights.dtype == np.float32 and weights.flags['C_CONTIGUOUS']):
+            raise TypeError("gaincal_set_weights: the weights must be a C-contiguous float32 array")
+        return self._lib.xengGaincalSetWeights(_host_floats(weights), int(refant))
+
+    def gaincal_set_solver(self, niter, tol):
+        return self._lib.xengGaincalSetSolver(int(niter), float(tol))
+
+    def gaincal_run(self, vis_arr, out_arr, stats_offset, warm):
+        """Enqueue only: cf32 [nfine][nstand][2][nstand][2] in; cf32 [nfine][2][nstand] gains at the start of out_arr and f32
+        [nfine][2][4] stats `stats_offset` bytes into it; gaincal_mark / wait cover it."""
+        return self._enq.xengGaincalRun(vis_arr.ptr, out_arr.ptr, out_arr.ptr + int(stats_offset), int(bool(warm)))
+
+    def gaincal_info(self):
+        """(LDS bytes per work-group, niter, tol, the reference stand)"""
+        l, n, t, r = ctypes.c_int(), ctypes.c_int(), ctypes.c_double(), ctypes.c_int()
+        ffi.call("xengGaincalGetInfo", ctypes.byref(l), ctypes.byref(n), ctypes.byref(t), ctypes.byref(r))
+        return l.value, n.value, t.value, r.value
+
+    def gaincal_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengGaincalCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def gaincal_mark(self):
+        return self._mark("xengGaincalMark")
+
+    def gaincal_wait(self, ticket):
+        self._wait("xengGaincalTicketDone", "xengGaincalWait", ticket)
+
+    def gaincal_sync(self):
+        ffi.call("xengGaincalSync")
+
     # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold, Period,
-    # Cdedisp, Image)
+    # Cdedisp, Image, Gaincal)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

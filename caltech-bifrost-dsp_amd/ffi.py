@@ -134,6 +134,11 @@ SYMBOLS = {
     "xengImageSetGeometry": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], "xengImageSetWeights": [ctypes.POINTER(ctypes.c_float), _i],
     "xengImageRun": [_vp, _vp], "xengImageCheckGuards": [_pi], "xengImageMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengImageWait": [ctypes.c_ulonglong],
     "xengImageTicketDone": [ctypes.c_ulonglong, _pi], "xengImageSync": [], "xengImageDestroy": [],
+    "xengGaincalInitialize": [_i, _i, _i, _i], "xengGaincalGetInfo": [_pi, _pi, ctypes.POINTER(ctypes.c_double), _pi],
+    "xengGaincalSetModel": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float)],
+    "xengGaincalSetWeights": [ctypes.POINTER(ctypes.c_float), _i], "xengGaincalSetSolver": [_i, ctypes.c_double], "xengGaincalRun": [_vp, _vp, _vp, _i],
+    "xengGaincalCheckGuards": [_pi], "xengGaincalMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengGaincalWait": [ctypes.c_ulonglong],
+    "xengGaincalTicketDone": [ctypes.c_ulonglong, _pi], "xengGaincalSync": [], "xengGaincalDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -187,6 +192,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengPeriodRun", "xengPeriodReset", "xengPeriodMark", "xengPeriodTicketDone",
                 "xengCdedispRun", "xengCdedispReset", "xengCdedispMark", "xengCdedispTicketDone",
                 "xengImageRun", "xengImageMark", "xengImageTicketDone",
+                "xengGaincalRun", "xengGaincalMark", "xengGaincalTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

@@ -985,6 +985,77 @@ int xengImageTicketDone(unsigned long long ticket, int *done);
 int xengImageSync(void);
 int xengImageDestroy(void);
 
+/* ---------------------------------------------------------------- Per-stand gains from the fine-channel visibilities
+ * UpchanGainCal (no reference counterpart: the reference leaves calibration to offline packages that read its visibility files):
+ * one complex gain per (fine channel, polarisation, stand) from UpchanCorr's matrix and a point-source sky model, by StEFCal
+ * (Salvini & Wijnholds 2014).  The library knows nothing of the array or the sky: blocks/imaging.py builds the delays of the
+ * sources' directions.  A context of its own, independent of all others, whose kernel runs on the beamformer's stream -- rings
+ * declared 'beam' cover it, and xengBeamformSync waits for it too.  One kernel per call, the whole iteration inside it
+ * (csrc/gaincal_kernels.h).
+ *   vis      cf32[nfine][nstand][2][nstand][2], the output of xengUpchanCorrDump unchanged; 16-byte aligned; never written.  Per
+ *            fine channel c and polarisation p only the pp block is used, and it is read along its rows:
+ *              X[s][t] = conj(vis[c][t p][s p]),   which is V[c][s p][t p] of a Hermitian matrix (UpchanCorr's is, bit for bit)
+ *            under the conjugation convention by which a unit point source (V = a a^H) images to 1 with xengImage*.
+ *   model    tau f64[nsrc][nstand] seconds, freq f64[nfine] Hz, flux F f32[nfine][nsrc], finite and >= 0:
+ *              M_c[s][t] = sum_k F[c][k] * a_ks * conj(a_kt),   a_ks = exp(-2 pi i * frac(freq[c] * tau[k][s]))
+ *            freq*tau and its reduction to a fraction of a turn in [-1/2, 1/2] are fp64 on the device; sincospif of the fraction and
+ *            everything after it are fp32.  The matrix M is never formed.
+ *   weights  w f32[nstand], finite and >= 0.  A stand with w_s = 0 is NOT READ (a select on the load: it may hold NaN or Inf) and
+ *            its gain is written as 0 + 0i.  The autos s = t are never read.
+ *   solver   from g = 1 at every stand of weight > 0 (or the warm start below), for i = 1 .. niter:
+ *              N_s = sum_k F_k conj(a_ks) * sum_{t != s} X[s][t] * (w_t g_t a_kt)
+ *              D_s = sum_{t != s} w_t |g_t|^2 |M_c[s][t]|^2,  by the Gram route (the one route, in this summation order):
+ *                    G[k][k'] = sum_t w_t |g_t|^2 conj(a_kt) a_k't                      over all t in ascending order
+ *                    D_s = sum_k Re( z_k * sum_k' G[k][k'] conj(z_k') ) - w_s |g_s|^2 (sum_k F_k)^2,    z_k = F_k a_ks,
+ *                    k and k' ascending, the t = s term removed by one final subtraction
+ *              g_s <- N_s / D_s, and g_s = 0 where D_s is not > 0.
+ *            On even i, delta = ||g_i - g_(i-1)|| / ||g_i|| over the stands of weight > 0.  With tol > 0 and delta <= tol the loop
+ *            stops there (converged); otherwise g_i <- (g_i + g_(i-1)) / 2.  With tol = 0 exactly niter iterations run.
+ *   phase    after the loop every gain of the (channel, pol) is multiplied by conj(g_ref) / |g_ref| of the reference stand refant
+ *            (left as they are where |g_ref| is not > 0).
+ *   gains    cf32[nfine][2][nstand]; 8-byte aligned
+ *   stats    f32[nfine][2][4] = {iterations run, the last delta (-1: none was formed), stands solved (weight > 0 and a gain that is
+ *            not 0), converged 0/1}
+ *   warm     the context keeps, per (channel, pol), the last solution before its phase reference and whether it was converged and
+ *            finite.  Run(.., warm = 1) starts from it where it was, else from 1.  A Run with niter = 0 returns its start, phase
+ *            referenced, and leaves the kept solution alone.  SetModel, SetWeights and Initialize forget it.
+ * Every output word is a fixed function of its own channel's block of vis, the model and the weights: no atomics, one owner per
+ * word, one summation order (N: the stands t in ascending order on f32-input MFMAs, two per instruction, then the sources in
+ * ascending order per half of the tile's rows, the halves added; delta: a thread's stands, one fixed tree over the wave, the four
+ * waves in order).  It does not depend on what else runs on the GPU nor on which other channels are in the call.  A NaN in the
+ * visibilities of a stand that is read stays within its (channel, pol).
+ * The state sits between two guard bands of 64 KiB.  SetModel and SetWeights wait for the context's work in flight: a call
+ * between two Runs applies to the later one only; SetSolver sets the arguments of the Runs after it.
+ * Rejected with INVALID_ARGUMENT at the call that sees it: a non-positive size, nsrc > XENG_GAINCAL_MAX_NSRC, nstand >
+ * XENG_GAINCAL_MAX_NSTAND, more than 65535 channels (Initialize); NULL, a non-finite word, a negative flux (SetModel); NULL, a
+ * negative or non-finite weight, refant out of range or of weight 0 (SetWeights); niter outside [0, XENG_GAINCAL_MAX_NITER], a
+ * negative or non-finite tol (SetSolver); NULL or misaligned pointers (Run).  Run before SetModel or before SetWeights, and every
+ * call without a context: XENG_STATUS_INVALID_STATE. */
+#define XENG_GAINCAL_MAX_NSRC 32
+#define XENG_GAINCAL_MAX_NSTAND 512
+#define XENG_GAINCAL_MAX_NITER 1024
+#define XENG_GAINCAL_DEFAULT_NITER 60
+#define XENG_GAINCAL_DEFAULT_TOL 1e-5
+int xengGaincalInitialize(int gpu, int nstand, int nfine, int nsrc);
+/* the LDS bytes of a work-group, the solver's niter and tol, the reference stand */
+int xengGaincalGetInfo(int *lds_bytes, int *niter, double *tol, int *refant);
+/* tau: f64[nsrc][nstand] seconds, freq: f64[nfine] Hz, flux: f32[nfine][nsrc], on the host.  Waits for the context's work in flight. */
+int xengGaincalSetModel(const double *tau, const double *freq, const float *flux);
+/* w: f32[nstand] on the host.  Waits for the context's work in flight; holds from the next Run. */
+int xengGaincalSetWeights(const float *w, int refant);
+/* after Initialize: XENG_GAINCAL_DEFAULT_NITER, XENG_GAINCAL_DEFAULT_TOL */
+int xengGaincalSetSolver(int niter, double tol);
+/* enqueue only: one integration */
+int xengGaincalRun(const void *vis_dev, void *gains_dev, void *stats_dev, int warm);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengGaincalCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengGaincalMark(unsigned long long *ticket);
+int xengGaincalWait(unsigned long long ticket);
+int xengGaincalTicketDone(unsigned long long ticket, int *done);
+int xengGaincalSync(void);
+int xengGaincalDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
