@@ -730,8 +730,59 @@ class HipBackend:
     def gaincal_sync(self):
         ffi.call("xengGaincalSync")
 
+    # ---- calibrated, source-subtracted visibilities (UpchanCalApply; include/xeng.h "Calibrated, source-subtracted visibilities"): a
+    # context of its own, its kernels on the beamformer's stream
+    def calapply_initialize(self, gpu, nstand, nfine, nsrc):
+        return self._lib.xengCalapplyInitialize(int(gpu), int(nstand), int(nfine), int(nsrc))
+
+    def calapply_set_model(self, tau, freq, flux):
+        """tau: host float64 [nsrc][nstand] seconds, freq: host float64 [nfine] Hz, flux: host float32 [nfine][nsrc], all
+        C-contiguous; tau and flux may be None in a context without sources.  Waits for the context's work in flight."""
+        import numpy as np
+        for a, t, optional in ((tau, np.float64, True), (freq, np.float64, False), (flux, np.float32, True)):
+            if a is None and optional:
+                continue
+            if not (isinstance(a, np.ndarray) and a.dtype == t and a.flags['C_CONTIGUOUS']):
+                raise TypeError("calapply_set_model: the tables must be C-contiguous float64, float64 and float32 arrays")
+        pd = ctypes.POINTER(ctypes.c_double)
+        return self._lib.xengCalapplySetModel(None if tau is None or not tau.size else tau.ctypes.data_as(pd), freq.ctypes.data_as(pd),
+                                              None if flux is None or not flux.size else _host_floats(flux))
+
+    def calapply_set_factors(self, h):
+        """h: host complex64 [nfine][2][nstand], finite, 0 where a (stand, polarisation) is left out.  Waits for the context's work
+        in flight; holds from the next run."""
+        import numpy as np
+        if not (isinstance(h, np.ndarray) and h.dtype == np.complex64 and h.flags['C_CONTIGUOUS']):
+            raise TypeError("calapply_set_factors: the factors must be a C-contiguous complex64 array")
+        return self._lib.xengCalapplySetFactors(h.ctypes.data_as(ctypes.c_void_p))
+
+    def calapply_run(self, vis_arr, out_arr):
+        """Enqueue only: cf32 [nfine][nstand][2][nstand][2] in and out; calapply_mark / wait cover it."""
+        return self._enq.xengCalapplyRun(vis_arr.ptr, out_arr.ptr)
+
+    def calapply_info(self):
+        """(tiles of 32 stands per side, work-groups per run, LDS bytes per work-group, bytes of a span)"""
+        t, g, l, b = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+        ffi.call("xengCalapplyGetInfo", ctypes.byref(t), ctypes.byref(g), ctypes.byref(l), ctypes.byref(b))
+        return t.value, g.value, l.value, b.value
+
+    def calapply_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengCalapplyCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def calapply_mark(self):
+        return self._mark("xengCalapplyMark")
+
+    def calapply_wait(self, ticket):
+        self._wait("xengCalapplyTicketDone", "xengCalapplyWait", ticket)
+
+    def calapply_sync(self):
+        ffi.call("xengCalapplySync")
+
     # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold, Period,
-    # Cdedisp, Image, Gaincal)
+    # Cdedisp, Image, Gaincal, Calapply)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

@@ -139,6 +139,11 @@ SYMBOLS = {
     "xengGaincalSetWeights": [ctypes.POINTER(ctypes.c_float), _i], "xengGaincalSetSolver": [_i, ctypes.c_double], "xengGaincalRun": [_vp, _vp, _vp, _i],
     "xengGaincalCheckGuards": [_pi], "xengGaincalMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengGaincalWait": [ctypes.c_ulonglong],
     "xengGaincalTicketDone": [ctypes.c_ulonglong, _pi], "xengGaincalSync": [], "xengGaincalDestroy": [],
+    "xengCalapplyInitialize": [_i, _i, _i, _i], "xengCalapplyGetInfo": [_pi, _pi, _pi, _pll],
+    "xengCalapplySetModel": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float)],
+    "xengCalapplySetFactors": [_vp], "xengCalapplyRun": [_vp, _vp], "xengCalapplyCheckGuards": [_pi],
+    "xengCalapplyMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCalapplyWait": [ctypes.c_ulonglong],
+    "xengCalapplyTicketDone": [ctypes.c_ulonglong, _pi], "xengCalapplySync": [], "xengCalapplyDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -193,6 +198,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengCdedispRun", "xengCdedispReset", "xengCdedispMark", "xengCdedispTicketDone",
                 "xengImageRun", "xengImageMark", "xengImageTicketDone",
                 "xengGaincalRun", "xengGaincalMark", "xengGaincalTicketDone",
+                "xengCalapplyRun", "xengCalapplyMark", "xengCalapplyTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

@@ -1056,6 +1056,68 @@ int xengGaincalTicketDone(unsigned long long ticket, int *done);
 int xengGaincalSync(void);
 int xengGaincalDestroy(void);
 
+/* ---------------------------------------------------------------- Calibrated, source-subtracted visibilities
+ * UpchanCalApply (no reference counterpart: the reference leaves calibration and source subtraction to offline packages): UpchanCorr's
+ * matrix with a gain solution applied and a point-source model taken out, written as a matrix of the same format, so that
+ * xengImage* and a second xengGaincal* (a residual solve) read it unchanged.  The library knows nothing of the array or the sky:
+ * blocks/imaging.py builds the delays, blocks/calibration.py (inverse_gains) the factors.  A context of its own, independent of
+ * all others, whose kernels run on the beamformer's stream -- rings declared 'beam' cover it, and xengBeamformSync waits for it
+ * too.  One kernel per Run (csrc/calapply_kernels.h), one more per SetModel.
+ *   vis      cf32[nfine][nstand][2][nstand][2], the output of xengUpchanCorrDump unchanged, V[c][s p][t q]; 16-byte aligned; never
+ *            written.  With row i = 2 s + p and column j = 2 t + q only the words i >= j are read: the upper triangle may hold
+ *            anything.
+ *   model    tau f64[nsrc][nstand] seconds, freq f64[nfine] Hz, flux F f32[nfine][nsrc], finite and >= 0, 0 <= nsrc <=
+ *            XENG_CALAPPLY_MAX_NSRC:
+ *              M_c[s][t] = sum_k F[c][k] * a_ks * conj(a_kt),   a_ks = exp(-2 pi i * frac(freq[c] * tau[k][s]))
+ *            freq*tau and its reduction to a fraction of a turn in [-1/2, 1/2] are fp64 on the device; sincospif of the fraction and
+ *            everything after it are fp32 (the convention of xengImage* and xengGaincal*).  The factors a are formed once per
+ *            SetModel, not once per Run: the same words.  z_ks = F_k * a_ks is one fp32 multiply per part; per word of M and per part
+ *            one chain of fused multiply-adds on f32-input MFMAs, the sources two per instruction in ascending order: of each pair
+ *            first Re z Re a (k even, k odd), then Im z Im a (k even, k odd) for the real part; Im z Re a, then -Re z Im a for the
+ *            imaginary part.  With nsrc = 0 there is no model (calibration only): tau and flux may be NULL and Run needs no SetModel.
+ *   factors  h cf32[nfine][2][nstand], finite; after Initialize every factor is 1.  h_i of input i = 2 s + p is h[c][p][s].  h = 0
+ *            marks a (stand, polarisation) that is left out.  The device divides nothing: the host forms h = 1 / g in float64
+ *            (blocks/calibration.py inverse_gains) and rounds once.
+ *   out      cf32 in vis's layout; 16-byte aligned; nothing past it is written.
+ *              i > j:  out[c][i][j] = (h_i * conj(h_j)) * V[c][i][j] - delta_pq * M_c[s][t]
+ *                      w = h_i conj(h_j):  Re w = fma(Re h_i, Re h_j, Im h_i Im h_j),  Im w = fma(Im h_i, Re h_j, -(Re h_i Im h_j))
+ *                      y = w V          :  Re y = fma(Re w, Re V, -(Im w Im V)),       Im y = fma(Re w, Im V, Im w Re V)
+ *                      then M is subtracted, part by part, where p = q.  No other contraction is taken.
+ *              i = j:  the real part of the same expression; the imaginary part is written as +0.
+ *              i < j:  the conjugate of out[c][j][i]: the same word with the sign of its imaginary part turned, not computed again
+ *                      (xengUpchanCorrDump's convention), so the output is Hermitian bit for bit.
+ *            With unit factors and nsrc = 0 the lower triangle is the input bit for bit (up to the sign of a zero).
+ *   flags    a word whose h_i or h_j is 0 is NOT READ (a select on the load: it may hold NaN or Inf) and is written as +0 + 0i,
+ *            in both triangles.  A NaN in a word that is read stays in that word and its mirror.
+ * Every output word is a fixed function of its own input word, the two factors and the model: one owner per Hermitian pair, no
+ * atomics, one summation order.  It does not depend on nstand, on which other channels are in the call nor on what else runs on
+ * the GPU.
+ * The state (freq, tau, a, h, flux) sits between two guard bands of 64 KiB.  SetModel and SetFactors wait for the context's work in
+ * flight: a call between two Runs applies to the later one only.
+ * Rejected with INVALID_ARGUMENT at the call that sees it: a non-positive nstand or nfine, a negative nsrc, nsrc >
+ * XENG_CALAPPLY_MAX_NSRC, nstand > XENG_CALAPPLY_MAX_NSTAND, more than 65535 channels (Initialize); NULL frequencies, with nsrc > 0
+ * NULL delays or fluxes, a non-finite word, a negative flux (SetModel); NULL, a non-finite word (SetFactors); NULL or misaligned
+ * pointers (Run).  Run before SetModel with nsrc > 0, and every call without a context: XENG_STATUS_INVALID_STATE. */
+#define XENG_CALAPPLY_MAX_NSRC 32
+#define XENG_CALAPPLY_MAX_NSTAND 512
+int xengCalapplyInitialize(int gpu, int nstand, int nfine, int nsrc);
+/* the tiles of 32 stands per side, the work-groups of a Run, the LDS bytes of a work-group, the bytes of a span (input = output) */
+int xengCalapplyGetInfo(int *ntile, int *ngroup, int *lds_bytes, long long *span_bytes);
+/* tau: f64[nsrc][nstand] seconds, freq: f64[nfine] Hz, flux: f32[nfine][nsrc], on the host.  Waits for the context's work in flight. */
+int xengCalapplySetModel(const double *tau, const double *freq, const float *flux);
+/* h: cf32[nfine][2][nstand] on the host.  Waits for the context's work in flight; holds from the next Run. */
+int xengCalapplySetFactors(const void *h);
+/* enqueue only: one integration */
+int xengCalapplyRun(const void *vis_dev, void *out_dev);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengCalapplyCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengCalapplyMark(unsigned long long *ticket);
+int xengCalapplyWait(unsigned long long ticket);
+int xengCalapplyTicketDone(unsigned long long ticket, int *done);
+int xengCalapplySync(void);
+int xengCalapplyDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
