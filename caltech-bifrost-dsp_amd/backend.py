@@ -781,8 +781,70 @@ class HipBackend:
     def calapply_sync(self):
         ffi.call("xengCalapplySync")
 
+    # ---- Hogbom CLEAN of the dirty images (UpchanClean; include/xeng.h "Hogbom CLEAN of the dirty images"): a context of its own,
+    # its kernel on the beamformer's stream
+    def clean_initialize(self, gpu, nstand, nfine, nfavg, npix, niter_max):
+        return self._lib.xengCleanInitialize(int(gpu), int(nstand), int(nfine), int(nfavg), int(npix), int(niter_max))
+
+    def clean_set_geometry(self, tau, freq):
+        """tau: host float64 [npix][nstand] seconds, freq: host float64 [nfine] Hz, both C-contiguous.  Waits for the context's work
+        in flight."""
+        import numpy as np
+        for a in (tau, freq):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags['C_CONTIGUOUS']):
+                raise TypeError("clean_set_geometry: the tables must be C-contiguous float64 arrays")
+        pd = ctypes.POINTER(ctypes.c_double)
+        return self._lib.xengCleanSetGeometry(tau.ctypes.data_as(pd), freq.ctypes.data_as(pd))
+
+    def clean_set_weights(self, weights, autos):
+        """weights: host float32 [nstand], finite and >= 0.  Waits for the context's work in flight; holds from the next run."""
+        import numpy as np
+        if not (isinstance(weights, np.ndarray) and weights.dtype == np.float32 and weights.flags['C_CONTIGUOUS']):
+            raise TypeError("clean_set_weights: the weights must be a C-contiguous float32 array")
+        return self._lib.xengCleanSetWeights(_host_floats(weights), int(bool(autos)))
+
+    def clean_set_window(self, mask):
+        """mask: host uint8 [npix] (non-zero: a component may sit there), or None for every pixel.  Waits for the context's work in
+        flight; holds from the next run."""
+        import numpy as np
+        if mask is None:
+            return self._lib.xengCleanSetWindow(None)
+        if not (isinstance(mask, np.ndarray) and mask.dtype == np.uint8 and mask.flags['C_CONTIGUOUS']):
+            raise TypeError("clean_set_window: the window must be a C-contiguous uint8 array")
+        return self._lib.xengCleanSetWindow(mask.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
+
+    def clean_set_control(self, niter, gain, threshold, fraction):
+        return self._lib.xengCleanSetControl(int(niter), float(gain), float(threshold), float(fraction))
+
+    def clean_run(self, image_arr, out_arr):
+        """Enqueue only: f32 [ngroup][4][npix] in; the residual, the component records and the stats out (clean_info gives the
+        layout); clean_mark / wait cover it."""
+        return self._enq.xengCleanRun(image_arr.ptr, out_arr.ptr)
+
+    def clean_info(self):
+        """(channel groups, pixels per work-group, comp_offset, stats_offset, span_bytes, norm)"""
+        g, t, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+        c, s, b = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong()
+        ffi.call("xengCleanGetInfo", ctypes.byref(g), ctypes.byref(t), ctypes.byref(c), ctypes.byref(s), ctypes.byref(b), ctypes.byref(n))
+        return g.value, t.value, c.value, s.value, b.value, n.value
+
+    def clean_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengCleanCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def clean_mark(self):
+        return self._mark("xengCleanMark")
+
+    def clean_wait(self, ticket):
+        self._wait("xengCleanTicketDone", "xengCleanWait", ticket)
+
+    def clean_sync(self):
+        ffi.call("xengCleanSync")
+
     # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold, Period,
-    # Cdedisp, Image, Gaincal, Calapply)
+    # Cdedisp, Image, Gaincal, Calapply, Clean)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

@@ -77,3 +77,90 @@ def stokes_i(image):
     """I = XX + YY of an image f32 [...][4][npix] -> [...][npix]."""
     image = np.asarray(image)
     return image[..., 0, :] + image[..., 1, :]
+
+
+# ---- Hogbom CLEAN of the dirty images (UpchanClean; include/xeng.h "Hogbom CLEAN of the dirty images")
+CLEAN_COMPONENT = np.dtype([('pixel', '<i4'), ('I', '<f4'), ('C', '<f4', (4,)), ('pad', '<u4', (2,))])      # 32 bytes: one record
+CLEAN_STATS = np.dtype([('ncomp', '<i4'), ('reason', '<i4'), ('peak', '<f4'), ('pad', '<u4')])              # 16 bytes per channel group
+
+
+def psf(freq, tau, w, autos, nfavg, x0):
+    """The exact point-spread function of the direct Fourier sum: the response of UpchanImage, at every pixel of the list and in
+    every channel group, to a unit point source at list pixel x0; float64 [nfine / nfavg][npix], the same for all four words.
+      PSF_g(x, x0) = norm * sum_{c in g} ( |sum_s w_s exp(2 pi i (fr_c(x,s) - fr_c(x0,s)))|^2 - D ),  D = sum w_s^2 without autos, else 0
+    with fr_c(x,s) the product freq[c] tau[x][s] minus its nearest integer; PSF_g(x0, x0) = 1."""
+    freq, tau = np.asarray(freq, np.float64).reshape(-1), np.asarray(tau, np.float64)
+    w = np.asarray(w, np.float64).reshape(-1)
+    if tau.ndim != 2 or tau.shape[1] != w.size or not 0 <= int(x0) < tau.shape[0]:
+        raise ValueError("psf: delays [npix][nstand] %r, %d weights, pixel %r" % (tau.shape, w.size, x0))
+    norm = image_norm(w, autos, nfavg)
+    if freq.size % int(nfavg):
+        raise ValueError("psf: nfavg %d does not divide %d channels" % (nfavg, freq.size))
+    turns = freq[:, None, None] * tau[None]
+    fr = turns - np.rint(turns)
+    S = (w * np.exp(2j * np.pi * (fr - fr[:, int(x0):int(x0) + 1, :]))).sum(axis=2)
+    p = S.real ** 2 + S.imag ** 2 - (0.0 if autos else (w * w).sum())
+    return norm * p.reshape(freq.size // int(nfavg), int(nfavg), -1).sum(axis=1)
+
+
+def clean_layout(ngroup, niter, npix):
+    """(comp_offset, stats_offset, span_bytes) of UpchanClean's span"""
+    comp = 16 * int(ngroup) * int(npix)
+    stats = comp + 32 * int(ngroup) * int(niter)
+    return comp, stats, stats + 16 * int(ngroup)
+
+
+def clean_components(span, ngroup, niter, npix):
+    """One span of UpchanClean (any buffer of its bytes) taken apart, without a copy: (components CLEAN_COMPONENT [ngroup][niter],
+    stats CLEAN_STATS [ngroup], residual f32 [ngroup][4][npix]).  stats['ncomp'][g] records of group g are filled; the rest hold
+    pixel -1."""
+    raw = np.asarray(span).reshape(-1).view(np.uint8)
+    comp, stats, total = clean_layout(ngroup, niter, npix)
+    if raw.size < total:
+        raise ValueError("clean_components: %d bytes, a span of %d groups, %d iterations and %d pixels has %d" % (raw.size, ngroup, niter, npix, total))
+    return (raw[comp:stats].view(CLEAN_COMPONENT).reshape(ngroup, niter), raw[stats:total].view(CLEAN_STATS).reshape(ngroup),
+            raw[:comp].view(np.float32).reshape(ngroup, 4, npix))
+
+
+def restore(residual, components, lmn, fwhm_rad):
+    """The restored image, float64 [ngroup][4][npix]: the residual plus, per component, its four words times a Gaussian of full width
+    at half maximum `fwhm_rad` in the angular distance between the component's direction and each pixel's (from the direction
+    cosines: the angle between the two unit vectors), on the free pixel list."""
+    d = np.asarray(lmn, np.float64)
+    out = np.array(residual, np.float64)
+    if out.ndim != 3 or out.shape[1] != 4 or d.shape != (out.shape[2], 3) or len(components) != out.shape[0]:
+        raise ValueError("restore: residual [ngroup][4][npix] %r, components for %d groups, directions %r" % (out.shape, len(components), d.shape))
+    if not (np.isfinite(fwhm_rad) and fwhm_rad > 0):
+        raise ValueError("restore: a beam width of %r radians" % (fwhm_rad,))
+    sigma = fwhm_rad / (2.0 * np.sqrt(2.0 * np.log(2.0)))
+    for g in range(out.shape[0]):
+        for rec in components[g]:
+            if rec['pixel'] < 0:
+                continue
+            x0 = d[rec['pixel']]
+            # the angle from the chord: well conditioned for small separations, where arccos of the dot product is not
+            ang = 2.0 * np.arcsin(np.minimum(np.linalg.norm(d - x0, axis=1) / 2.0, 1.0))
+            out[g] += rec['C'].astype(np.float64)[:, None] * np.exp(-0.5 * (ang / sigma) ** 2)[None]
+    return out
+
+
+def components_to_model(components, lmn, nfavg, nsrc_max=32):
+    """The sky model of a span's components, as UpchanGainCal and UpchanCalApply take it: (src_lmn float64 [nsrc][3], flux float32
+    [nfine][nsrc]).  Components at the same pixel are merged: the flux of a pixel in a channel group is the sum of its (C_XX + C_YY) /
+    2 there -- the unit point source of both polarisations images to XX = YY = 1.  The nsrc_max brightest pixels are kept, ranked by
+    the sum over the groups of |flux| (ties: the lower pixel); a flux that comes out negative is set to 0 (the model's fluxes are >=
+    0).  Each group's flux is repeated over its nfavg channels."""
+    d = np.asarray(lmn, np.float64)
+    ngroup = len(components)
+    if int(nfavg) != nfavg or nfavg <= 0 or int(nsrc_max) != nsrc_max or nsrc_max <= 0:
+        raise ValueError("components_to_model: nfavg %r and nsrc_max %r must be positive integers" % (nfavg, nsrc_max))
+    per = {}
+    for g in range(ngroup):
+        for rec in components[g]:
+            if rec['pixel'] >= 0:
+                per.setdefault(int(rec['pixel']), np.zeros(ngroup))[g] += (float(rec['C'][0]) + float(rec['C'][1])) / 2.0
+    pix = sorted(per, key=lambda x: (-np.abs(per[x]).sum(), x))[:int(nsrc_max)]
+    flux = np.zeros((ngroup, len(pix)))
+    for k, x in enumerate(pix):
+        flux[:, k] = np.maximum(per[x], 0.0)
+    return np.ascontiguousarray(d[pix].reshape(len(pix), 3)), np.ascontiguousarray(np.repeat(flux, int(nfavg), axis=0), np.float32)

@@ -144,6 +144,11 @@ SYMBOLS = {
     "xengCalapplySetFactors": [_vp], "xengCalapplyRun": [_vp, _vp], "xengCalapplyCheckGuards": [_pi],
     "xengCalapplyMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCalapplyWait": [ctypes.c_ulonglong],
     "xengCalapplyTicketDone": [ctypes.c_ulonglong, _pi], "xengCalapplySync": [], "xengCalapplyDestroy": [],
+    "xengCleanInitialize": [_i, _i, _i, _i, _i, _i], "xengCleanGetInfo": [_pi, _pi, _pll, _pll, _pll, ctypes.POINTER(ctypes.c_double)],
+    "xengCleanSetGeometry": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], "xengCleanSetWeights": [ctypes.POINTER(ctypes.c_float), _i],
+    "xengCleanSetWindow": [ctypes.POINTER(ctypes.c_ubyte)], "xengCleanSetControl": [_i, ctypes.c_float, ctypes.c_float, ctypes.c_float],
+    "xengCleanRun": [_vp, _vp], "xengCleanCheckGuards": [_pi], "xengCleanMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCleanWait": [ctypes.c_ulonglong],
+    "xengCleanTicketDone": [ctypes.c_ulonglong, _pi], "xengCleanSync": [], "xengCleanDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -199,6 +204,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengImageRun", "xengImageMark", "xengImageTicketDone",
                 "xengGaincalRun", "xengGaincalMark", "xengGaincalTicketDone",
                 "xengCalapplyRun", "xengCalapplyMark", "xengCalapplyTicketDone",
+                "xengCleanRun", "xengCleanMark", "xengCleanTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

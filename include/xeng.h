@@ -1118,6 +1118,88 @@ int xengCalapplyTicketDone(unsigned long long ticket, int *done);
 int xengCalapplySync(void);
 int xengCalapplyDestroy(void);
 
+/* ---------------------------------------------------------------- Hogbom CLEAN of the dirty images
+ * UpchanClean (no reference counterpart: the reference leaves imaging and deconvolution to offline packages): Hogbom's CLEAN of the
+ * images of xengImage*, per channel group, with the imager's EXACT point-spread function -- the imaging is a direct Fourier sum
+ * over a free list of directions, so the response of pixel x to a unit source at pixel x0 is a closed form, the same for all four
+ * words.  A context of its own, independent of all others, whose kernel runs on the beamformer's stream -- rings declared 'beam'
+ * cover it, and xengBeamformSync waits for it too.  niter + 2 launches of one kernel per Run (csrc/clean_kernels.h); nothing is
+ * read back, and no work-group waits for another.
+ *   image    f32[ngroup][4][npix], the words [XX, YY, Re(XY), Im(XY)]: the output of xengImageRun, or the residual of an earlier
+ *            xengCleanRun (cleaning deeper); 16-byte aligned; never written.  ngroup = nfine / nfavg.
+ *   tables   those of xengImage*: freq f64[nfine] Hz; tau f64[npix][nstand] s; w f32[nstand], finite and >= 0 (after Initialize: all
+ *            1); autos (after Initialize: 0).  They must be the ones the image was made with.
+ *            norm = 1 / (nfavg * sum_{s,t} w_s w_t), over s != t with autos = 0, float64 on the host, rounded once.
+ *   PSF      PSF_g(x, x0) = norm * sum_{c in group g, ascending} ( |S_c(x, x0)|^2 - D )
+ *            S_c(x, x0)   = sum_s w_s * exp(+2 pi i * (fr_c(x,s) - fr_c(x0,s)))
+ *            fr_c(x,s)    = freq[c]*tau[x][s] (the fp64 product, rounded) minus its nearest integer: xengImage*'s rule
+ *            D            = sum_s w_s^2 with autos = 0 (float64 on the host, rounded once), else 0
+ *            The difference of the two fractions is fp64; its conversion to fp32, sincospif of it and everything after are fp32:
+ *              Re S = fma(w_s, cos, Re S), Im S = fma(w_s, sin, Im S), the stands in ascending order;
+ *              p_c = fma(Re S, Re S, Im S * Im S) - D;  acc = acc + p_c, the channels of the group in ascending order;  PSF = norm * acc.
+ *            It is real, PSF_g(x0, x0) = 1 up to rounding, and a stand with w_s = 0 contributes nothing: its tau is never turned
+ *            into a phase.
+ *   window   mask u8[npix]: components are searched among the pixels with mask != 0 only (after Initialize: every pixel); every
+ *            pixel of the list, in or out of the window, is subtracted from.
+ *   control  niter in [0, niter_max], gain in (0, 1], threshold >= 0, fraction >= 0 (after Initialize: niter_max, 0.1, 0, 0)
+ *   loop     per channel group, R a copy of the image, k = 0, 1, ...:
+ *              1. x_k = the window pixel that maximises |I(x)|, I = R[0][x] + R[1][x] (one fp32 add); strict >, ascending pixels: a
+ *                 tie goes to the lowest index; a non-finite I never wins
+ *              2. stop with reason 2 if no pixel won (an empty window, or no finite I in it); with reason 1 if
+ *                 |I(x_k)| <= max(threshold, fraction * |I(x_0)|) (an fp32 product; x_0 the first peak of THIS Run); with reason 0 if
+ *                 k = niter -- tested in this order
+ *              3. component k: the pixel, I(x_k) and C_j = gain * R[j][x_k] (one fp32 multiply per word j); then at every pixel
+ *                 R[j][x] = fma(-C_j, PSF_g(x, x_k), R[j][x])
+ *   out      one span, 16-byte aligned; nothing past it is written:
+ *              0             f32[ngroup][4][npix], the residual: the format of the input
+ *              comp_offset   [ngroup][niter][8] 32-bit words {i32 pixel, f32 I(x_k), f32 C_XX, C_YY, C_Re, C_Im, +0, +0}; the records
+ *                            past ncomp hold pixel -1 and +0
+ *              stats_offset  [ngroup][4] 32-bit words {i32 ncomp, i32 reason, f32 peak, 0}: peak = |I| of the residual's peak in the
+ *                            window (reasons 0 and 1), +0 (reason 2)
+ *            comp_offset = 16 ngroup npix, stats_offset = comp_offset + 32 ngroup niter, span_bytes = stats_offset + 16 ngroup: they
+ *            follow the niter of SetControl (GetInfo reports them for the current one).
+ *   NaN      a pixel whose I is not finite is never a component; the subtraction leaves its NaN where it is.  A component whose
+ *            own XY words are NaN (I is XX + YY: it can still win) turns those words of its group NaN at every pixel.  A group with no
+ *            finite I in the window stops with reason 2 and its residual is the input bit for bit.  Nothing crosses from one channel
+ *            group to another.
+ * Every output word is a fixed function of the image, the tables and the controls: no atomics, one owner per word, one summation
+ * order.  A pixel's residual words depend on its own row of tau and the component list only, not on which other pixels share its
+ * work-group: a sub-list of the pixels that holds the whole window, in the same order, gives the same words bit for bit.  Nothing
+ * depends on what else runs on the GPU.  Run(niter = a) followed by a Run on its residual with niter = b and fraction = 0 gives the
+ * residual and the records of Run(niter = a + b).
+ * The state (freq, tau transposed, w, mask, the launches' hand-over buffers) sits between two guard bands of 64 KiB.  SetGeometry,
+ * SetWeights and SetWindow wait for the context's work in flight: a call between two Runs applies to the later one only;
+ * SetControl sets the arguments of the Runs after it.
+ * Rejected with INVALID_ARGUMENT at the call that sees it, before any device is touched: a non-positive size, nfavg not dividing
+ * nfine, niter_max outside [1, XENG_CLEAN_MAX_NITER], nstand > XENG_CLEAN_MAX_NSTAND, more than 65535 channel groups, npix > 2^24, a
+ * delay table above XENG_CLEAN_MAX_STATE_BYTES (Initialize); NULL, a non-finite word (SetGeometry); NULL, a negative or non-finite
+ * weight, weights that leave no pair (SetWeights); niter outside [0, niter_max], gain outside (0, 1], a negative or non-finite
+ * threshold or fraction (SetControl); NULL or misaligned pointers (Run).  Run before SetGeometry, or with a single stand and the
+ * initial autos = 0, and every call without a context: XENG_STATUS_INVALID_STATE. */
+#define XENG_CLEAN_MAX_NITER 4096
+#define XENG_CLEAN_MAX_NSTAND 2048
+#define XENG_CLEAN_MAX_STATE_BYTES (1LL << 31)
+int xengCleanInitialize(int gpu, int nstand, int nfine, int nfavg, int npix, int niter_max);
+/* the live context's number of channel groups, the pixels per work-group, the span's layout for the current niter, and norm (float64) */
+int xengCleanGetInfo(int *ngroup, int *pixel_tile, long long *comp_offset, long long *stats_offset, long long *span_bytes, double *norm);
+/* tau: f64[npix][nstand] seconds, freq: f64[nfine] Hz, on the host.  Waits for the context's work in flight, uploads both. */
+int xengCleanSetGeometry(const double *tau, const double *freq);
+/* w: f32[nstand] on the host.  Waits for the context's work in flight; holds from the next Run. */
+int xengCleanSetWeights(const float *w, int autos);
+/* mask: u8[npix] on the host, or NULL for every pixel.  Waits for the context's work in flight; holds from the next Run. */
+int xengCleanSetWindow(const unsigned char *mask);
+int xengCleanSetControl(int niter, float gain, float threshold, float fraction);
+/* enqueue only: one image; image_dev is never written */
+int xengCleanRun(const void *image_dev, void *out_dev);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengCleanCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengCleanMark(unsigned long long *ticket);
+int xengCleanWait(unsigned long long ticket);
+int xengCleanTicketDone(unsigned long long ticket, int *done);
+int xengCleanSync(void);
+int xengCleanDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
