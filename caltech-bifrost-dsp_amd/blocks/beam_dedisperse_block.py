@@ -17,13 +17,11 @@ one flagged by UpchanSpectra's spectral kurtosis) takes effect at the next span,
 """
 import json
 import math
-import time
 
 import numpy as np
 
 from ..backend import default_backend
-from ..ndarray import XArray
-from .block_base import Block, InFlight, declare_streams, gulp_time, spans_outlive_release
+from .block_base import Block, InFlight, SpanLoop, declare_streams, spans_outlive_release
 from .dedisp import dm_delays
 
 STOKES = {'I': 1, 'full': 4}
@@ -126,17 +124,13 @@ class BeamDedisperse(Block):
         return checked_fine_weights("BEAM_DEDISPERSE", w, self.nfine, quiet)
 
     def _initialize(self, max_delay):
-        rv = self._bf.dedisp_initialize(self.gpu, self.npair, self.nfine, self.nwin, self.ndm, max_delay, self.nprod)
-        if rv != self._bf.BF_STATUS_SUCCESS:
-            raise RuntimeError("xengDedispInitialize returned %d: %s" % (rv, self._bf.last_error()))
+        self._call('dedisp_initialize', self.gpu, self.npair, self.nfine, self.nwin, self.ndm, max_delay, self.nprod)
         self._ctx_delay = max_delay
         if self._weights is not None:
             self._set_weights()
 
     def _set_weights(self):
-        rv = self._bf.dedisp_set_weights(self._weights)
-        if rv != self._bf.BF_STATUS_SUCCESS:
-            raise RuntimeError("xengDedispSetWeights returned %d: %s" % (rv, self._bf.last_error()))
+        self._call('dedisp_set_weights', self._weights)
 
     def _check_header(self, ihdr):
         """The dual-pol fine-channel power beams of UpchanSumBeams / UpchanBeamform(dual_pol=True) only."""
@@ -158,16 +152,17 @@ class BeamDedisperse(Block):
 
     def main(self):
         self.bind()
-        self._oshape = (self.nwin, self.npair, self.ndm, self.nprod)
-        ogulp_size = int(np.prod(self._oshape)) * 4
+        ogulp_size = self.nwin * self.npair * self.ndm * self.nprod * 4
         self.oring.resize(ogulp_size)
-        # Streaming, tickets and the staged copy into a pinned-host output ring: InFlight (block_base.py)
+        # Streaming, tickets and the staged copy into a pinned-host output ring: InFlight; the loop over the spans: SpanLoop
+        # (block_base.py)
         streaming = spans_outlive_release(self.iring, self.oring)
-        self._staged = streaming and self.oring.space == 'cuda_host' and hasattr(self._bf, 'copy_async')
-        self._dev = None if streaming else XArray(shape=self._oshape, dtype=np.float32, space=self._bf.space_in)
-        with InFlight(self._bf.dedisp_wait, self._bf.dedisp_sync, self._bf) as inflight, self.oring.begin_writing() as oring:
+        staged = streaming and self.oring.space == 'cuda_host' and hasattr(self._bf, 'copy_async')
+        with InFlight(self._bf.dedisp_wait, self._bf.dedisp_sync, self._bf, mark=self._bf.dedisp_mark) as inflight, \
+                self.oring.begin_writing() as oring:
+            loop = SpanLoop(self, "BEAM_DEDISPERSE", inflight, oring, streaming, staged, gap_note=": the history starts again")
             for iseq in self.iring.read(guarantee=self.guarantee):
-                self._sequence(iseq, oring, ogulp_size, streaming, inflight)
+                self._sequence(iseq, loop, ogulp_size)
 
     def _load_pending_weights(self):
         """A `weights` command: on the device before the next span is enqueued (SetWeights waits for the spans in flight)."""
@@ -177,7 +172,7 @@ class BeamDedisperse(Block):
             self._weights = self._checked_weights(w)
             self._set_weights()
 
-    def _sequence(self, iseq, oring, ogulp_size, streaming, inflight):
+    def _sequence(self, iseq, loop, ogulp_size):
         ihdr = json.loads(iseq.header.tostring())
         self.sequence_proclog.update(ihdr)
         acc_len = self._check_header(ihdr)
@@ -185,72 +180,21 @@ class BeamDedisperse(Block):
         S = int(table.max())
         if self.max_delay is not None and S > self.max_delay:
             raise ValueError("BEAM_DEDISPERSE: DM %g needs a delay of %d windows of %g s, max_delay is %d" % (self.dms.max(), S, tsamp, self.max_delay))
-        inflight.retire(0)
+        loop.inflight.retire(0)
         if self.max_delay is None and self._ctx_delay != S:
             self._initialize(S)                 # (a history as long as this sequence's table needs)
-        rv = self._bf.dedisp_set_delays(table)  # (clears the history and the window count: a new sequence starts from nothing)
-        if rv != self._bf.BF_STATUS_SUCCESS:
-            raise RuntimeError("xengDedispSetDelays returned %d: %s" % (rv, self._bf.last_error()))
+        self._call('dedisp_set_delays', table)  # (clears the history and the window count: a new sequence starts from nothing)
         self.update_stats({'dedisp_latency': S})
-        seq0 = ihdr['seq0']
-        ntime_span = self.nwin * acc_len        # samples of the beamformer's clock per span
-        igulp_size = self.nwin * self.npair * self.nfine * 16
-        this_gulp_time = seq0
-        expected = seq0
-        oseq = None
-        try:
-            prev_time = time.time()
-            for ispan in iseq.read(igulp_size):
-                if ispan.size < igulp_size:
-                    continue                    # a short final span is skipped (as the reference's gulp_nframe reader does)
-                this_gulp_time = gulp_time(ispan, seq0, igulp_size, ntime_span, this_gulp_time)
-                if this_gulp_time != expected:
-                    # windows this reader never saw: what the history holds does not line up with what comes now
-                    self._bf.dedisp_reset()
-                    self.update_stats({'ngap': self.stats['ngap'] + 1})
-                    self.log.warning("BEAM_DEDISPERSE >> samples [%d, %d) were not read: the history starts again" % (expected, this_gulp_time))
-                    if oseq is not None:
-                        inflight.retire(0)
-                        oseq.end()
-                        oseq = None
-                expected = this_gulp_time + ntime_span
-                self.update_stats({'curr_sample': this_gulp_time})
-                if self.update_pending:
-                    self._load_pending_weights()
-                held = ispan.data
-                if oseq is None:
-                    oseq = oring.begin_sequence(time_tag=this_gulp_time, header=json.dumps(self.output_header(ihdr, this_gulp_time, S, tsamp)))
-                curr_time = time.time()
-                acquire_time = curr_time - prev_time
-                prev_time = curr_time
-                ospan = oseq.reserve(ogulp_size)
-                stage = None
-                try:
-                    if self._staged:
-                        stage = inflight.take_stage(ogulp_size)
-                    target = stage if stage is not None else (ospan.data if streaming else self._dev)
-                    rv = self._bf.dedisp_run(held, self.nwin, target)
-                    if rv != self._bf.BF_STATUS_SUCCESS:
-                        raise RuntimeError("xengDedispRun returned %d: %s" % (rv, self._bf.last_error()))
-                    self.update_stats({'nwindow': self.stats['nwindow'] + self.nwin, 'last_end_sample': this_gulp_time + ntime_span})
-                    osp, ospan = ospan, None
-                    if streaming:
-                        inflight.push(self._bf.dedisp_mark(), osp, held, stage)
-                        inflight.retire(self.STREAM_DEPTH)
-                    else:
-                        self._bf.dedisp_sync()
-                        try:
-                            osp.data_view(np.float32).reshape(self._oshape)[...] = self._dev      # (synchronous copy)
-                        finally:
-                            osp.close()
-                finally:
-                    if ospan is not None:
-                        ospan.close()
-                curr_time = time.time()
-                process_time = curr_time - prev_time
-                prev_time = curr_time
-                self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
-        finally:
-            inflight.retire(0)                  # every call in flight is complete (and every output span committed) first
-            if oseq is not None:
-                oseq.end()
+
+        def pending(t):
+            if self.update_pending:
+                self._load_pending_weights()
+
+        def dedisperse(t, held, out):
+            self._call('dedisp_run', held, self.nwin, out.target())
+            return {'nwindow': self.stats['nwindow'] + self.nwin}
+
+        # (a span is nwin windows of acc_len samples of the beamformer's clock; after a gap what the history holds does not line up
+        # with what comes now)
+        loop.run(iseq, ihdr['seq0'], self.nwin * self.npair * self.nfine * 16, self.nwin * acc_len, ogulp_size,
+                 lambda t: self.output_header(ihdr, t, S, tsamp), dedisperse, before=pending, on_gap=self._bf.dedisp_reset)

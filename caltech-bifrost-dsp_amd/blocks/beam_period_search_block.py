@@ -25,14 +25,12 @@ next segment to complete.
 Not built: acceleration search, median whitening, more than one peak per series and level, sifting of harmonically related
 candidates, segments beyond 2^14 windows."""
 import json
-import time
 
 import numpy as np
 
 from ..backend import default_backend
-from ..ndarray import XArray
 from .beam_dedisperse_block import _number, check_dedispersed_header
-from .block_base import Block, InFlight, declare_streams, gulp_time, spans_outlive_release
+from .block_base import SKIP, Block, InFlight, SpanLoop, declare_streams, spans_outlive_release
 from .period_search import RECORD, as_records, period_candidates
 
 
@@ -85,9 +83,7 @@ class BeamPeriodSearch(Block):
         self._nwindows = 0                      # windows given to the context since its last reset
 
     def _initialize(self, nprod):
-        rv = self._bf.period_initialize(self.gpu, self.npair, self.ndm, self.nwin, nprod, self.nt, self.nstack, self.nlevel, self.nwhite, self.kmin)
-        if rv != self._bf.BF_STATUS_SUCCESS:
-            raise RuntimeError("xengPeriodInitialize returned %d: %s" % (rv, self._bf.last_error()))
+        self._call('period_initialize', self.gpu, self.npair, self.ndm, self.nwin, nprod, self.nt, self.nstack, self.nlevel, self.nwhite, self.kmin)
         self._ctx_nprod = nprod
         self._nwindows = 0
         if self._mask:
@@ -97,9 +93,7 @@ class BeamPeriodSearch(Block):
         keep = np.ones(self.nt // 2, np.uint8)
         for lo, hi in ranges:
             keep[lo:hi] = 0
-        rv = self._bf.period_set_mask(keep)
-        if rv != self._bf.BF_STATUS_SUCCESS:
-            raise RuntimeError("xengPeriodSetMask returned %d: %s" % (rv, self._bf.last_error()))
+        self._call('period_set_mask', keep)
         self._mask = ranges
 
     def _reset(self):
@@ -127,106 +121,64 @@ class BeamPeriodSearch(Block):
         self.bind()
         ogulp_size = self.npair * self.ndm * self.nlevel * RECORD.itemsize
         self.oring.resize(ogulp_size)
-        # Streaming, tickets and the staged copy into a pinned-host output ring: InFlight (block_base.py)
+        # Streaming, tickets and the staged copy into a pinned-host output ring: InFlight; the loop over the spans: SpanLoop
+        # (block_base.py)
         ospace = getattr(self.oring, 'space', 'system')
         direct = ospace in (self._bf.space_in, 'cuda_host')     # (the kernel can write the span itself)
-        self._staged = spans_outlive_release(self.iring, self.oring) and ospace == 'cuda_host' and hasattr(self._bf, 'copy_async')
-        streaming = spans_outlive_release(self.iring, self.oring) and (direct or self._staged)
-        self._dev = None if streaming else XArray(shape=(ogulp_size,), dtype=np.uint8, space=self._bf.space_in)
-        with InFlight(self._bf.period_wait, self._bf.period_sync, self._bf, finish=self._finish) as inflight, self.oring.begin_writing() as oring:
+        staged = spans_outlive_release(self.iring, self.oring) and ospace == 'cuda_host' and hasattr(self._bf, 'copy_async')
+        streaming = spans_outlive_release(self.iring, self.oring) and (direct or staged)
+        with InFlight(self._bf.period_wait, self._bf.period_sync, self._bf, finish=self._finish, mark=self._bf.period_mark) as inflight, \
+                self.oring.begin_writing() as oring:
+            loop = SpanLoop(self, "BEAM_PERIOD_SEARCH", inflight, oring, streaming, staged, gap_note=": the stack starts again", count_gaps=False)
             for iseq in self.iring.read(guarantee=self.guarantee):
-                self._sequence(iseq, oring, ogulp_size, streaming, inflight)
+                self._sequence(iseq, loop, ogulp_size)
 
-    def _sequence(self, iseq, oring, ogulp_size, streaming, inflight):
+    def _load_pending_commands(self):
+        self.update_command_vals()
+        if self.command_vals.get('threshold') is not None:
+            self.threshold = float(self.command_vals['threshold'])
+        if self.command_vals.get('mask') is not None and self.command_vals['mask'] != self._mask:
+            if any(hi > self.nt // 2 for _, hi in self.command_vals['mask']):
+                self.log.warning("BEAM_PERIOD_SEARCH >> a mask beyond bin %d is ignored" % (self.nt // 2))
+            else:
+                self._set_mask(self.command_vals['mask'])
+
+    def _sequence(self, iseq, loop, ogulp_size):
         ihdr = json.loads(iseq.header.tostring())
         self.sequence_proclog.update(ihdr)
         nprod, acc_len, S, dms, tsamp = check_dedispersed_header("BEAM_PERIOD_SEARCH", ihdr, self.npair, self.ndm)
-        inflight.retire(0)
+        loop.inflight.retire(0)
         if self._ctx_nprod != nprod:
             self._initialize(nprod)
         else:
             self._reset()                       # (a new sequence starts from nothing: no partial segment, no partial stack)
         seq0 = ihdr['seq0']
-        ntime_span = self.nwin * acc_len        # samples of the beamformer's clock per span
-        igulp_size = self.nwin * self.npair * self.ndm * nprod * 4
         nstack_win = self.nt * self.nstack      # windows of a stack
-        this_gulp_time = seq0
-        expected = seq0
-        oseq = None
-        try:
-            prev_time = time.time()
-            for ispan in iseq.read(igulp_size):
-                if ispan.size < igulp_size:
-                    continue                    # a short final span is skipped (as the reference's gulp_nframe reader does)
-                this_gulp_time = gulp_time(ispan, seq0, igulp_size, ntime_span, this_gulp_time)
-                if this_gulp_time != expected:
-                    # windows this reader never saw: the segment and the stack in progress do not line up with what comes now
-                    if self._nwindows % nstack_win:
-                        self.update_stats({'ndropped': self.stats['ndropped'] + 1})
-                    self._reset()
-                    self.log.warning("BEAM_PERIOD_SEARCH >> samples [%d, %d) were not read: the stack starts again" % (expected, this_gulp_time))
-                    if oseq is not None:
-                        inflight.retire(0)
-                        oseq.end()
-                        oseq = None
-                expected = this_gulp_time + ntime_span
-                self.update_stats({'curr_sample': this_gulp_time})
-                if self.update_pending:
-                    self.update_command_vals()
-                    if self.command_vals.get('threshold') is not None:
-                        self.threshold = float(self.command_vals['threshold'])
-                    if self.command_vals.get('mask') is not None and self.command_vals['mask'] != self._mask:
-                        if any(hi > self.nt // 2 for _, hi in self.command_vals['mask']):
-                            self.log.warning("BEAM_PERIOD_SEARCH >> a mask beyond bin %d is ignored" % (self.nt // 2))
-                        else:
-                            self._set_mask(self.command_vals['mask'])
-                if (this_gulp_time - seq0) // acc_len < S:
-                    self.update_stats({'nstartup': self.stats['nstartup'] + 1})
-                    continue                    # (the span begins inside the dedisperser's partial sums)
-                held = ispan.data
-                if oseq is None:
-                    oseq = oring.begin_sequence(time_tag=this_gulp_time, header=json.dumps(self.output_header(ihdr, this_gulp_time)))
-                curr_time = time.time()
-                acquire_time = curr_time - prev_time
-                prev_time = curr_time
-                completes = (self._nwindows + self.nwin) // nstack_win > self._nwindows // nstack_win
-                meta = (self.threshold, dms, tsamp)
-                ospan = oseq.reserve(ogulp_size) if completes else None
-                stage = None
-                try:
-                    target = None
-                    if completes:
-                        if self._staged:
-                            stage = inflight.take_stage(ogulp_size)
-                        target = stage if stage is not None else (ospan.data if streaming else self._dev)
-                    rv, completed = self._bf.period_run(held, self.nwin, target)
-                    if rv != self._bf.BF_STATUS_SUCCESS:
-                        raise RuntimeError("xengPeriodRun returned %d: %s" % (rv, self._bf.last_error()))
-                    if bool(completed) != completes:
-                        raise RuntimeError("BEAM_PERIOD_SEARCH: the context and the block disagree on which call completes a stack")
-                    self._nwindows += self.nwin
-                    self.update_stats({'nwindow': self.stats['nwindow'] + self.nwin, 'last_end_sample': this_gulp_time + ntime_span})
-                    osp, ospan = ospan, None
-                    if streaming:
-                        inflight.push(self._bf.period_mark(), osp, held, stage, meta)
-                        inflight.retire(self.STREAM_DEPTH)
-                    else:
-                        self._bf.period_sync()
-                        if osp is not None:
-                            try:
-                                osp.data_view(np.uint8)[...] = self._dev          # (synchronous copy)
-                            except Exception:
-                                osp.close()
-                                raise
-                            self._finish(osp, meta)
-                finally:
-                    if ospan is not None:
-                        ospan.close()
-                curr_time = time.time()
-                process_time = curr_time - prev_time
-                prev_time = curr_time
-                self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
-        finally:
-            inflight.retire(0)                  # every call in flight is complete (and every output span committed) first
-            if oseq is not None:
-                oseq.end()
+
+        def gap():
+            # windows this reader never saw: the segment and the stack in progress do not line up with what comes now
+            if self._nwindows % nstack_win:
+                self.update_stats({'ndropped': self.stats['ndropped'] + 1})
+            self._reset()
+
+        def pending(t):
+            if self.update_pending:
+                self._load_pending_commands()
+            if (t - seq0) // acc_len < S:
+                self.update_stats({'nstartup': self.stats['nstartup'] + 1})
+                return SKIP                     # (the span begins inside the dedisperser's partial sums)
+
+        def search(t, held, out):
+            # only the call that completes a stack reserves and writes an output span
+            completes = (self._nwindows + self.nwin) // nstack_win > self._nwindows // nstack_win
+            rv, completed = self._bf.period_run(held, self.nwin, out.target((self.threshold, dms, tsamp)) if completes else None)
+            if rv != self._bf.BF_STATUS_SUCCESS:
+                raise RuntimeError("period_run returned %d: %s" % (rv, self._bf.last_error()))
+            if bool(completed) != completes:
+                raise RuntimeError("BEAM_PERIOD_SEARCH: the context and the block disagree on which call completes a stack")
+            self._nwindows += self.nwin
+            return {'nwindow': self.stats['nwindow'] + self.nwin}
+
+        # (a span is nwin windows of acc_len samples of the beamformer's clock)
+        loop.run(iseq, seq0, self.nwin * self.npair * self.ndm * nprod * 4, self.nwin * acc_len, ogulp_size, lambda t: self.output_header(ihdr, t),
+                 search, before=pending, on_gap=gap)

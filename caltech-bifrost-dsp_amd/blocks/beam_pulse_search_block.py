@@ -24,14 +24,12 @@ sequence of its own (UpchanSumBeams' rule, as in BeamDedisperse).  A `threshold`
 Not built: a robust baseline (a bright pulse in block k raises sigma for block k+1), clustering in time across spans, and a
 trigger writer."""
 import json
-import time
 
 import numpy as np
 
 from ..backend import default_backend
-from ..ndarray import XArray
 from .beam_dedisperse_block import _number, check_dedispersed_header
-from .block_base import Block, InFlight, declare_streams, gulp_time, spans_outlive_release
+from .block_base import Block, InFlight, SpanLoop, declare_streams, spans_outlive_release
 from .pulse_search import RECORD, as_records, pulse_candidates
 
 
@@ -68,9 +66,7 @@ class BeamPulseSearch(Block):
         self._ctx_nprod = None                  # nprod of the live context
 
     def _initialize(self, nprod):
-        rv = self._bf.pulse_initialize(self.gpu, self.npair, self.ndm, self.nwin, nprod, self.nwidth, self.nstat)
-        if rv != self._bf.BF_STATUS_SUCCESS:
-            raise RuntimeError("xengPulseInitialize returned %d: %s" % (rv, self._bf.last_error()))
+        self._call('pulse_initialize', self.gpu, self.npair, self.ndm, self.nwin, nprod, self.nwidth, self.nstat)
         self._ctx_nprod = nprod
 
     def output_header(self, ihdr, start):
@@ -101,89 +97,40 @@ class BeamPulseSearch(Block):
         self.bind()
         ogulp_size = self.npair * self.ndm * RECORD.itemsize
         self.oring.resize(ogulp_size)
-        # Streaming, tickets and the staged copy into a pinned-host output ring: InFlight (block_base.py)
+        # Streaming, tickets and the staged copy into a pinned-host output ring: InFlight; the loop over the spans: SpanLoop
+        # (block_base.py)
         ospace = getattr(self.oring, 'space', 'system')
         direct = ospace in (self._bf.space_in, 'cuda_host')     # (the kernel can write the span itself)
-        self._staged = spans_outlive_release(self.iring, self.oring) and ospace == 'cuda_host' and hasattr(self._bf, 'copy_async')
-        streaming = spans_outlive_release(self.iring, self.oring) and (direct or self._staged)
-        self._dev = None if streaming else XArray(shape=(ogulp_size,), dtype=np.uint8, space=self._bf.space_in)
-        with InFlight(self._bf.pulse_wait, self._bf.pulse_sync, self._bf, finish=self._finish) as inflight, self.oring.begin_writing() as oring:
+        staged = spans_outlive_release(self.iring, self.oring) and ospace == 'cuda_host' and hasattr(self._bf, 'copy_async')
+        streaming = spans_outlive_release(self.iring, self.oring) and (direct or staged)
+        with InFlight(self._bf.pulse_wait, self._bf.pulse_sync, self._bf, finish=self._finish, mark=self._bf.pulse_mark) as inflight, \
+                self.oring.begin_writing() as oring:
+            loop = SpanLoop(self, "BEAM_PULSE_SEARCH", inflight, oring, streaming, staged, gap_note=": the baseline starts again")
             for iseq in self.iring.read(guarantee=self.guarantee):
-                self._sequence(iseq, oring, ogulp_size, streaming, inflight)
+                self._sequence(iseq, loop, ogulp_size)
 
-    def _sequence(self, iseq, oring, ogulp_size, streaming, inflight):
+    def _sequence(self, iseq, loop, ogulp_size):
         ihdr = json.loads(iseq.header.tostring())
         self.sequence_proclog.update(ihdr)
         nprod, acc_len, S, dms, _ = check_dedispersed_header("BEAM_PULSE_SEARCH", ihdr, self.npair, self.ndm)
-        inflight.retire(0)
+        loop.inflight.retire(0)
         if self._ctx_nprod != nprod:
             self._initialize(nprod)
         else:
             self._bf.pulse_reset()              # (a new sequence starts from nothing: no baseline, no boxcar reaches back)
         seq0 = ihdr['seq0']
-        ntime_span = self.nwin * acc_len        # samples of the beamformer's clock per span
-        igulp_size = self.nwin * self.npair * self.ndm * nprod * 4
-        this_gulp_time = seq0
-        expected = seq0
-        oseq = None
-        try:
-            prev_time = time.time()
-            for ispan in iseq.read(igulp_size):
-                if ispan.size < igulp_size:
-                    continue                    # a short final span is skipped (as the reference's gulp_nframe reader does)
-                this_gulp_time = gulp_time(ispan, seq0, igulp_size, ntime_span, this_gulp_time)
-                if this_gulp_time != expected:
-                    # windows this reader never saw: the baseline and the last windows do not line up with what comes now
-                    self._bf.pulse_reset()
-                    self.update_stats({'ngap': self.stats['ngap'] + 1})
-                    self.log.warning("BEAM_PULSE_SEARCH >> samples [%d, %d) were not read: the baseline starts again" % (expected, this_gulp_time))
-                    if oseq is not None:
-                        inflight.retire(0)
-                        oseq.end()
-                        oseq = None
-                expected = this_gulp_time + ntime_span
-                self.update_stats({'curr_sample': this_gulp_time})
-                if self.update_pending:
-                    self.update_command_vals()
-                    if self.command_vals.get('threshold') is not None:
-                        self.threshold = float(self.command_vals['threshold'])
-                held = ispan.data
-                if oseq is None:
-                    oseq = oring.begin_sequence(time_tag=this_gulp_time, header=json.dumps(self.output_header(ihdr, this_gulp_time)))
-                curr_time = time.time()
-                acquire_time = curr_time - prev_time
-                prev_time = curr_time
-                meta = (self.threshold, (this_gulp_time - seq0) // acc_len, seq0, S, acc_len, dms)
-                ospan = oseq.reserve(ogulp_size)
-                stage = None
-                try:
-                    if self._staged:
-                        stage = inflight.take_stage(ogulp_size)
-                    target = stage if stage is not None else (ospan.data if streaming else self._dev)
-                    rv = self._bf.pulse_run(held, self.nwin, target)
-                    if rv != self._bf.BF_STATUS_SUCCESS:
-                        raise RuntimeError("xengPulseRun returned %d: %s" % (rv, self._bf.last_error()))
-                    self.update_stats({'nwindow': self.stats['nwindow'] + self.nwin, 'last_end_sample': this_gulp_time + ntime_span})
-                    osp, ospan = ospan, None
-                    if streaming:
-                        inflight.push(self._bf.pulse_mark(), osp, held, stage, meta)
-                        inflight.retire(self.STREAM_DEPTH)
-                    else:
-                        self._bf.pulse_sync()
-                        try:
-                            osp.data_view(np.uint8)[...] = self._dev          # (synchronous copy)
-                        except Exception:
-                            osp.close()
-                            raise
-                        self._finish(osp, meta)
-                finally:
-                    if ospan is not None:
-                        ospan.close()
-                curr_time = time.time()
-                process_time = curr_time - prev_time
-                prev_time = curr_time
-                self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
-        finally:
-            inflight.retire(0)                  # every call in flight is complete (and every output span committed) first
-            if oseq is not None:
-                oseq.end()
+
+        def pending(t):
+            if self.update_pending:
+                self.update_command_vals()
+                if self.command_vals.get('threshold') is not None:
+                    self.threshold = float(self.command_vals['threshold'])
+
+        def search(t, held, out):
+            self._call('pulse_run', held, self.nwin, out.target((self.threshold, (t - seq0) // acc_len, seq0, S, acc_len, dms)))
+            return {'nwindow': self.stats['nwindow'] + self.nwin}
+
+        # (a span is nwin windows of acc_len samples of the beamformer's clock; after a gap the baseline and the last windows do
+        # not line up with what comes now)
+        loop.run(iseq, seq0, self.nwin * self.npair * self.ndm * nprod * 4, self.nwin * acc_len, ogulp_size, lambda t: self.output_header(ihdr, t),
+                 search, before=pending, on_gap=self._bf.pulse_reset)

@@ -49,7 +49,8 @@ class InFlight(object):
     """The calls of a streaming block whose kernels may still run, oldest first, and the copies of their outputs that may:
     everything that keeps span memory from going back to a ring under a running kernel or copy.
 
-    `wait(ticket)` / `sync()` are the backend's ticket wait and stream sync.  A call is pushed with the ticket that follows its
+    `wait(ticket)` / `sync()` / `mark()` are the backend's ticket wait, stream sync and ticket for what has been enqueued so far
+    (`mark`: kept for SpanLoop, which pushes it).  A call is pushed with the ticket that follows its
     kernels, its output span(s) (none: only the input is held) and the input it reads.  Its kernel wrote either the span itself,
     or a `stage` from take_stage(): a device buffer that the copy stream (`backend`: copy_async / copy_done / copy_wait,
     space_in) moves into the span(s) once the ticket is done -- a kernel that stores into a pinned-host span holds its stream
@@ -61,8 +62,9 @@ class InFlight(object):
     copies before it drops their spans, uncommitted -- released under a running kernel, their memory would go back to the
     ring, to be handed out again or freed."""
 
-    def __init__(self, wait, sync, backend=None, finish=None, outstanding=2):
+    def __init__(self, wait, sync, backend=None, finish=None, outstanding=2, mark=None):
         self._wait, self._sync, self._bf, self._outstanding = wait, sync, backend, outstanding
+        self.mark = mark
         self._finish = finish if finish is not None else lambda ospan, meta: ospan.close()
         self._calls = collections.deque()       # (ticket, output spans, input kept alive, stage or None, meta)
         self._copies = collections.deque()      # (stamp, output span, stage to give back after this copy or None, meta)
@@ -107,6 +109,19 @@ class InFlight(object):
         if self._copies:
             self._finish_copies((self._outstanding() if callable(self._outstanding) else self._outstanding) if keep else 0)
 
+    def finish_now(self, ospan, dev, meta=None):
+        """The synchronous path, for rings whose spans do not outlive release: wait for the stream, copy the bytes the kernel
+        wrote into the scratch buffer `dev` to the span and finish it (no span: only the wait)."""
+        self._sync()
+        if ospan is None:
+            return
+        try:
+            ospan.data_view(np.uint8).reshape(-1)[...] = dev
+        except BaseException:
+            ospan.close()
+            raise
+        self._finish(ospan, meta)
+
     def __enter__(self):
         return self
 
@@ -131,6 +146,106 @@ def gulp_time(ispan, seq0, igulp_size, ntime_gulp, prev):
     if getattr(ispan, 'skipped', 0):
         return prev + (ispan.skipped // igulp_size) * ntime_gulp
     return prev
+
+
+RESTART, SKIP = 'restart', 'skip'               # what SpanLoop's `before` hook may answer
+
+
+class SpanLoop(object):
+    """The loop of a block that reads one span and writes at most one: which span is closed uncommitted on an error, what is
+    waited for before an output sequence ends, and what keeps an input alive under a running kernel.
+
+    Made once in main(): `block` gives the log, the stats, the perf log, STREAM_DEPTH and the backend's space; `who` heads the
+    log lines and `gap_note` ends the one about a gap; `inflight` is the block's InFlight (with `mark`), `oring` the output
+    ring being written.  `streaming`: the rings' spans outlive release, so calls are pushed and up to STREAM_DEPTH stay in
+    flight; else every call is waited for and its output copied from the loop's device scratch buffer.  `staged`: the kernel
+    writes a stage of the InFlight, not the span.  `count_gaps`: a gap bumps stats['ngap'].
+
+    run() is one input sequence.  Per whole span (a short final one is ignored), with t its first sample:
+      a gap (t is not where the span before ended): on_gap(), the log line, the output sequence ends;
+      before(t) loads what is pending and may answer RESTART (the output sequence ends here) or SKIP (the span is dropped);
+      the output sequence is begun if there is none, at time tag t with header(t);
+      body(t, held, loop) enqueues the kernels on the input `held`.  It writes where loop.target(meta) says -- which reserves
+      the output span -- or nowhere, and returns the stats it changes; 'last_end_sample' is added.
+    The call is then pushed with its ticket, or waited for and finished.  An output sequence ends only after retire(0)."""
+
+    def __init__(self, block, who, inflight, oring, streaming, staged=False, gap_note="", count_gaps=True):
+        self.block, self.who, self.inflight, self.oring = block, who, inflight, oring
+        self.streaming, self.staged, self.gap_note, self.count_gaps = streaming, staged, gap_note, count_gaps
+        self._oseq = self._ospan = self._stage = self._meta = self._dev = None
+
+    def target(self, meta=None):
+        """Reserve this call's output span and give what its kernel writes: a stage, the span itself, or the scratch buffer.
+        `meta` goes to the InFlight's finish with the span."""
+        self._meta = meta
+        self._ospan = self._oseq.reserve(self._ogulp_size)
+        if self.staged:
+            self._stage = self.inflight.take_stage(self._ogulp_size)
+            return self._stage
+        return self._ospan.data if self.streaming else self._dev
+
+    def _end_sequence(self):
+        if self._oseq is not None:
+            self.inflight.retire(0)             # every call in flight is complete (and every output span committed) first
+            oseq, self._oseq = self._oseq, None
+            oseq.end()
+
+    def run(self, iseq, seq0, igulp_size, ntime_gulp, ogulp_size, header, body, before=None, on_gap=None):
+        block, inflight = self.block, self.inflight
+        self._ogulp_size, self._oseq = ogulp_size, None
+        if not self.streaming and (self._dev is None or self._dev.nbytes != ogulp_size):
+            self._dev = XArray(shape=(ogulp_size,), dtype=np.uint8, space=block._bf.space_in)
+        this_gulp_time = expected = seq0
+        try:
+            prev_time = time.time()
+            for ispan in iseq.read(igulp_size):
+                if ispan.size < igulp_size:
+                    continue                    # a short final span is skipped (as the reference's gulp_nframe reader does)
+                this_gulp_time = gulp_time(ispan, seq0, igulp_size, ntime_gulp, this_gulp_time)
+                if this_gulp_time != expected:
+                    # spans this reader never saw: the output goes on in a sequence of its own, so that a span's time follows
+                    # from its place
+                    if on_gap is not None:
+                        on_gap()
+                    if self.count_gaps:
+                        block.update_stats({'ngap': block.stats['ngap'] + 1})
+                    block.log.warning("%s >> samples [%d, %d) were not read%s" % (self.who, expected, this_gulp_time, self.gap_note))
+                    self._end_sequence()
+                expected = this_gulp_time + ntime_gulp
+                block.update_stats({'curr_sample': this_gulp_time})
+                action = before(this_gulp_time) if before is not None else None
+                if action == SKIP:
+                    continue
+                if action == RESTART:
+                    self._end_sequence()
+                held = ispan.data
+                if self._oseq is None:
+                    self._oseq = self.oring.begin_sequence(time_tag=this_gulp_time, header=json.dumps(header(this_gulp_time)))
+                curr_time = time.time()
+                acquire_time = curr_time - prev_time
+                prev_time = curr_time
+                self._ospan = self._stage = self._meta = None
+                try:
+                    stats = body(this_gulp_time, held, self) or {}
+                    stats['last_end_sample'] = this_gulp_time + ntime_gulp
+                    block.update_stats(stats)
+                    osp, self._ospan = self._ospan, None
+                    if self.streaming:
+                        inflight.push(inflight.mark(), osp, held, self._stage, self._meta)
+                        inflight.retire(block.STREAM_DEPTH)
+                    else:
+                        inflight.finish_now(osp, self._dev, self._meta)
+                finally:
+                    if self._ospan is not None:
+                        self._ospan.close()     # (reserved, but not handed over)
+                        self._ospan = None
+                curr_time = time.time()
+                process_time = curr_time - prev_time
+                prev_time = curr_time
+                block.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
+        finally:
+            inflight.retire(0)                  # (with or without an output sequence: the input spans are let go of)
+            self._end_sequence()
 
 
 def split_frames(parts, row, nupchan, who):
@@ -301,6 +416,21 @@ class Block(object):
             self.stats['update_pending'] = False
             self.stats['last_cmd_proc_time'] = time.time()
         self.update_stats(self.command_vals)
+
+    def take_commands(self, keys):
+        """update_command_vals(), then {key: value} of the `keys` a command has set.  A command is taken once: left in place, a
+        later command for another key would bring it back over a set_*() made since."""
+        self.update_command_vals()
+        taken = {}
+        with self._control_lock:
+            for k in keys:
+                cmd = self.command_vals.get(k)
+                if cmd is not None:
+                    taken[k] = cmd
+                    self.command_vals[k] = None
+                    if self._pending_command_vals.get(k) is cmd:
+                        self._pending_command_vals[k] = None
+        return taken
 
     def acquire_control_lock(self):
         self._control_lock.acquire()

@@ -33,6 +33,26 @@ def model_flux(flux, nfine, nsrc):
     return np.ascontiguousarray(F)
 
 
+MAX_NSRC, MAX_NSTAND = 32, 512          # include/xeng.h XENG_GAINCAL_MAX_* and XENG_CALAPPLY_MAX_*
+
+
+def checked_flux(who, flux, nsrc, nfine=None, quiet=False):
+    """The fluxes of a block's `nsrc` > 0 sources, float64 [nsrc] or [nfine][nsrc], finite and >= 0 (`nfine`: of the sequence being
+    read, None before the first); else ValueError, or None if `quiet`."""
+    try:
+        F = np.asarray(flux, np.float64)
+        ok = nsrc > 0 and F.ndim in (1, 2) and F.shape[-1] == nsrc and F.size > 0 and bool(np.all(np.isfinite(F))) and bool(F.min() >= 0)
+        if ok and F.ndim == 2 and nfine is not None:
+            ok = F.shape[0] == nfine
+    except (TypeError, ValueError):
+        F, ok = None, False
+    if ok:
+        return F
+    if quiet:
+        return None
+    raise ValueError("%s: the fluxes must be [%d] or [nfine][%d] finite numbers >= 0" % (who, nsrc, nsrc))
+
+
 def _gains(g, V=None):
     g = np.asarray(g, np.complex128)
     if g.ndim != 3 or g.shape[1] != 2 or (V is not None and (V.ndim != 5 or V.shape != (g.shape[0], g.shape[2], 2, g.shape[2], 2))):

@@ -79,6 +79,58 @@ def stokes_i(image):
     return image[..., 0, :] + image[..., 1, :]
 
 
+# ---- what the readers of UpchanCorr's ring (UpchanImage, UpchanGainCal, UpchanCalApply) and of UpchanImage's (UpchanClean) share
+def check_fine_axis(who, ihdr):
+    """The fine-channel frequencies (fine_sfreq, fine_bw_hz) and the integration length of a header; returns acc_len."""
+    for k in ('fine_sfreq', 'fine_bw_hz'):
+        v = ihdr.get(k)
+        if not isinstance(v, (int, float)) or isinstance(v, bool) or not np.isfinite(v) or (k == 'fine_bw_hz' and not v > 0):
+            raise ValueError("%s: the header's '%s' is %r" % (who, k, v))
+    acc_len = ihdr.get('acc_len', 1)
+    if not isinstance(acc_len, int) or isinstance(acc_len, bool) or acc_len <= 0:
+        raise ValueError("%s: the header's 'acc_len' is %r" % (who, acc_len))
+    return acc_len
+
+
+def check_visibility_header(who, ihdr, nstand, reject=()):
+    """The header of UpchanCorr's dual-polarisation cf32 visibilities of `nstand` stands, with none of the keys in `reject` (what
+    a block that has consumed visibilities adds); returns (nfine, acc_len)."""
+    if ihdr.get('npol') != 2:
+        raise ValueError("%s: npol %r in the header: dual-polarisation visibilities only" % (who, ihdr.get('npol')))
+    if ihdr.get('nstand') != nstand:
+        raise ValueError("%s: %r stands in the header, positions for %d" % (who, ihdr.get('nstand'), nstand))
+    if ihdr.get('nbit') != 32 or not ihdr.get('complex'):
+        raise ValueError("%s: the input is not cf32 visibilities (nbit %r, complex %r)" % (who, ihdr.get('nbit'), ihdr.get('complex')))
+    if any(k in ihdr for k in reject):
+        raise ValueError("%s: the input carries %s: it is an image or a gain solution, not visibilities" % (who, " or ".join("'%s'" % k for k in reject)))
+    nfine = ihdr.get('nfine')
+    if not isinstance(nfine, int) or isinstance(nfine, bool) or nfine <= 0:
+        raise ValueError("%s: the header's 'nfine' is %r: not UpchanCorr's visibilities" % (who, nfine))
+    return nfine, check_fine_axis(who, ihdr)
+
+
+def fine_frequencies(ihdr, nfine):
+    """The fine channels' centre frequencies of a sequence, float64 [nfine] Hz."""
+    return np.ascontiguousarray(ihdr['fine_sfreq'] + ihdr['fine_bw_hz'] * np.arange(nfine, dtype=np.float64))
+
+
+def checked_weights(who, w, nstand, pair=None, quiet=False):
+    """Per-stand weights as the library takes them, f32 [nstand], finite and >= 0 and, with pair = (autos, nfavg), leaving a pair
+    of stands for image_norm; else ValueError, or None if `quiet`."""
+    try:
+        a = np.ascontiguousarray(w, np.float32).reshape(-1)
+        ok = a.size == nstand and bool(np.all(np.isfinite(a))) and bool(a.min() >= 0)
+        if ok and pair is not None:
+            image_norm(a, *pair)
+    except (TypeError, ValueError):
+        a, ok = None, False
+    if ok:
+        return a
+    if quiet:
+        return None
+    raise ValueError("%s: the weights must be %d finite numbers >= 0%s" % (who, nstand, " that leave a pair of stands" if pair is not None else ""))
+
+
 # ---- Hogbom CLEAN of the dirty images (UpchanClean; include/xeng.h "Hogbom CLEAN of the dirty images")
 CLEAN_COMPONENT = np.dtype([('pixel', '<i4'), ('I', '<f4'), ('C', '<f4', (4,)), ('pad', '<u4', (2,))])      # 32 bytes: one record
 CLEAN_STATS = np.dtype([('ncomp', '<i4'), ('reason', '<i4'), ('peak', '<f4'), ('pad', '<u4')])              # 16 bytes per channel group

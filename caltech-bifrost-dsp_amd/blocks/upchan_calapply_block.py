@@ -22,18 +22,14 @@ from UpchanImage at the sources' directions and calls set_flux), direction-depen
 life, cross-hand model terms.
 """
 import json
-import time
 from threading import Lock
 
 import numpy as np
 
 from ..backend import default_backend
-from ..ndarray import XArray
-from .block_base import Block, InFlight, declare_streams, gulp_time, spans_outlive_release
-from .calibration import inverse_gains, model_flux
-from .imaging import steering_delays
-
-MAX_NSRC, MAX_NSTAND = 32, 512          # include/xeng.h XENG_CALAPPLY_MAX_*
+from .block_base import Block, InFlight, SpanLoop, declare_streams, spans_outlive_release
+from .calibration import MAX_NSRC, MAX_NSTAND, checked_flux, inverse_gains, model_flux
+from .imaging import check_visibility_header, fine_frequencies, steering_delays
 
 
 class UpchanCalApply(Block):
@@ -95,18 +91,7 @@ class UpchanCalApply(Block):
 
     def _checked_flux(self, flux, quiet=False):
         """float64 [nsrc] or [nfine][nsrc], finite and >= 0 (nfine is checked against the sequence); else ValueError or None."""
-        try:
-            F = np.asarray(flux, np.float64)
-            ok = self.nsrc > 0 and F.ndim in (1, 2) and F.shape[-1] == self.nsrc and F.size > 0 and bool(np.all(np.isfinite(F))) and bool(F.min() >= 0)
-            if ok and F.ndim == 2 and self._nfine is not None:
-                ok = F.shape[0] == self._nfine
-        except (TypeError, ValueError):
-            F, ok = None, False
-        if ok:
-            return F
-        if quiet:
-            return None
-        raise ValueError("UPCHAN_CALAPPLY: the fluxes must be [%d] or [nfine][%d] finite numbers >= 0" % (self.nsrc, self.nsrc))
+        return checked_flux("UPCHAN_CALAPPLY", flux, self.nsrc, self._nfine, quiet)
 
     def set_gains(self, g):
         """A gain solution [nfine][2][nstand] (UpchanGainCal's output span) from the next integration on: the factors are
@@ -130,36 +115,15 @@ class UpchanCalApply(Block):
     def _check_header(self, ihdr):
         """UpchanCorr's output, or this block's own; returns (nfine, acc_len)."""
         who = "UPCHAN_CALAPPLY"
-        if ihdr.get('npol') != 2:
-            raise ValueError("%s: npol %r in the header: dual-polarisation visibilities only" % (who, ihdr.get('npol')))
-        if ihdr.get('nstand') != self.nstand:
-            raise ValueError("%s: %r stands in the header, positions for %d" % (who, ihdr.get('nstand'), self.nstand))
-        if ihdr.get('nbit') != 32 or not ihdr.get('complex'):
-            raise ValueError("%s: the input is not cf32 visibilities (nbit %r, complex %r)" % (who, ihdr.get('nbit'), ihdr.get('complex')))
-        if 'npix' in ihdr or 'nsrc' in ihdr:
-            raise ValueError("%s: the input carries 'npix' or 'nsrc': it is an image or a gain solution, not visibilities" % who)
-        nfine = ihdr.get('nfine')
-        if not isinstance(nfine, int) or isinstance(nfine, bool) or nfine <= 0:
-            raise ValueError("%s: the header's 'nfine' is %r: not UpchanCorr's visibilities" % (who, nfine))
+        nfine, acc_len = check_visibility_header(who, ihdr, self.nstand, reject=('npix', 'nsrc'))
         if self._flux.ndim == 2 and self._flux.shape[0] != nfine:
             raise ValueError("%s: fluxes for %d fine channels, the header's nfine is %d" % (who, self._flux.shape[0], nfine))
         if self._factors is not None and self._factors.shape[0] != nfine:
             raise ValueError("%s: factors for %d fine channels, the header's nfine is %d" % (who, self._factors.shape[0], nfine))
-        for k in ('fine_sfreq', 'fine_bw_hz'):
-            v = ihdr.get(k)
-            if not isinstance(v, (int, float)) or isinstance(v, bool) or not np.isfinite(v) or (k == 'fine_bw_hz' and not v > 0):
-                raise ValueError("%s: the header's '%s' is %r" % (who, k, v))
-        acc_len = ihdr.get('acc_len', 1)
-        if not isinstance(acc_len, int) or isinstance(acc_len, bool) or acc_len <= 0:
-            raise ValueError("%s: the header's 'acc_len' is %r" % (who, acc_len))
         nsub = ihdr.get('nsubtracted', 0)
         if not isinstance(nsub, int) or isinstance(nsub, bool) or nsub < 0:
             raise ValueError("%s: the header's 'nsubtracted' is %r" % (who, nsub))
         return nfine, acc_len
-
-    def frequencies(self, ihdr, nfine):
-        """The fine channels' centre frequencies of a sequence, float64 [nfine] Hz."""
-        return np.ascontiguousarray(ihdr['fine_sfreq'] + ihdr['fine_bw_hz'] * np.arange(nfine, dtype=np.float64))
 
     def output_header(self, ihdr, start):
         ohdr = ihdr.copy()
@@ -168,9 +132,9 @@ class UpchanCalApply(Block):
 
     def _set_model(self, ihdr, nfine):
         if self.nsrc:
-            self._call('calapply_set_model', self.tau, self.frequencies(ihdr, nfine), np.ascontiguousarray(model_flux(self._flux, nfine, self.nsrc), np.float32))
+            self._call('calapply_set_model', self.tau, fine_frequencies(ihdr, nfine), np.ascontiguousarray(model_flux(self._flux, nfine, self.nsrc), np.float32))
         else:
-            self._call('calapply_set_model', None, self.frequencies(ihdr, nfine), None)
+            self._call('calapply_set_model', None, fine_frequencies(ihdr, nfine), None)
 
     def _set_factors(self, nfine):
         self._call('calapply_set_factors', self._factors if self._factors is not None else np.ones((nfine, 2, self.nstand), np.complex64))
@@ -181,15 +145,7 @@ class UpchanCalApply(Block):
         with self._next_lock:
             nxt, self._next = self._next, {}
         if self.update_pending:
-            self.update_command_vals()
-            with self._control_lock:
-                # a command is taken once: left in place, a later command for another key would bring it back over a set_*() since
-                cmd = self.command_vals.get('flux')
-                if cmd is not None:
-                    nxt['flux'] = cmd
-                    self.command_vals['flux'] = None
-                    if self._pending_command_vals.get('flux') is cmd:
-                        self._pending_command_vals['flux'] = None
+            nxt.update(self.take_commands(('flux',)))
         if 'factors' in nxt:
             h = self._checked_factors(nxt['factors'], quiet=True)
             if h is None:
@@ -207,17 +163,19 @@ class UpchanCalApply(Block):
 
     def main(self):
         self.bind()
-        # Streaming and tickets: InFlight (block_base.py).  The span size follows the header's nfine: the ring is sized per sequence.
+        # Streaming and tickets: InFlight, the loop over the spans: SpanLoop (block_base.py).  The span size follows the header's
+        # nfine: the ring is sized per sequence.
         streaming = spans_outlive_release(self.iring, self.oring)
-        with InFlight(self._bf.calapply_wait, self._bf.calapply_sync) as inflight, self.oring.begin_writing() as oring:
+        with InFlight(self._bf.calapply_wait, self._bf.calapply_sync, mark=self._bf.calapply_mark) as inflight, self.oring.begin_writing() as oring:
+            loop = SpanLoop(self, "UPCHAN_CALAPPLY", inflight, oring, streaming)
             for iseq in self.iring.read(guarantee=self.guarantee):
-                self._sequence(iseq, oring, streaming, inflight)
+                self._sequence(iseq, loop)
 
-    def _sequence(self, iseq, oring, streaming, inflight):
+    def _sequence(self, iseq, loop):
         ihdr = json.loads(iseq.header.tostring())
         self.sequence_proclog.update(ihdr)
         nfine, acc_len = self._check_header(ihdr)
-        inflight.retire(0)
+        loop.inflight.retire(0)
         if self._ctx != (self.nstand, nfine):
             self._call('calapply_initialize', self.gpu, self.nstand, nfine, self.nsrc)
             self._ctx = (self.nstand, nfine)
@@ -226,57 +184,13 @@ class UpchanCalApply(Block):
         self._set_model(ihdr, nfine)            # (the frequencies are the sequence's)
         gulp_size = nfine * (2 * self.nstand) ** 2 * 8
         self.oring.resize(gulp_size)
-        dev = None if streaming else XArray(shape=(gulp_size,), dtype=np.uint8, space=self._bf.space_in)
-        seq0 = ihdr['seq0']
-        this_gulp_time = seq0
-        expected = seq0
-        oseq = None
-        try:
-            prev_time = time.time()
-            for ispan in iseq.read(gulp_size):
-                if ispan.size < gulp_size:
-                    continue                    # a short final span is skipped (as the reference's gulp_nframe reader does)
-                this_gulp_time = gulp_time(ispan, seq0, gulp_size, acc_len, this_gulp_time)
-                if this_gulp_time != expected:
-                    # integrations this reader never saw: the output goes on in a sequence of its own
-                    self.update_stats({'ngap': self.stats['ngap'] + 1})
-                    self.log.warning("UPCHAN_CALAPPLY >> samples [%d, %d) were not read" % (expected, this_gulp_time))
-                    if oseq is not None:
-                        inflight.retire(0)
-                        oseq.end()
-                        oseq = None
-                expected = this_gulp_time + acc_len
-                self.update_stats({'curr_sample': this_gulp_time})
-                if self.update_pending or self._next:
-                    self._load_pending(ihdr, nfine)
-                held = ispan.data
-                if oseq is None:
-                    oseq = oring.begin_sequence(time_tag=this_gulp_time, header=json.dumps(self.output_header(ihdr, this_gulp_time)))
-                curr_time = time.time()
-                acquire_time = curr_time - prev_time
-                prev_time = curr_time
-                ospan = oseq.reserve(gulp_size)
-                try:
-                    self._call('calapply_run', held, ospan.data if streaming else dev)
-                    self.update_stats({'napply': self.stats['napply'] + 1, 'last_end_sample': this_gulp_time + acc_len})
-                    osp, ospan = ospan, None
-                    if streaming:
-                        inflight.push(self._bf.calapply_mark(), osp, held)
-                        inflight.retire(self.STREAM_DEPTH)
-                    else:
-                        self._bf.calapply_sync()
-                        try:
-                            osp.data_view(np.uint8).reshape(-1)[...] = dev               # (synchronous copy)
-                        finally:
-                            osp.close()
-                finally:
-                    if ospan is not None:
-                        ospan.close()
-                curr_time = time.time()
-                process_time = curr_time - prev_time
-                prev_time = curr_time
-                self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
-        finally:
-            inflight.retire(0)                  # every call in flight is complete (and every output span committed) first
-            if oseq is not None:
-                oseq.end()
+
+        def pending(t):
+            if self.update_pending or self._next:
+                self._load_pending(ihdr, nfine)
+
+        def apply(t, held, out):
+            self._call('calapply_run', held, out.target())
+            return {'napply': self.stats['napply'] + 1}
+
+        loop.run(iseq, ihdr['seq0'], gulp_size, acc_len, gulp_size, lambda t: self.output_header(ihdr, t), apply, before=pending)

@@ -22,15 +22,13 @@ ngroup of a shallower run is not written.  A gap in the input loses nothing but 
 sequence of its own.  No reference counterpart.
 """
 import json
-import time
 from threading import Lock
 
 import numpy as np
 
 from ..backend import default_backend
-from ..ndarray import XArray
-from .block_base import Block, InFlight, declare_streams, gulp_time, spans_outlive_release
-from .imaging import clean_layout, image_norm, steering_delays
+from .block_base import RESTART, Block, InFlight, SpanLoop, declare_streams, spans_outlive_release
+from .imaging import check_fine_axis, checked_weights, clean_layout, fine_frequencies, image_norm, steering_delays
 
 MAX_NITER = 4096        # XENG_CLEAN_MAX_NITER
 
@@ -75,18 +73,7 @@ class UpchanClean(Block):
     # ------------------------------------------------------------------ checked arguments
     def _checked_weights(self, w, quiet=False):
         """f32 [nstand], finite and >= 0, with two stands left (a pair whatever the header's autos); else ValueError, or None if `quiet`."""
-        try:
-            a = np.ascontiguousarray(w, np.float32).reshape(-1)
-            ok = a.size == self.nstand and bool(np.all(np.isfinite(a))) and bool(a.min() >= 0)
-            if ok:
-                image_norm(a, False, 1)
-        except (TypeError, ValueError):
-            a, ok = None, False
-        if ok:
-            return a
-        if quiet:
-            return None
-        raise ValueError("UPCHAN_CLEAN: the weights must be %d finite numbers >= 0 that leave a pair of stands" % self.nstand)
+        return checked_weights("UPCHAN_CLEAN", w, self.nstand, (False, 1), quiet)
 
     def _checked_window(self, window):
         if window is None:
@@ -147,13 +134,7 @@ class UpchanClean(Block):
             raise ValueError("%s: the header's nfavg %d does not divide its nfine %d" % (who, nfavg, nfine))
         if not isinstance(ihdr.get('autos'), bool):
             raise ValueError("%s: the header's 'autos' is %r" % (who, ihdr.get('autos')))
-        for k in ('fine_sfreq', 'fine_bw_hz'):
-            v = ihdr.get(k)
-            if not isinstance(v, (int, float)) or isinstance(v, bool) or not np.isfinite(v) or (k == 'fine_bw_hz' and not v > 0):
-                raise ValueError("%s: the header's '%s' is %r" % (who, k, v))
-        acc_len = ihdr.get('acc_len', 1)
-        if not isinstance(acc_len, int) or isinstance(acc_len, bool) or acc_len <= 0:
-            raise ValueError("%s: the header's 'acc_len' is %r" % (who, acc_len))
+        acc_len = check_fine_axis(who, ihdr)
         if ihdr.get('cleaned'):
             so = ihdr.get('stats_offset')
             if not isinstance(so, int) or isinstance(so, bool) or so < 16 * (nfine // nfavg) * self.npix:
@@ -166,10 +147,6 @@ class UpchanClean(Block):
         if ihdr.get('cleaned'):
             return max(ihdr['stats_offset'] + 16 * ngroup, ihdr.get('span_bytes', 0))
         return ngroup * 4 * self.npix * 4
-
-    def frequencies(self, ihdr, nfine):
-        """The fine channels' centre frequencies of a sequence, float64 [nfine] Hz."""
-        return np.ascontiguousarray(ihdr['fine_sfreq'] + ihdr['fine_bw_hz'] * np.arange(nfine, dtype=np.float64))
 
     def output_header(self, ihdr, start, ngroup, span_bytes):
         niter, gain, threshold, fraction = self._control
@@ -187,16 +164,7 @@ class UpchanClean(Block):
             nxt, self._next = self._next, {}
         w, control = nxt.get('weights'), nxt.get('control', self._control)
         if self.update_pending:
-            self.update_command_vals()
-            self.acquire_control_lock()
-            try:
-                cmd = dict(self.command_vals)
-                for k in ('weights', 'niter', 'gain', 'threshold'):     # a command is taken once: a later one does not bring it back
-                    if self._pending_command_vals[k] is cmd[k]:
-                        self._pending_command_vals[k] = None
-                    self.command_vals[k] = None
-            finally:
-                self.release_control_lock()
+            cmd = self.take_commands(('weights', 'niter', 'gain', 'threshold'))
             if cmd.get('weights') is not None:
                 w = self._checked_weights(cmd['weights'])
             new = [cmd.get('niter'), cmd.get('gain'), cmd.get('threshold'), None]
@@ -215,13 +183,15 @@ class UpchanClean(Block):
 
     def main(self):
         self.bind()
-        # Streaming and tickets: InFlight (block_base.py).  The output size follows the header's nfine: the ring is sized per sequence.
+        # Streaming and tickets: InFlight, the loop over the spans: SpanLoop (block_base.py).  The output size follows the header's
+        # nfine: the ring is sized per sequence.
         streaming = spans_outlive_release(self.iring, self.oring)
-        with InFlight(self._bf.clean_wait, self._bf.clean_sync) as inflight, self.oring.begin_writing() as oring:
+        with InFlight(self._bf.clean_wait, self._bf.clean_sync, mark=self._bf.clean_mark) as inflight, self.oring.begin_writing() as oring:
+            loop = SpanLoop(self, "UPCHAN_CLEAN", inflight, oring, streaming)
             for iseq in self.iring.read(guarantee=self.guarantee):
-                self._sequence(iseq, oring, streaming, inflight)
+                self._sequence(iseq, loop)
 
-    def _sequence(self, iseq, oring, streaming, inflight):
+    def _sequence(self, iseq, loop):
         ihdr = json.loads(iseq.header.tostring())
         self.sequence_proclog.update(ihdr)
         nfine, nfavg, autos, acc_len = self._check_header(ihdr)
@@ -229,7 +199,7 @@ class UpchanClean(Block):
             image_norm(self._weights, autos, nfavg)
         except ValueError as e:
             raise ValueError("UPCHAN_CLEAN: %s" % e)
-        inflight.retire(0)
+        loop.inflight.retire(0)
         self._autos = autos
         if self._ctx != (self.nstand, nfine, nfavg):
             self._call('clean_initialize', self.gpu, self.nstand, nfine, nfavg, self.npix, self.niter_max)
@@ -237,64 +207,19 @@ class UpchanClean(Block):
             self._call('clean_set_window', self._window)
             self._call('clean_set_control', *self._control)
         self._call('clean_set_weights', self._weights, autos)
-        self._call('clean_set_geometry', self.tau, self.frequencies(ihdr, nfine))
+        self._call('clean_set_geometry', self.tau, fine_frequencies(ihdr, nfine))
         ngroup = nfine // nfavg
         ogulp_size = clean_layout(ngroup, self.niter_max, self.npix)[2]
         self.oring.resize(ogulp_size)
-        dev = None if streaming else XArray(shape=(ogulp_size,), dtype=np.uint8, space=self._bf.space_in)
-        seq0 = ihdr['seq0']
-        igulp_size = self.input_span_bytes(ihdr, nfine, nfavg)
-        this_gulp_time = seq0
-        expected = seq0
-        oseq = None
-        try:
-            prev_time = time.time()
-            for ispan in iseq.read(igulp_size):
-                if ispan.size < igulp_size:
-                    continue                    # a short final span is skipped (as the reference's gulp_nframe reader does)
-                this_gulp_time = gulp_time(ispan, seq0, igulp_size, acc_len, this_gulp_time)
-                if this_gulp_time != expected:
-                    # integrations this reader never saw: nothing is carried from one to the next, only the time axis breaks
-                    self.update_stats({'ngap': self.stats['ngap'] + 1})
-                    self.log.warning("UPCHAN_CLEAN >> samples [%d, %d) were not read" % (expected, this_gulp_time))
-                    if oseq is not None:
-                        inflight.retire(0)
-                        oseq.end()
-                        oseq = None
-                expected = this_gulp_time + acc_len
-                self.update_stats({'curr_sample': this_gulp_time})
-                if (self.update_pending or self._next) and self._load_pending() and oseq is not None:
-                    inflight.retire(0)          # another control: a sequence of its own, whose header says so
-                    oseq.end()
-                    oseq = None
-                held = ispan.data
-                if oseq is None:
-                    oseq = oring.begin_sequence(time_tag=this_gulp_time, header=json.dumps(self.output_header(ihdr, this_gulp_time, ngroup, ogulp_size)))
-                curr_time = time.time()
-                acquire_time = curr_time - prev_time
-                prev_time = curr_time
-                ospan = oseq.reserve(ogulp_size)
-                try:
-                    self._call('clean_run', held, ospan.data if streaming else dev)
-                    self.update_stats({'nclean': self.stats['nclean'] + 1, 'last_end_sample': this_gulp_time + acc_len})
-                    osp, ospan = ospan, None
-                    if streaming:
-                        inflight.push(self._bf.clean_mark(), osp, held)
-                        inflight.retire(self.STREAM_DEPTH)
-                    else:
-                        self._bf.clean_sync()
-                        try:
-                            osp.data_view(np.uint8).reshape(ogulp_size)[...] = dev          # (synchronous copy)
-                        finally:
-                            osp.close()
-                finally:
-                    if ospan is not None:
-                        ospan.close()
-                curr_time = time.time()
-                process_time = curr_time - prev_time
-                prev_time = curr_time
-                self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
-        finally:
-            inflight.retire(0)                  # every call in flight is complete (and every output span committed) first
-            if oseq is not None:
-                oseq.end()
+
+        def pending(t):
+            if (self.update_pending or self._next) and self._load_pending():
+                return RESTART                  # another control: a sequence of its own, whose header says so
+
+        def clean(t, held, out):
+            self._call('clean_run', held, out.target())
+            return {'nclean': self.stats['nclean'] + 1}
+
+        # (nothing is carried from one integration to the next: a gap only breaks the time axis)
+        loop.run(iseq, ihdr['seq0'], self.input_span_bytes(ihdr, nfine, nfavg), acc_len, ogulp_size,
+                 lambda t: self.output_header(ihdr, t, ngroup, ogulp_size), clean, before=pending)

@@ -19,18 +19,16 @@ every span's time follows from its place, and forces a cold start.  set_weights(
 `weights`, `refant` and `flux`) take effect at the next integration; each forgets the warm start.
 """
 import json
-import time
 from threading import Lock
 
 import numpy as np
 
 from ..backend import default_backend
-from ..ndarray import XArray
-from .block_base import Block, InFlight, declare_streams, gulp_time, spans_outlive_release
-from .calibration import model_flux
-from .imaging import steering_delays
+from .block_base import RESTART, Block, InFlight, SpanLoop, declare_streams, spans_outlive_release
+from .calibration import MAX_NSRC, MAX_NSTAND, checked_flux, model_flux
+from .imaging import check_visibility_header, checked_weights, fine_frequencies, steering_delays
 
-MAX_NSRC, MAX_NSTAND, MAX_NITER = 32, 512, 1024        # include/xeng.h XENG_GAINCAL_MAX_*
+MAX_NITER = 1024        # include/xeng.h XENG_GAINCAL_MAX_NITER
 
 
 class UpchanGainCal(Block):
@@ -52,6 +50,7 @@ class UpchanGainCal(Block):
         if isinstance(tol, bool) or not isinstance(tol, (int, float, np.floating)) or not np.isfinite(tol) or tol < 0:
             raise ValueError("%s: tol %r is not a finite number >= 0" % (who, tol))
         self.niter, self.tol, self.warm_start, self.gpu = int(niter), float(tol), bool(warm_start), gpu
+        self._nfine = None                      # of the sequence being read
         self._flux = self._checked_flux(flux)               # [nsrc] or [nfine][nsrc], float64
         self._weights = self._checked_weights(np.ones(self.nstand, np.float32) if weights is None else weights)
         self._refant = self._checked_refant(refant, self._weights)
@@ -67,20 +66,11 @@ class UpchanGainCal(Block):
         self.define_command_key('flux', type=list, condition=lambda v: self._checked_flux(v, quiet=True) is not None)
         self.update_stats({'nsolve': 0, 'ngap': 0})
         self._ctx = None                        # (nstand, nfine) of the live context
-        self._nfine = None
+        self._warm = False                      # the integration before this one was solved, in this output sequence
 
     def _checked_weights(self, w, quiet=False):
         """f32 [nstand], finite and >= 0; else ValueError, or None if `quiet`."""
-        try:
-            a = np.ascontiguousarray(w, np.float32).reshape(-1)
-            ok = a.size == self.nstand and bool(np.all(np.isfinite(a))) and bool(a.min() >= 0)
-        except (TypeError, ValueError):
-            a, ok = None, False
-        if ok:
-            return a
-        if quiet:
-            return None
-        raise ValueError("UPCHAN_GAINCAL: the weights must be %d finite numbers >= 0" % self.nstand)
+        return checked_weights("UPCHAN_GAINCAL", w, self.nstand, quiet=quiet)
 
     def _checked_refant(self, refant, w):
         if isinstance(refant, bool) or not isinstance(refant, (int, np.integer)) or not 0 <= refant < self.nstand:
@@ -91,18 +81,7 @@ class UpchanGainCal(Block):
 
     def _checked_flux(self, flux, quiet=False):
         """float64 [nsrc] or [nfine][nsrc], finite and >= 0 (nfine is checked against the sequence); else ValueError or None."""
-        try:
-            F = np.asarray(flux, np.float64)
-            ok = F.ndim in (1, 2) and F.shape[-1] == self.nsrc and F.size > 0 and bool(np.all(np.isfinite(F))) and bool(F.min() >= 0)
-            if ok and F.ndim == 2 and getattr(self, '_nfine', None) is not None:
-                ok = F.shape[0] == self._nfine
-        except (TypeError, ValueError):
-            F, ok = None, False
-        if ok:
-            return F
-        if quiet:
-            return None
-        raise ValueError("UPCHAN_GAINCAL: the fluxes must be [%d] or [nfine][%d] finite numbers >= 0" % (self.nsrc, self.nsrc))
+        return checked_flux("UPCHAN_GAINCAL", flux, self.nsrc, self._nfine, quiet)
 
     def set_weights(self, w):
         """Per-stand weights from the next integration on (0: the stand is not read and its gain is 0)."""
@@ -126,31 +105,10 @@ class UpchanGainCal(Block):
     def _check_header(self, ihdr):
         """UpchanCorr's output only; returns (nfine, acc_len)."""
         who = "UPCHAN_GAINCAL"
-        if ihdr.get('npol') != 2:
-            raise ValueError("%s: npol %r in the header: dual-polarisation visibilities only" % (who, ihdr.get('npol')))
-        if ihdr.get('nstand') != self.nstand:
-            raise ValueError("%s: %r stands in the header, positions for %d" % (who, ihdr.get('nstand'), self.nstand))
-        if ihdr.get('nbit') != 32 or not ihdr.get('complex'):
-            raise ValueError("%s: the input is not cf32 visibilities (nbit %r, complex %r)" % (who, ihdr.get('nbit'), ihdr.get('complex')))
-        if 'npix' in ihdr or 'nsrc' in ihdr:
-            raise ValueError("%s: the input carries 'npix' or 'nsrc': it is an image or a gain solution, not visibilities" % who)
-        nfine = ihdr.get('nfine')
-        if not isinstance(nfine, int) or isinstance(nfine, bool) or nfine <= 0:
-            raise ValueError("%s: the header's 'nfine' is %r: not UpchanCorr's visibilities" % (who, nfine))
+        nfine, acc_len = check_visibility_header(who, ihdr, self.nstand, reject=('npix', 'nsrc'))
         if self._flux.ndim == 2 and self._flux.shape[0] != nfine:
             raise ValueError("%s: fluxes for %d fine channels, the header's nfine is %d" % (who, self._flux.shape[0], nfine))
-        for k in ('fine_sfreq', 'fine_bw_hz'):
-            v = ihdr.get(k)
-            if not isinstance(v, (int, float)) or isinstance(v, bool) or not np.isfinite(v) or (k == 'fine_bw_hz' and not v > 0):
-                raise ValueError("%s: the header's '%s' is %r" % (who, k, v))
-        acc_len = ihdr.get('acc_len', 1)
-        if not isinstance(acc_len, int) or isinstance(acc_len, bool) or acc_len <= 0:
-            raise ValueError("%s: the header's 'acc_len' is %r" % (who, acc_len))
         return nfine, acc_len
-
-    def frequencies(self, ihdr, nfine):
-        """The fine channels' centre frequencies of a sequence, float64 [nfine] Hz."""
-        return np.ascontiguousarray(ihdr['fine_sfreq'] + ihdr['fine_bw_hz'] * np.arange(nfine, dtype=np.float64))
 
     def output_header(self, ihdr, start, nfine):
         ohdr = ihdr.copy()
@@ -159,7 +117,7 @@ class UpchanGainCal(Block):
         return ohdr
 
     def _set_model(self, ihdr, nfine):
-        self._call('gaincal_set_model', self.tau, self.frequencies(ihdr, nfine), np.ascontiguousarray(model_flux(self._flux, nfine, self.nsrc), np.float32))
+        self._call('gaincal_set_model', self.tau, fine_frequencies(ihdr, nfine), np.ascontiguousarray(model_flux(self._flux, nfine, self.nsrc), np.float32))
 
     def _set_weights(self):
         self._call('gaincal_set_weights', self._weights, self._refant)
@@ -171,16 +129,7 @@ class UpchanGainCal(Block):
         with self._next_lock:
             nxt, self._next = self._next, {}
         if self.update_pending:
-            self.update_command_vals()
-            with self._control_lock:
-                # a command is taken once: left in place, a later command for another key would bring it back over a set_*() since
-                for k in ('weights', 'refant', 'flux'):
-                    cmd = self.command_vals.get(k)
-                    if cmd is not None:
-                        nxt[k] = cmd
-                        self.command_vals[k] = None
-                        if self._pending_command_vals.get(k) is cmd:
-                            self._pending_command_vals[k] = None
+            nxt.update(self.take_commands(('weights', 'refant', 'flux')))
         w = self._checked_weights(nxt['weights']) if 'weights' in nxt else self._weights
         ref = nxt.get('refant', self._refant)
         changed = ref != self._refant
@@ -207,17 +156,19 @@ class UpchanGainCal(Block):
 
     def main(self):
         self.bind()
-        # Streaming and tickets: InFlight (block_base.py).  The output size follows the header's nfine: the ring is sized per sequence.
+        # Streaming and tickets: InFlight, the loop over the spans: SpanLoop (block_base.py).  The output size follows the header's
+        # nfine: the ring is sized per sequence.
         streaming = spans_outlive_release(self.iring, self.oring)
-        with InFlight(self._bf.gaincal_wait, self._bf.gaincal_sync) as inflight, self.oring.begin_writing() as oring:
+        with InFlight(self._bf.gaincal_wait, self._bf.gaincal_sync, mark=self._bf.gaincal_mark) as inflight, self.oring.begin_writing() as oring:
+            loop = SpanLoop(self, "UPCHAN_GAINCAL", inflight, oring, streaming)
             for iseq in self.iring.read(guarantee=self.guarantee):
-                self._sequence(iseq, oring, streaming, inflight)
+                self._sequence(iseq, loop)
 
-    def _sequence(self, iseq, oring, streaming, inflight):
+    def _sequence(self, iseq, loop):
         ihdr = json.loads(iseq.header.tostring())
         self.sequence_proclog.update(ihdr)
         nfine, acc_len = self._check_header(ihdr)
-        inflight.retire(0)
+        loop.inflight.retire(0)
         if self._ctx != (self.nstand, nfine):
             self._call('gaincal_initialize', self.gpu, self.nstand, nfine, self.nsrc)
             self._ctx = (self.nstand, nfine)
@@ -225,70 +176,26 @@ class UpchanGainCal(Block):
             self._set_weights()
         self._nfine = nfine
         self._set_model(ihdr, nfine)            # (forgets the warm start: a new sequence starts cold)
+        self._warm = False
         stats_offset = nfine * 2 * self.nstand * 8
         ogulp_size = stats_offset + nfine * 2 * 4 * 4
         self.oring.resize(ogulp_size)
-        dev = None if streaming else XArray(shape=(ogulp_size,), dtype=np.uint8, space=self._bf.space_in)
-        seq0 = ihdr['seq0']
-        igulp_size = nfine * (2 * self.nstand) ** 2 * 8
-        this_gulp_time = seq0
-        expected = seq0
-        oseq = None
-        warm = False                            # the integration before this one was solved, in this output sequence
-        try:
-            prev_time = time.time()
-            for ispan in iseq.read(igulp_size):
-                if ispan.size < igulp_size:
-                    continue                    # a short final span is skipped (as the reference's gulp_nframe reader does)
-                this_gulp_time = gulp_time(ispan, seq0, igulp_size, acc_len, this_gulp_time)
-                if this_gulp_time != expected:
-                    # integrations this reader never saw: the kept solution is older than one integration, so the next one starts cold
-                    self.update_stats({'ngap': self.stats['ngap'] + 1})
-                    self.log.warning("UPCHAN_GAINCAL >> samples [%d, %d) were not read" % (expected, this_gulp_time))
-                    warm = False
-                    if oseq is not None:
-                        inflight.retire(0)
-                        oseq.end()
-                        oseq = None
-                expected = this_gulp_time + acc_len
-                self.update_stats({'curr_sample': this_gulp_time})
-                if self.update_pending or self._next:
-                    applied, new_ref = self._load_pending(ihdr, nfine)
-                    if applied:
-                        warm = False            # (SetWeights and SetModel have forgotten the kept solution)
-                    if new_ref and oseq is not None:
-                        inflight.retire(0)      # the header names the reference stand: a sequence of its own from here
-                        oseq.end()
-                        oseq = None
-                held = ispan.data
-                if oseq is None:
-                    oseq = oring.begin_sequence(time_tag=this_gulp_time, header=json.dumps(self.output_header(ihdr, this_gulp_time, nfine)))
-                curr_time = time.time()
-                acquire_time = curr_time - prev_time
-                prev_time = curr_time
-                ospan = oseq.reserve(ogulp_size)
-                try:
-                    self._call('gaincal_run', held, ospan.data if streaming else dev, stats_offset, self.warm_start and warm)
-                    warm = True
-                    self.update_stats({'nsolve': self.stats['nsolve'] + 1, 'last_end_sample': this_gulp_time + acc_len})
-                    osp, ospan = ospan, None
-                    if streaming:
-                        inflight.push(self._bf.gaincal_mark(), osp, held)
-                        inflight.retire(self.STREAM_DEPTH)
-                    else:
-                        self._bf.gaincal_sync()
-                        try:
-                            osp.data_view(np.uint8).reshape(-1)[...] = dev               # (synchronous copy)
-                        finally:
-                            osp.close()
-                finally:
-                    if ospan is not None:
-                        ospan.close()
-                curr_time = time.time()
-                process_time = curr_time - prev_time
-                prev_time = curr_time
-                self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
-        finally:
-            inflight.retire(0)                  # every call in flight is complete (and every output span committed) first
-            if oseq is not None:
-                oseq.end()
+
+        def gap():
+            self._warm = False                  # (the kept solution is older than one integration: the next one starts cold)
+
+        def pending(t):
+            if self.update_pending or self._next:
+                applied, new_ref = self._load_pending(ihdr, nfine)
+                if applied:
+                    self._warm = False          # (SetWeights and SetModel have forgotten the kept solution)
+                if new_ref:
+                    return RESTART              # the header names the reference stand: a sequence of its own from here
+
+        def solve(t, held, out):
+            self._call('gaincal_run', held, out.target(), stats_offset, self.warm_start and self._warm)
+            self._warm = True
+            return {'nsolve': self.stats['nsolve'] + 1}
+
+        loop.run(iseq, ihdr['seq0'], nfine * (2 * self.nstand) ** 2 * 8, acc_len, ogulp_size, lambda t: self.output_header(ihdr, t, nfine), solve,
+                 before=pending, on_gap=gap)

@@ -17,15 +17,13 @@ so that every span's time follows from its place.  set_weights(w) (or a `weights
 at the next integration.
 """
 import json
-import time
 from threading import Lock
 
 import numpy as np
 
 from ..backend import default_backend
-from ..ndarray import XArray
-from .block_base import Block, InFlight, declare_streams, gulp_time, spans_outlive_release
-from .imaging import image_norm, steering_delays
+from .block_base import Block, InFlight, SpanLoop, declare_streams, spans_outlive_release
+from .imaging import check_visibility_header, checked_weights, fine_frequencies, steering_delays
 
 
 class UpchanImage(Block):
@@ -57,18 +55,7 @@ class UpchanImage(Block):
 
     def _checked_weights(self, w, quiet=False):
         """f32 [nstand], finite and >= 0, leaving a pair of stands; else ValueError, or None if `quiet`."""
-        try:
-            a = np.ascontiguousarray(w, np.float32).reshape(-1)
-            ok = a.size == self.nstand and bool(np.all(np.isfinite(a))) and bool(a.min() >= 0)
-            if ok:
-                image_norm(a, self.autos, self.nfavg)
-        except (TypeError, ValueError):
-            a, ok = None, False
-        if ok:
-            return a
-        if quiet:
-            return None
-        raise ValueError("UPCHAN_IMAGE: the weights must be %d finite numbers >= 0 that leave a pair of stands" % self.nstand)
+        return checked_weights("UPCHAN_IMAGE", w, self.nstand, (self.autos, self.nfavg), quiet)
 
     def set_weights(self, w):
         """Per-stand weights from the next integration on (0: the stand is not read)."""
@@ -79,31 +66,12 @@ class UpchanImage(Block):
     def _check_header(self, ihdr):
         """UpchanCorr's output only; returns (nfine, acc_len)."""
         who = "UPCHAN_IMAGE"
-        if ihdr.get('npol') != 2:
-            raise ValueError("%s: npol %r in the header: dual-polarisation visibilities only" % (who, ihdr.get('npol')))
-        if ihdr.get('nstand') != self.nstand:
-            raise ValueError("%s: %r stands in the header, positions for %d" % (who, ihdr.get('nstand'), self.nstand))
-        if ihdr.get('nbit') != 32 or not ihdr.get('complex'):
-            raise ValueError("%s: the input is not cf32 visibilities (nbit %r, complex %r)" % (who, ihdr.get('nbit'), ihdr.get('complex')))
         if 'npix' in ihdr:
             raise ValueError("%s: the input carries 'npix': it has been imaged already" % who)
-        nfine = ihdr.get('nfine')
-        if not isinstance(nfine, int) or isinstance(nfine, bool) or nfine <= 0:
-            raise ValueError("%s: the header's 'nfine' is %r: not UpchanCorr's visibilities" % (who, nfine))
+        nfine, acc_len = check_visibility_header(who, ihdr, self.nstand)
         if nfine % self.nfavg:
             raise ValueError("%s: nfavg %d does not divide the header's nfine %d" % (who, self.nfavg, nfine))
-        for k in ('fine_sfreq', 'fine_bw_hz'):
-            v = ihdr.get(k)
-            if not isinstance(v, (int, float)) or isinstance(v, bool) or not np.isfinite(v) or (k == 'fine_bw_hz' and not v > 0):
-                raise ValueError("%s: the header's '%s' is %r" % (who, k, v))
-        acc_len = ihdr.get('acc_len', 1)
-        if not isinstance(acc_len, int) or isinstance(acc_len, bool) or acc_len <= 0:
-            raise ValueError("%s: the header's 'acc_len' is %r" % (who, acc_len))
         return nfine, acc_len
-
-    def frequencies(self, ihdr, nfine):
-        """The fine channels' centre frequencies of a sequence, float64 [nfine] Hz."""
-        return np.ascontiguousarray(ihdr['fine_sfreq'] + ihdr['fine_bw_hz'] * np.arange(nfine, dtype=np.float64))
 
     def output_header(self, ihdr, start, nfine):
         ohdr = ihdr.copy()
@@ -130,77 +98,35 @@ class UpchanImage(Block):
 
     def main(self):
         self.bind()
-        # Streaming and tickets: InFlight (block_base.py).  The output size follows the header's nfine: the ring is sized per sequence.
+        # Streaming and tickets: InFlight, the loop over the spans: SpanLoop (block_base.py).  The output size follows the header's
+        # nfine: the ring is sized per sequence.
         streaming = spans_outlive_release(self.iring, self.oring)
-        with InFlight(self._bf.image_wait, self._bf.image_sync) as inflight, self.oring.begin_writing() as oring:
+        with InFlight(self._bf.image_wait, self._bf.image_sync, mark=self._bf.image_mark) as inflight, self.oring.begin_writing() as oring:
+            loop = SpanLoop(self, "UPCHAN_IMAGE", inflight, oring, streaming)
             for iseq in self.iring.read(guarantee=self.guarantee):
-                self._sequence(iseq, oring, streaming, inflight)
+                self._sequence(iseq, loop)
 
-    def _sequence(self, iseq, oring, streaming, inflight):
+    def _sequence(self, iseq, loop):
         ihdr = json.loads(iseq.header.tostring())
         self.sequence_proclog.update(ihdr)
         nfine, acc_len = self._check_header(ihdr)
-        inflight.retire(0)
+        loop.inflight.retire(0)
         if self._ctx != (self.nstand, nfine):
             self._call('image_initialize', self.gpu, self.nstand, nfine, self.nfavg, self.npix)
             self._ctx = (self.nstand, nfine)
             self._set_weights()
-        self._call('image_set_geometry', self.tau, self.frequencies(ihdr, nfine))
-        oshape = (nfine // self.nfavg, 4, self.npix)
-        ogulp_size = int(np.prod(oshape)) * 4
+        self._call('image_set_geometry', self.tau, fine_frequencies(ihdr, nfine))
+        ogulp_size = (nfine // self.nfavg) * 4 * self.npix * 4
         self.oring.resize(ogulp_size)
-        dev = None if streaming else XArray(shape=oshape, dtype=np.float32, space=self._bf.space_in)
-        seq0 = ihdr['seq0']
-        igulp_size = nfine * (2 * self.nstand) ** 2 * 8
-        this_gulp_time = seq0
-        expected = seq0
-        oseq = None
-        try:
-            prev_time = time.time()
-            for ispan in iseq.read(igulp_size):
-                if ispan.size < igulp_size:
-                    continue                    # a short final span is skipped (as the reference's gulp_nframe reader does)
-                this_gulp_time = gulp_time(ispan, seq0, igulp_size, acc_len, this_gulp_time)
-                if this_gulp_time != expected:
-                    # integrations this reader never saw: nothing is carried from one to the next, only the time axis breaks
-                    self.update_stats({'ngap': self.stats['ngap'] + 1})
-                    self.log.warning("UPCHAN_IMAGE >> samples [%d, %d) were not read" % (expected, this_gulp_time))
-                    if oseq is not None:
-                        inflight.retire(0)
-                        oseq.end()
-                        oseq = None
-                expected = this_gulp_time + acc_len
-                self.update_stats({'curr_sample': this_gulp_time})
-                if self.update_pending or self._next_weights is not None:
-                    self._load_pending_weights()
-                held = ispan.data
-                if oseq is None:
-                    oseq = oring.begin_sequence(time_tag=this_gulp_time, header=json.dumps(self.output_header(ihdr, this_gulp_time, nfine)))
-                curr_time = time.time()
-                acquire_time = curr_time - prev_time
-                prev_time = curr_time
-                ospan = oseq.reserve(ogulp_size)
-                try:
-                    self._call('image_run', held, ospan.data if streaming else dev)
-                    self.update_stats({'nimage': self.stats['nimage'] + 1, 'last_end_sample': this_gulp_time + acc_len})
-                    osp, ospan = ospan, None
-                    if streaming:
-                        inflight.push(self._bf.image_mark(), osp, held)
-                        inflight.retire(self.STREAM_DEPTH)
-                    else:
-                        self._bf.image_sync()
-                        try:
-                            osp.data_view(np.float32).reshape(oshape)[...] = dev        # (synchronous copy)
-                        finally:
-                            osp.close()
-                finally:
-                    if ospan is not None:
-                        ospan.close()
-                curr_time = time.time()
-                process_time = curr_time - prev_time
-                prev_time = curr_time
-                self.perf_proclog.update({'acquire_time': acquire_time, 'reserve_time': 0.0, 'process_time': process_time})
-        finally:
-            inflight.retire(0)                  # every call in flight is complete (and every output span committed) first
-            if oseq is not None:
-                oseq.end()
+
+        def pending(t):
+            if self.update_pending or self._next_weights is not None:
+                self._load_pending_weights()
+
+        def image(t, held, out):
+            self._call('image_run', held, out.target())
+            return {'nimage': self.stats['nimage'] + 1}
+
+        # (nothing is carried from one integration to the next: a gap only breaks the time axis)
+        loop.run(iseq, ihdr['seq0'], nfine * (2 * self.nstand) ** 2 * 8, acc_len, ogulp_size, lambda t: self.output_header(ihdr, t, nfine), image,
+                 before=pending)
