@@ -343,7 +343,9 @@ static int run_slabs(const void* packets0_dev, int npkt0, int ntime0, const void
         XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Beamform: bad slab (npkt %d / %d, stride %zu)", npkt0, npkt1, pkt_stride);
     if (((uintptr_t)weights_dev & 15) || ((uintptr_t)out_dev & 15)) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Beamform: weights/out must be 16-byte aligned");
     if (!packets1_dev) ntime0 = x.ntime;
-    // (parts on 16-sample boundaries: a wave's 16 rows of one load never straddle two descriptors; and whole 16-byte pieces)
+    // (parts on 16-sample boundaries: the 16 rows of one int8x3 LDS-DMA piece never straddle two descriptors, so that kernel takes a
+    // piece's descriptor mode once per wave; a bf16x3 piece is 32 rows and may straddle them -- that kernel selects per lane; and
+    // whole 16-byte pieces)
     if (ntime0 <= 0 || ntime0 > x.ntime || (packets1_dev && (ntime0 == x.ntime || ntime0 % 16)) || x.ninput % 16)
         XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "Beamform: slab parts of %d + %d samples (inputs %d): parts must be multiples of 16 samples, inputs of 16",
                   ntime0, x.ntime - ntime0, x.ninput);

@@ -74,8 +74,9 @@ struct GulpAddr {
             return reinterpret_cast<const uint8_t*>((second ? tab[1] : tab[0]) + (size_t)(second ? t - split : t) * nblk);
         return base + (size_t)(second ? t - split : t) * tstr + (size_t)c * cstr;
     }
-    // TAB: is the part that holds sample t read through its index?  (uniform over the 16 rows of an LDS-DMA piece: parts begin on
-    // 16-sample boundaries)
+    // TAB: is the part that holds sample t read through its index?  Uniform over 16 aligned rows (parts begin on 16-sample
+    // boundaries): the int8x3 kernel, whose LDS-DMA pieces are 16 rows, takes it once per piece (readfirstlane); the bf16x3 kernel
+    // stages 32 rows per piece, which a part boundary may cut in the middle, and asks per lane
     __device__ __forceinline__ bool indexed(int t) const { return TAB && (t >= split ? mode[1] : mode[0]) == 2u; }
     // ... then: the 16 bytes at input i of (sample t, channel c), given the sample's index row (what row() returned) -- in the packet
     // the entry names if it is of this call's generation, else in the page of zeros
@@ -316,9 +317,12 @@ __global__ __launch_bounds__(64 * BF3_NW, BF3_NW == 8 ? 2 : 3) void beamform_bf1
     const GulpAddr<DESC, TAB> ga(in, in1, split, gd, nchan, ninput);
     uint32_t xbstr;
     const uint8_t* xsrc = ga.row(xt, c, &xbstr);
-    // TAB: the part of this wave's rows is read through its index (xsrc: the sample's index row).  The entry is looked up when the
-    // piece is issued -- this kernel only runs the few routed tiles, its staging pipeline is not worth a prefetch register
-    const bool xidx = TAB && __builtin_amdgcn_readfirstlane((int)ga.indexed(xt)) != 0;
+    // TAB: the part of this LANE's row is read through its index (xsrc: the sample's index row).  Per lane, not per wave: a wave stages
+    // 32 rows in one piece and parts begin on 16-sample boundaries, so with a split at 16 mod 32 lanes 0..31 and 32..63 of one wave
+    // lie in different parts, which may be of different modes (one by index, the other the scratch gulp).  xsrc, xbstr and the
+    // generation / base that piece() picks are per lane already.  The entry is looked up when the piece is issued -- this kernel only
+    // runs the few routed tiles, its staging pipeline is not worth a prefetch register
+    const bool xidx = ga.indexed(xt);
     const int xhalf = ((lane & 1) ^ ((lane >> 4) & 1)) * 16;
     // every stage costs exactly BF3_WSLOTS + 1 pieces per wave on the vmcnt counter (chunks past the end re-read
     // the last one; weight slots past the 12th piece re-copy an earlier piece onto itself)

@@ -30,25 +30,55 @@ __device__ __forceinline__ void slab_clear_part(const SlabArgs& a, uint8_t* scra
     for (size_t k = tid; k < n16; k += nthreads) dst[k] = make_uint4(0, 0, 0, 0);
 }
 
-// scatter: one wave per packet (any order, duplicates allowed), `nwaves` waves (this one: `wave`) share the packets; the
-// validation of snap2_unpack_kernel (ingest.hip), rows of npol bytes
+// scatter: one wave per packet (any order, duplicates allowed), `nwaves` waves (this one: `wave`) share the SAMPLES: wave w copies
+// the packets of the samples t = w mod nwaves, in slab order.  Packets that write the same bytes carry the same sample, so they meet
+// in one wave and the LAST one in the slab wins, as in the oracle's scatter and as through the packet indices (atomicMax), whatever
+// the order the waves run in (a wave's stores are issued and performed in program order).  Every wave that has a sample reads all
+// sequence numbers for that, SLAB_SCAN x 64 of them in flight per step (a slab's headers stay in L2).  The validation of
+// snap2_unpack_kernel (ingest.hip), rows of npol bytes
+constexpr int SLAB_SCAN = 8;
 __device__ __forceinline__ void slab_scatter_part(const SlabArgs& a, uint8_t* scratch, int wave, int nwaves, int lane) {
     const int payload_max = (int)a.stride - 32;
-    for (int p = wave; p < a.npkt; p += nwaves) {
-        const uint8_t* hp = a.pkts + (size_t)p * a.stride;
-        const SlabHeader h = slab_header(hp, a.chan0);
-        const bool ok = h.seq >= a.seq0 && h.seq - a.seq0 < (unsigned long long)a.ntime && h.npol > 0 && h.nchan > 0 && h.chan0 >= 0 &&
-                        h.chan0 + h.nchan <= a.nchan && h.pol0 + h.npol <= a.ninput && (long long)h.nchan * h.npol <= payload_max;
-        if (!ok) continue;
-        uint8_t* dst = scratch + (((size_t)(h.seq - a.seq0) * a.nchan + (size_t)h.chan0) * a.ninput + (size_t)h.pol0);
-        const uint8_t* src = hp + 32;
-        const int n = h.nchan * h.npol;
-        if (((h.npol | (int)h.pol0 | a.ninput) & 15) == 0 && (a.stride & 15) == 0 && (((uintptr_t)a.pkts | (uintptr_t)scratch) & 15) == 0) {
-            const int per_row = h.npol >> 4;             // 16-byte pieces (the deployed 64-byte rows: four per channel)
-            for (int i = lane; i < (n >> 4); i += 64)
-                *reinterpret_cast<uint4*>(dst + (size_t)(i / per_row) * a.ninput + (size_t)(i % per_row) * 16) = *reinterpret_cast<const uint4*>(src + (size_t)i * 16);
-        } else {
-            for (int i = lane; i < n; i += 64) dst[(size_t)(i / h.npol) * a.ninput + (i % h.npol)] = src[i];
+    if (wave >= a.ntime) return;                         // (no sample is this wave's)
+    const bool words = ((a.stride | (uintptr_t)a.pkts) & 3) == 0;
+    for (int p0 = 0; p0 < a.npkt; p0 += 64 * SLAB_SCAN) {
+        unsigned long long seq[SLAB_SCAN];
+#pragma unroll
+        for (int k = 0; k < SLAB_SCAN; k++) {
+            const int q = p0 + 64 * k + lane;
+            seq[k] = 0ull;
+            if (q < a.npkt) {
+                const uint8_t* hq = a.pkts + (size_t)q * a.stride;
+                if (words) {
+                    const uint32_t* hw = reinterpret_cast<const uint32_t*>(hq);
+                    seq[k] = ((unsigned long long)__builtin_bswap32(hw[0]) << 32) | __builtin_bswap32(hw[1]);
+                } else seq[k] = ((unsigned long long)slab_be32(hq) << 32) | slab_be32(hq + 4);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < SLAB_SCAN; k++) {
+            const unsigned long long t = seq[k] - a.seq0;
+            const bool mine = p0 + 64 * k + lane < a.npkt && seq[k] >= a.seq0 && t < (unsigned long long)a.ntime &&
+                              (unsigned int)t % (unsigned int)nwaves == (unsigned int)wave;
+            for (unsigned long long todo = __ballot(mine); todo != 0ull; todo &= todo - 1ull) {
+                const int p = p0 + 64 * k + __ffsll((long long)todo) - 1;
+                const uint8_t* hp = a.pkts + (size_t)p * a.stride;
+                const SlabHeader h = slab_header(hp, a.chan0);
+                const bool ok = h.seq >= a.seq0 && h.seq - a.seq0 < (unsigned long long)a.ntime && h.npol > 0 && h.nchan > 0 && h.chan0 >= 0 &&
+                                h.chan0 + h.nchan <= a.nchan && h.pol0 + h.npol <= a.ninput && (long long)h.nchan * h.npol <= payload_max;
+                if (!ok) continue;
+                uint8_t* dst = scratch + (((size_t)(h.seq - a.seq0) * a.nchan + (size_t)h.chan0) * a.ninput + (size_t)h.pol0);
+                const uint8_t* src = hp + 32;
+                const int n = h.nchan * h.npol;
+                if (((h.npol | (int)h.pol0 | a.ninput) & 15) == 0 && (a.stride & 15) == 0 && (((uintptr_t)a.pkts | (uintptr_t)scratch) & 15) == 0) {
+                    const int per_row = h.npol >> 4;             // 16-byte pieces (the deployed 64-byte rows: four per channel)
+                    for (int i = lane; i < (n >> 4); i += 64)
+                        *reinterpret_cast<uint4*>(dst + (size_t)(i / per_row) * a.ninput + (size_t)(i % per_row) * 16) = *reinterpret_cast<const uint4*>(src + (size_t)i * 16);
+                } else {
+                    for (int i = lane; i < n; i += 64) dst[(size_t)(i / h.npol) * a.ninput + (i % h.npol)] = src[i];
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");    // (the next packet's stores stay behind these)
+            }
         }
     }
 }

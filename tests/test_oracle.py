@@ -261,6 +261,58 @@ def test_snap2_oracle_is_pinned_by_the_reference_transmitter(golden_dir):
     assert np.array_equal(out.reshape(vin.shape), vin)
 
 
+@pytest.mark.parametrize("lo,hi", [(0, 16), (80, 224), (208, 224)])
+def test_slab_part_kinds_are_what_the_unpacker_makes_of_them(lo, hi):
+    """the gulp parts of tests/test_beam_slab_parts_gpu.py (tests/slab_parts.part_packets) on the CPU, so that the GPU cases cannot
+    degenerate: a lossy part (L) has its missing sample zero and the LATE copy of its doubled (sample, block); a part with a packet
+    of another geometry (F) is that part plus a packet that snap2_unpack places -- valid by the test of slab_index_prepare_kernel
+    (slab.hip), not of the deployed geometry -- and its gulp differs from the lossy part's; an empty part (E) is all zero"""
+    import struct
+    from tests import slab_parts as sp
+    nstand, nchan, ntime = 64, 4, 224
+    ninput, nblk, stride, n = nstand * 2, nstand * 2 // 64, 32 + nchan * 64, hi - lo
+    vin = sp.voltages(ntime, nchan, nstand, seed=224)
+    flat, alt = vin.reshape(ntime, nchan, ninput), vin[::-1].reshape(ntime, nchan, ninput)
+    unpack = lambda pk: orc.snap2_unpack(pk, sp.SEQ0 + lo, n, sp.CHAN0, nchan, ninput)
+
+    reg, _ = sp.part_packets("R", vin, lo, hi)
+    g, placed, dropped = unpack(reg)
+    assert len(reg) == n * nblk and (placed, dropped) == (len(reg), 0) and np.array_equal(g, flat[lo:hi])
+    assert sp.part_packets("E", vin, lo, hi)[0] == [] and not unpack([])[0].any() and unpack([])[0].shape == (n, nchan, ninput)
+
+    lossy, info = sp.part_packets("L", vin, lo, hi, seed=1)
+    assert all(len(p) == stride for p in lossy)
+    assert len(lossy) == n * nblk - nblk - info["nlost"] + 1 and info["nlost"] >= 1 and len(lossy) != len(reg)
+    gl, placed, dropped = unpack(lossy)
+    assert (placed, dropped) == (len(lossy), 0)
+    tmiss, (tdup, bdup) = info["tmiss"], info["dup"]
+    assert not gl[tmiss].any() and flat[lo + tmiss].any()
+    cols = slice(bdup * 64, bdup * 64 + 64)
+    assert sum(struct.unpack(orc.SNAP2_HDR, p[:32])[0::8] == (sp.SEQ0 + lo + tdup, bdup * 64) for p in lossy) == 2     # carried twice
+    assert np.array_equal(gl[tdup, :, cols], alt[lo + tdup, :, cols]) and not np.array_equal(gl[tdup, :, cols], flat[lo + tdup, :, cols])
+    assert np.count_nonzero((gl != flat[lo:hi]).any(axis=(1, 2))) >= 3         # the missing sample, the doubled one, a dropped packet's
+    assert lossy != reg[:len(lossy)]                                          # behind a loss everything sits early
+
+    odd, info_f = sp.part_packets("F", vin, lo, hi, seed=1)
+    foreign = info_f["foreign"]
+    assert (info_f["tmiss"], info_f["dup"]) == (tmiss, (tdup, bdup)) and len(foreign) == stride
+    assert [p for p in odd if p != foreign] == lossy and odd.count(foreign) == 1 and 0 < odd.index(foreign) < len(odd) - 1
+    seq, _, npol, _, nch, _, _, chan0, pol0 = struct.unpack(orc.SNAP2_HDR, foreign[:32])
+    t, c0 = seq - (sp.SEQ0 + lo), chan0 - sp.CHAN0
+    # (the `ok` test of slab_index_prepare_kernel / slab_scatter_part ...
+    assert 0 <= t < n and npol > 0 and nch > 0 and c0 >= 0 and c0 + nch <= nchan and pol0 + npol <= ninput and nch * npol <= stride - 32
+    # ... and its geometry test, which this packet fails on npol alone)
+    assert npol == 32 and nch == nchan and c0 == 0 and (t, pol0) == (tmiss, 32)
+    gf, placed, dropped = unpack(odd)
+    assert (placed, dropped) == (len(odd), 0)
+    payload = np.frombuffer(foreign[32:32 + nch * npol], dtype=np.uint8).reshape(nch, npol)
+    assert payload.any() and np.array_equal(gf[tmiss, :, 32:64], payload) and np.array_equal(payload, alt[lo + tmiss, :, 32:64])
+    assert not np.array_equal(gf, gl)
+    rest = gf.copy()
+    rest[tmiss, :, 32:64] = 0
+    assert np.array_equal(rest, gl)                                           # (nothing else differs)
+
+
 def test_vectorised_cpu_baseline_equals_the_scalar_oracle():
     """bench.py's cpu_baseline runs oracle/xeng_cpu_fast.c (the same contraction written for the host it runs on: -march=native, AVX-512
     VNNI where there is one, built on this machine).  Word for word the scalar oracle -- every word of the planes, the diagonal

@@ -14,16 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import xeng_oracle as orc  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    from tests import gpu_util
-    assert gpu_util.ffi.device_count() >= 1
-    return gpu_util
-
-
-SEQ0, CHAN0 = 10 ** 12 + 7, 1000
+from tests.slab_parts import SEQ0, CHAN0, _slab, _beam_init, _beam_weights, gpu, part_gulp, part_packets  # noqa: E402,F401
 
 
 def _need_fused(ffi):
@@ -34,12 +25,6 @@ def _need_fused(ffi):
             ffi.call("xengXgpuKernelAsyncSlab", 1 << 20, 1, 64, 0, 0, 1 << 21, 0, None, 0)
         ffi.call("xengXgpuDestroy")
         pytest.skip("packet slabs need the fused contraction kernel")
-
-
-def _slab(pkts):
-    stride = len(pkts[0])
-    assert all(len(p) == stride for p in pkts)
-    return np.frombuffer(b"".join(pkts), dtype=np.uint8), stride
 
 
 def _expected(pkt_lists, ntime, nchan, nstand):
@@ -158,8 +143,8 @@ def test_lossy_links_shifted_slabs_and_last_duplicate_wins(gpu, nstand, nchan, n
       3  two packets carry the same (sample, block) with DIFFERENT payloads: the later one wins, as in the oracle's scatter
       4  a whole sample and a whole 64-input block missing
       5  nothing but foreign packets: the gulp reads as zeros
-    Following the tables all are read in place, none is scattered; by strides all six take the scatter (two different payloads for one
-    sample make that path's result depend on the order of its waves: that gulp is left out there)."""
+    Following the tables all are read in place, none is scattered; by strides all six take the scatter, which applies the packets of a
+    sample in slab order: the later of two payloads for one sample wins there too."""
     rng = np.random.default_rng(nstand)
     vin = gpu.synth_voltages(6 * ntime, nchan, nstand, "full", seed=21)
     nblk = nstand * 2 // 64
@@ -186,7 +171,7 @@ def test_lossy_links_shifted_slabs_and_last_duplicate_wins(gpu, nstand, nchan, n
     lists.append([pk for i, pk in enumerate(full) if i // nblk != 17 and i % nblk != 1])
     lists.append(orc.snap2_packets(vin[:ntime], seq0=SEQ0 + 5 * ntime, sync_time=3, nchan_blocks=1, nstand_per_pkt=32, chan0_pipeline=CHAN0 + 5000))
     if not tables:
-        lists[3] = _mk(gpu, vin, 3, ntime)[::-1]              # (reversed instead: the scatter has no order among duplicates)
+        lists[3] = lists[3][::-1]                             # (by strides also reversed: then the other copy of each pair is the later one)
     vis, acc, nfb = _run(gpu, lists, nstand, nchan, ntime, acc_mode=1, tables=tables)
     want = _expected(lists, ntime, nchan, nstand)
     assert (nfb, _run.irregular) == ((0, 6) if tables else (6, 0))
@@ -364,30 +349,6 @@ def test_streaming_slabs_with_alternating_outputs(gpu):
 
 
 # ---- the beamformer on packet slabs (xengBeamformRunSlabs) ----
-
-def _beam_init(ffi, mode, ninput, nchan, ntime, nbeam, ntime_blocks=0, tables=None):
-    """tables: XENG_SLAB_TABLES for this context ("1": the parts are read through their packet indices from the first call on)"""
-    import os
-    old = {k: os.environ.pop(k, None) for k in ("XENG_BEAM", "XENG_SLAB_TABLES")}
-    if mode:
-        os.environ["XENG_BEAM"] = mode
-    if tables is not None:
-        os.environ["XENG_SLAB_TABLES"] = tables
-    try:
-        ffi.call("xengBeamformInitialize", 0, ninput, nchan, ntime, nbeam, ntime_blocks)
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-
-
-def _beam_weights(rng, nchan, nbeam, ninput):
-    w = (rng.uniform(-17, 17, (nchan, nbeam, ninput)) + 1j * rng.uniform(-17, 17, (nchan, nbeam, ninput))).astype(np.complex64)
-    w[:, :, 3] *= 4096.0                                                       # an outlier input on every row
-    w[0] *= np.exp(rng.uniform(-12, 12, (nbeam, ninput))).astype(np.float32)    # channel 0: routed to the bf16x3 kernel
-    return w
-
 
 @pytest.mark.parametrize("tables", [None, "1"])
 @pytest.mark.parametrize("mode", ["", "bf16x3", "f32"])
@@ -588,4 +549,41 @@ def test_beamformer_slabs_in_the_integrated_power_mode(gpu):
         assert np.allclose(a, b, rtol=1e-6, atol=0) and np.abs(a).max() > 0      # (sums added atomically across work-groups: order may differ in the last bit)
     ffi.call("xengBeamformDestroy")
     for d in (d0, d1, dfull, dw, o1, o2):
+        d.free()
+
+
+def test_beamformer_integrated_power_mode_through_the_indices_on_mixed_parts(gpu):
+    """ntime_blocks > 0 with the parts read through their packet indices (XENG_SLAB_TABLES=1), split at 144 = 16 mod 32, one part lossy
+    (by index) and the other with a packet of another geometry (the scratch gulp), either way round (tests/slab_parts.part_packets):
+    the power sums equal those of the unpacked gulp to the bar of the test above (atomic adds across work-groups)"""
+    ffi = gpu.ffi
+    nstand, nchan, ntime, nbeam, ntime0, nblocks = 96, 8, 256, 32, 144, 8
+    ninput = nstand * 2
+    rng = np.random.default_rng(4)
+    vin = gpu.synth_voltages(ntime, nchan, nstand, "full", seed=10)
+    w = (rng.uniform(-17, 17, (nchan, nbeam, ninput)) + 1j * rng.uniform(-17, 17, (nchan, nbeam, ninput))).astype(np.complex64)
+    _beam_init(ffi, "", ninput, nchan, ntime, nbeam, nblocks, tables="1")
+    dw = ffi.DeviceBuffer(w.nbytes).upload(w)
+    nout = (nbeam // 2) * nblocks * nchan * 4 * 4
+    o1, o2 = ffi.DeviceBuffer(nout), ffi.DeviceBuffer(nout)
+    for pair in (("L", "F"), ("F", "L")):
+        p0, _ = part_packets(pair[0], vin, 0, ntime0, seed=0)
+        p1, _ = part_packets(pair[1], vin, ntime0, ntime, seed=1)
+        unpacked = np.concatenate([part_gulp(p0, 0, ntime0, nchan, ninput), part_gulp(p1, ntime0, ntime, nchan, ninput)])
+        (r0, stride), (r1, _) = _slab(p0), _slab(p1)
+        d0, d1 = ffi.DeviceBuffer(r0.size).upload(r0), ffi.DeviceBuffer(r1.size).upload(r1)
+        dfull = ffi.DeviceBuffer(unpacked.size).upload(unpacked.reshape(-1))
+        for _ in range(2):        # (the second pass: the routing answer is known, the fused epilogue forms the sums)
+            ffi.call("xengBeamformRunVersioned", dfull.ptr, o1.ptr, dw.ptr, 1)
+            ffi.call("xengBeamformRunSlabs", d0.ptr, len(p0), ntime0, d1.ptr, len(p1), stride, SEQ0, CHAN0, o2.ptr, dw.ptr, 1)
+            ffi.call("xengBeamformSync")
+            nfb, nir = ctypes.c_int(-1), ctypes.c_int(-1)
+            ffi.call("xengBeamformGetSlabStats", ctypes.byref(nfb), ctypes.byref(nir))
+            assert (nfb.value, nir.value) == (1, 1), pair
+            a, b = o1.download(np.float32), o2.download(np.float32)
+            assert np.allclose(a, b, rtol=1e-6, atol=0) and np.abs(a).max() > 0, pair
+        for d in (d0, d1, dfull):
+            d.free()
+    ffi.call("xengBeamformDestroy")
+    for d in (dw, o1, o2):
         d.free()
