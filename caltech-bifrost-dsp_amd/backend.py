@@ -781,6 +781,58 @@ class HipBackend:
     def calapply_sync(self):
         ffi.call("xengCalapplySync")
 
+    # ---- direction-dependent gains and peeling (UpchanPeel; include/xeng.h "Direction-dependent gains and peeling"): a context of
+    # its own, its kernels on the beamformer's stream
+    def peel_initialize(self, gpu, nstand, nfine, ndir):
+        return self._lib.xengPeelInitialize(int(gpu), int(nstand), int(nfine), int(ndir))
+
+    def peel_set_model(self, tau, freq, flux):
+        """tau: host float64 [ndir][nstand] seconds, freq: host float64 [nfine] Hz, flux: host float32 [nfine][ndir], all
+        C-contiguous.  Waits for the context's work in flight; forgets the warm start."""
+        import numpy as np
+        for a, t in ((tau, np.float64), (freq, np.float64), (flux, np.float32)):
+            if not (isinstance(a, np.ndarray) and a.dtype == t and a.flags['C_CONTIGUOUS']):
+                raise TypeError("peel_set_model: the tables must be C-contiguous float64, float64 and float32 arrays")
+        pd = ctypes.POINTER(ctypes.c_double)
+        return self._lib.xengPeelSetModel(tau.ctypes.data_as(pd), freq.ctypes.data_as(pd), _host_floats(flux))
+
+    def peel_set_weights(self, weights, refant):
+        """weights: host float32 [nstand], finite and >= 0, that of `refant` > 0.  Waits for the context's work in flight; holds from
+        the next run; forgets the warm start."""
+        import numpy as np
+        if not (isinstance(weights, np.ndarray) and weights.dtype == np.float32 and weights.flags['C_CONTIGUOUS']):
+            raise TypeError("peel_set_weights: the weights must be a C-contiguous float32 array")
+        return self._lib.xengPeelSetWeights(_host_floats(weights), int(refant))
+
+    def peel_set_solver(self, niter, tol):
+        return self._lib.xengPeelSetSolver(int(niter), float(tol))
+
+    def peel_run(self, vis_arr, out_arr, sol_arr, stats_offset, warm):
+        """Enqueue only: cf32 [nfine][nstand][2][nstand][2] in and out; cf32 [nfine][2][ndir][nstand] gains at the start of sol_arr
+        and f32 [nfine][2][4] stats `stats_offset` bytes into it; peel_mark / wait cover it."""
+        return self._enq.xengPeelRun(vis_arr.ptr, out_arr.ptr, sol_arr.ptr, sol_arr.ptr + int(stats_offset), int(bool(warm)))
+
+    def peel_info(self):
+        """(LDS bytes per work-group of the solve, niter, tol, the reference stand, bytes of a span)"""
+        l, n, t, r, b = ctypes.c_int(), ctypes.c_int(), ctypes.c_double(), ctypes.c_int(), ctypes.c_longlong()
+        ffi.call("xengPeelGetInfo", ctypes.byref(l), ctypes.byref(n), ctypes.byref(t), ctypes.byref(r), ctypes.byref(b))
+        return l.value, n.value, t.value, r.value, b.value
+
+    def peel_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengPeelCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def peel_mark(self):
+        return self._mark("xengPeelMark")
+
+    def peel_wait(self, ticket):
+        self._wait("xengPeelTicketDone", "xengPeelWait", ticket)
+
+    def peel_sync(self):
+        ffi.call("xengPeelSync")
+
     # ---- Hogbom CLEAN of the dirty images (UpchanClean; include/xeng.h "Hogbom CLEAN of the dirty images"): a context of its own,
     # its kernel on the beamformer's stream
     def clean_initialize(self, gpu, nstand, nfine, nfavg, npix, niter_max):
@@ -844,7 +896,7 @@ class HipBackend:
         ffi.call("xengCleanSync")
 
     # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold, Period,
-    # Cdedisp, Image, Gaincal, Calapply, Clean)
+    # Cdedisp, Image, Gaincal, Calapply, Peel, Clean)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

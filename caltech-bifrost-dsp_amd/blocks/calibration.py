@@ -92,3 +92,28 @@ def reference_phase(g, refant):
     mag = np.abs(ref)
     ph = np.where(mag > 0, np.conj(ref) / np.where(mag > 0, mag, 1.0), 1.0)
     return g * ph[:, :, None]
+
+
+MAX_NDIR = 8                            # include/xeng.h XENG_PEEL_MAX_NDIR
+
+
+def direction_model_visibilities(freq, tau, flux, g):
+    """The sky of UpchanPeel's model with a gain set per direction: sum_d F_d (g_d o a_d)(g_d o a_d)^H, complex128, of freq [nfine]
+    Hz, tau [ndir][nstand] seconds, flux [ndir] or [nfine][ndir] >= 0 and gains g [nfine][ndir][nstand] (the result is
+    [nfine][nstand][nstand]) or [nfine][2][ndir][nstand] (one per polarisation: [nfine][2][nstand][nstand]).  Dense, as
+    model_visibilities is, which it equals at g = 1."""
+    freq = np.asarray(freq, np.float64).reshape(-1)
+    tau = np.asarray(tau, np.float64)
+    g = np.asarray(g, np.complex128)
+    if tau.ndim != 2 or not tau.size or not freq.size:
+        raise ValueError("direction_model_visibilities: freq [nfine] and tau [ndir][nstand], got %r and %r" % (freq.shape, tau.shape))
+    if g.ndim not in (3, 4) or g.shape[0] != len(freq) or g.shape[-2:] != tau.shape or (g.ndim == 4 and g.shape[1] != 2):
+        raise ValueError("direction_model_visibilities: gains [nfine][ndir][nstand] or [nfine][2][ndir][nstand], got %r" % (g.shape,))
+    F = model_flux(flux, len(freq), tau.shape[0])
+    turns = freq[:, None, None] * tau[None]
+    a = np.exp(-2j * np.pi * (turns - np.rint(turns)))                      # [nfine][ndir][nstand]
+    if g.ndim == 3:
+        u = g * a
+        return np.einsum('cd,cds,cdt->cst', F, u, np.conj(u))
+    u = g * a[:, None]
+    return np.einsum('cd,cpds,cpdt->cpst', F, u, np.conj(u))

@@ -144,6 +144,11 @@ SYMBOLS = {
     "xengCalapplySetFactors": [_vp], "xengCalapplyRun": [_vp, _vp], "xengCalapplyCheckGuards": [_pi],
     "xengCalapplyMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCalapplyWait": [ctypes.c_ulonglong],
     "xengCalapplyTicketDone": [ctypes.c_ulonglong, _pi], "xengCalapplySync": [], "xengCalapplyDestroy": [],
+    "xengPeelInitialize": [_i, _i, _i, _i], "xengPeelGetInfo": [_pi, _pi, ctypes.POINTER(ctypes.c_double), _pi, _pll],
+    "xengPeelSetModel": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float)],
+    "xengPeelSetWeights": [ctypes.POINTER(ctypes.c_float), _i], "xengPeelSetSolver": [_i, ctypes.c_double], "xengPeelRun": [_vp, _vp, _vp, _vp, _i],
+    "xengPeelCheckGuards": [_pi], "xengPeelMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengPeelWait": [ctypes.c_ulonglong],
+    "xengPeelTicketDone": [ctypes.c_ulonglong, _pi], "xengPeelSync": [], "xengPeelDestroy": [],
     "xengCleanInitialize": [_i, _i, _i, _i, _i, _i], "xengCleanGetInfo": [_pi, _pi, _pll, _pll, _pll, ctypes.POINTER(ctypes.c_double)],
     "xengCleanSetGeometry": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], "xengCleanSetWeights": [ctypes.POINTER(ctypes.c_float), _i],
     "xengCleanSetWindow": [ctypes.POINTER(ctypes.c_ubyte)], "xengCleanSetControl": [_i, ctypes.c_float, ctypes.c_float, ctypes.c_float],
@@ -204,6 +209,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengImageRun", "xengImageMark", "xengImageTicketDone",
                 "xengGaincalRun", "xengGaincalMark", "xengGaincalTicketDone",
                 "xengCalapplyRun", "xengCalapplyMark", "xengCalapplyTicketDone",
+                "xengPeelRun", "xengPeelMark", "xengPeelTicketDone",
                 "xengCleanRun", "xengCleanMark", "xengCleanTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first

@@ -1118,6 +1118,87 @@ int xengCalapplyTicketDone(unsigned long long ticket, int *done);
 int xengCalapplySync(void);
 int xengCalapplyDestroy(void);
 
+/* ---------------------------------------------------------------- Direction-dependent gains and peeling
+ * UpchanPeel (no reference counterpart: the reference leaves calibration and source subtraction to offline packages): one complex
+ * gain per (fine channel, polarisation, direction, stand) for ndir <= XENG_PEEL_MAX_NDIR bright point sources, solved per
+ * integration, and each source taken out of the matrix with its own gains; the result is a matrix of the same format, so that
+ * xengImage*, xengGaincal* and a further xengCalapply* read it unchanged.  The input is normally xengCalapply*'s output: the
+ * iteration below converges from gains near 1 (amplitude 1 +- 0.2, phases of half a radian) and diverges from gains of arbitrary
+ * phase, so uncalibrated data are not its input.  The library knows nothing of the array or the sky: blocks/imaging.py builds the
+ * delays.  A context of its own, independent of all others, whose kernels run on the beamformer's stream -- rings declared 'beam'
+ * cover it, and xengBeamformSync waits for it too.  Two kernels per Run (csrc/peel_kernels.h), one more per SetModel.
+ * The conventions are those of xengGaincal*:
+ *   vis      cf32[nfine][nstand][2][nstand][2], 16-byte aligned, never written.  The solve uses, per fine channel c and polarisation p,
+ *            only the pp block, read along its rows: X[s][t] = conj(vis[c][t p][s p]).  The subtraction reads the words i >= j (row i
+ *            = 2 s + p, column j = 2 t + q).
+ *   model    tau f64[ndir][nstand] seconds, freq f64[nfine] Hz, flux F f32[nfine][ndir], finite and >= 0:
+ *              a_ds = exp(-2 pi i * frac(freq[c] * tau[d][s]))
+ *            freq*tau and its reduction to a fraction of a turn in [-1/2, 1/2] are fp64 on the device; sincospif of the fraction and
+ *            everything after it are fp32.  The factors are formed once per SetModel.  A direction with F_d = 0 is off: its gains
+ *            are 0 and it takes no part.  The directions are solved in the order given (the brightest first); nothing is sorted.
+ *   weights  w f32[nstand], finite and >= 0.  A stand with w_s = 0 is NOT LOADED by the solve (a select on the load: it may hold NaN
+ *            or Inf) and all its gains are written as 0 + 0i.  The autos s = t never enter the solve.
+ *   solver   V[s][t] ~ sum_d F_d u_ds conj(u_dt), u_ds = g_ds a_ds.  From g = 1 at every live (direction, stand) (or the warm start
+ *            below), for i = 1 .. niter one sweep:
+ *              1. for all directions at once, from the gains at the start of the sweep: Y[d][s] = sum_{t != s} X[s][t] * w_t u_dt,
+ *                 the only pass over V in a sweep;
+ *              2. for d ascending (Gauss-Seidel over the directions), with u~_e the new u_e for e < d and the sweep's old u_e for e > d:
+ *                   G_e = sum_t w_t conj(u~_et) u_dt over all t,  P = sum_t w_t |u_dt|^2
+ *                   N_s = Y[d][s] - sum_{e != d} F_e u~_es (G_e - w_s conj(u~_es) u_ds),  e ascending
+ *                   g'_ds = conj(a_ds) N_s / (F_d (P - w_s |u_ds|^2)),  and 0 where the denominator is not > 0 or w_s = 0
+ *                 which is the StEFCal step of direction d on V - sum_{e != d} F_e u~_e u~_e^H, that matrix never formed;
+ *              3. on odd i, g <- g'.  On even i, delta = ||g' - g|| / ||g'|| over all live (direction, stand); with tol > 0 and
+ *                 delta <= tol the loop stops with g <- g' (converged); otherwise g <- (g' + g) / 2.
+ *            The simultaneous (Jacobi) update of all directions diverges from 4 directions on; this order converged in every case tried.
+ *   phase    after the loop every direction's gains are multiplied by conj(g_d,ref) / |g_d,ref| of the reference stand refant (left
+ *            as they are where |g_d,ref| is not > 0).  The subtraction does not depend on it.
+ *   gains    cf32[nfine][2][ndir][nstand]; 8-byte aligned
+ *   stats    f32[nfine][2][4] = {sweeps run, the last delta (-1: none was formed), stands solved (weight > 0 and a gain that is not 0
+ *            in every direction that is on), converged 0/1}
+ *   out      cf32 in vis's layout; 16-byte aligned; not the input; nothing past it is written.  From the gains just written:
+ *              i > j:  out[c][s p][t q] = V[c][s p][t q] - delta_pq * sum_d (F_d u_ds) conj(u_dt); a word of a cross hand is the
+ *                      input's, bit for bit
+ *              i = j:  the real part of the same expression; the imaginary part is written as +0
+ *              i < j:  the conjugate of out[c][j][i], not computed again: the output is Hermitian bit for bit.
+ *            The rows and columns of a stand of weight 0 have u = 0: they pass through unchanged.
+ *   warm     the context keeps, per (channel, pol), the last solution before its phase reference and whether it was converged and
+ *            finite.  Run(.., warm = 1) starts from it where it was, else from 1.  A Run with niter = 0 returns its start, phase
+ *            referenced, and leaves the kept solution alone.  SetModel, SetWeights and Initialize forget it.
+ * Every word is a fixed sum: no atomics, one owner per word, one summation order.  A solution depends on its own (channel, pol) block
+ * of vis, the model and the weights only; it does not depend on what else runs on the GPU nor on which other channels are in the
+ * call.  A NaN in the visibilities of a stand that is read stays within its (channel, pol), which ends unconverged.
+ * The state sits between two guard bands of 64 KiB.  SetModel and SetWeights wait for the context's work in flight: a call between
+ * two Runs applies to the later one only; SetSolver sets the arguments of the Runs after it.
+ * Rejected with INVALID_ARGUMENT at the call that sees it: a non-positive size, ndir > XENG_PEEL_MAX_NDIR, nstand >
+ * XENG_PEEL_MAX_NSTAND, more than 65535 channels (Initialize); NULL, a non-finite word, a negative flux (SetModel); NULL, a negative
+ * or non-finite weight, refant out of range or of weight 0 (SetWeights); niter outside [0, XENG_PEEL_MAX_NITER], a negative or
+ * non-finite tol (SetSolver); NULL or misaligned pointers, out = vis (Run).  Run before SetModel or before SetWeights, and every call
+ * without a context: XENG_STATUS_INVALID_STATE. */
+#define XENG_PEEL_MAX_NDIR 8
+#define XENG_PEEL_MAX_NSTAND 512
+#define XENG_PEEL_MAX_NITER 1024
+#define XENG_PEEL_DEFAULT_NITER 60
+#define XENG_PEEL_DEFAULT_TOL 1e-5
+int xengPeelInitialize(int gpu, int nstand, int nfine, int ndir);
+/* the LDS bytes of a work-group of the solve, the solver's niter and tol, the reference stand, the bytes of a span (input = output) */
+int xengPeelGetInfo(int *lds_bytes, int *niter, double *tol, int *refant, long long *span_bytes);
+/* tau: f64[ndir][nstand] seconds, freq: f64[nfine] Hz, flux: f32[nfine][ndir], on the host.  Waits for the context's work in flight. */
+int xengPeelSetModel(const double *tau, const double *freq, const float *flux);
+/* w: f32[nstand] on the host.  Waits for the context's work in flight; holds from the next Run. */
+int xengPeelSetWeights(const float *w, int refant);
+/* after Initialize: XENG_PEEL_DEFAULT_NITER, XENG_PEEL_DEFAULT_TOL */
+int xengPeelSetSolver(int niter, double tol);
+/* enqueue only: one integration */
+int xengPeelRun(const void *vis_dev, void *out_dev, void *gains_dev, void *stats_dev, int warm);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengPeelCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengPeelMark(unsigned long long *ticket);
+int xengPeelWait(unsigned long long ticket);
+int xengPeelTicketDone(unsigned long long ticket, int *done);
+int xengPeelSync(void);
+int xengPeelDestroy(void);
+
 /* ---------------------------------------------------------------- Hogbom CLEAN of the dirty images
  * UpchanClean (no reference counterpart: the reference leaves imaging and deconvolution to offline packages): Hogbom's CLEAN of the
  * images of xengImage*, per channel group, with the imager's EXACT point-spread function -- the imaging is a direct Fourier sum
