@@ -895,8 +895,57 @@ class HipBackend:
     def clean_sync(self):
         ffi.call("xengCleanSync")
 
+    # ---- outlier flags from the fine-channel visibilities (UpchanFlag; include/xeng.h "Outlier flags from the fine-channel
+    # visibilities"): a context of its own, its kernels on the beamformer's stream
+    def flag_initialize(self, gpu, nstand, nfine):
+        return self._lib.xengFlagInitialize(int(gpu), int(nstand), int(nfine))
+
+    def flag_set_weights(self, weights):
+        """weights: host float32 [nstand], finite and >= 0, at least 4 of them > 0.  Waits for the context's work in flight; holds
+        from the next run."""
+        import numpy as np
+        if not (isinstance(weights, np.ndarray) and weights.dtype == np.float32 and weights.flags['C_CONTIGUOUS']):
+            raise TypeError("flag_set_weights: the weights must be a C-contiguous float32 array")
+        return self._lib.xengFlagSetWeights(_host_floats(weights))
+
+    def flag_set_control(self, nsig_cross, nsig_auto, nsig_chan, wchan):
+        return self._lib.xengFlagSetControl(float(nsig_cross), float(nsig_auto), float(nsig_chan), int(wchan))
+
+    def flag_run(self, vis_arr, out_arr, stats_offset, chan_offset):
+        """Enqueue only: cf32 [nfine][nstand][2][nstand][2] in; u8 [nfine][2][nstand] mask at the start of out_arr, f32
+        [nfine][2][nstand][2] stats and f32 [nfine][2][4] chan `stats_offset` and `chan_offset` bytes into it; flag_mark / wait cover
+        it."""
+        return self._enq.xengFlagRun(vis_arr.ptr, out_arr.ptr, out_arr.ptr + int(stats_offset), out_arr.ptr + int(chan_offset))
+
+    def flag_info(self):
+        """(bytes of mask, of stats, of chan, the most LDS bytes of a work-group)"""
+        m, s, c, l = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_int()
+        ffi.call("xengFlagGetInfo", ctypes.byref(m), ctypes.byref(s), ctypes.byref(c), ctypes.byref(l))
+        return m.value, s.value, c.value, l.value
+
+    def flag_control(self):
+        """(nsig_cross, nsig_auto, nsig_chan, wchan) of the runs to come"""
+        a, b, c, w = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+        ffi.call("xengFlagGetControl", ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(w))
+        return a.value, b.value, c.value, w.value
+
+    def flag_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengFlagCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def flag_mark(self):
+        return self._mark("xengFlagMark")
+
+    def flag_wait(self, ticket):
+        self._wait("xengFlagTicketDone", "xengFlagWait", ticket)
+
+    def flag_sync(self):
+        ffi.call("xengFlagSync")
+
     # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold, Period,
-    # Cdedisp, Image, Gaincal, Calapply, Peel, Clean)
+    # Cdedisp, Image, Gaincal, Calapply, Peel, Clean, Flag)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

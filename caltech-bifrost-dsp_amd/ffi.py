@@ -154,6 +154,11 @@ SYMBOLS = {
     "xengCleanSetWindow": [ctypes.POINTER(ctypes.c_ubyte)], "xengCleanSetControl": [_i, ctypes.c_float, ctypes.c_float, ctypes.c_float],
     "xengCleanRun": [_vp, _vp], "xengCleanCheckGuards": [_pi], "xengCleanMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCleanWait": [ctypes.c_ulonglong],
     "xengCleanTicketDone": [ctypes.c_ulonglong, _pi], "xengCleanSync": [], "xengCleanDestroy": [],
+    "xengFlagInitialize": [_i, _i, _i], "xengFlagGetInfo": [_pll, _pll, _pll, _pi], "xengFlagSetWeights": [ctypes.POINTER(ctypes.c_float)],
+    "xengFlagSetControl": [ctypes.c_double, ctypes.c_double, ctypes.c_double, _i],
+    "xengFlagGetControl": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _pi],
+    "xengFlagRun": [_vp, _vp, _vp, _vp], "xengFlagCheckGuards": [_pi], "xengFlagMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengFlagWait": [ctypes.c_ulonglong],
+    "xengFlagTicketDone": [ctypes.c_ulonglong, _pi], "xengFlagSync": [], "xengFlagDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -211,6 +216,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengCalapplyRun", "xengCalapplyMark", "xengCalapplyTicketDone",
                 "xengPeelRun", "xengPeelMark", "xengPeelTicketDone",
                 "xengCleanRun", "xengCleanMark", "xengCleanTicketDone",
+                "xengFlagRun", "xengFlagMark", "xengFlagTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

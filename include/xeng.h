@@ -1281,6 +1281,81 @@ int xengCleanTicketDone(unsigned long long ticket, int *done);
 int xengCleanSync(void);
 int xengCleanDestroy(void);
 
+/* ---------------------------------------------------------------- Outlier flags from the fine-channel visibilities
+ * UpchanFlag (no reference counterpart: the reference leaves flagging to offline packages): robust per-(fine channel, polarisation,
+ * stand) statistics from one pass over UpchanCorr's matrix, median / MAD outlier tests over the stands and over the channels, and a
+ * mask from which blocks/flagging.py forms the per-stand weights of xengGaincal*, xengImage* and xengPeel* and the factors of
+ * xengCalapply*.  A context of its own, independent of all others, whose kernels run on the beamformer's stream -- rings declared
+ * 'beam' cover it, and xengBeamformSync waits for it too.  Three kernels per Run (csrc/flag_kernels.h).
+ * Every integration stands alone: the context keeps nothing from one Run to the next, and there is no test along time.
+ *   vis      cf32[nfine][nstand][2][nstand][2], the output of xengUpchanCorrDump or of xengCalapplyRun, V[c][s p][t q]; 16-byte aligned;
+ *            never written.  With row i = 2 s + p and column j = 2 t + q only the words with i >= j and p = q contribute: the upper
+ *            triangle and the cross hands may hold anything (neither is loaded).
+ *   weights  w f32[nstand], finite and >= 0, used as on / off only; after Initialize all 1.  A stand with w_s = 0 is NOT READ (a select
+ *            on the load: it may hold NaN or Inf).  At least 4 stands must stay.
+ *   control  nsig_cross, nsig_auto, nsig_chan finite and >= 0 (0: that test is off), 0 <= wchan <= XENG_FLAG_MAX_WCHAN; after
+ *            Initialize the XENG_FLAG_DEFAULT_* below.  The thresholds k = float32(nsig * 1.4826) are float64 products on the host,
+ *            rounded once (1.4826 MAD = one sigma of a normal distribution).
+ *   step 1   for every (c, p, s) with w_s > 0:
+ *              A[c][p][s] = Re V[c][s p][s p]
+ *              R[c][p][s] = sum over t != s with w_t > 0 of |V[c][s p][t p]|^2, the word read at [s p][t p] for t < s and at
+ *                           [t p][s p] for t > s;  |z|^2 = fma(re, re, im * im)
+ *            and +0 for both where w_s = 0.  The one summation order: the stands in tiles of 32 (tile K = the stands 32 K .. 32 K + 31,
+ *            whatever nstand); a tile's partial is the sum of its terms from +0 in ascending t (a term that is left out adds +0); R
+ *            is the sum of the partials from +0 in ascending K.  Plain fp32 adds, no atomics, one owner per word.  R and A do not
+ *            depend on which other channels are in the call nor on what else runs on the GPU.  A non-finite word that is read makes
+ *            the R (or, on the diagonal, the A) of its two stands in that (c, p) non-finite, and nothing else.
+ *   step 2   per (c, p), exact in fp32.  L = the stands with w > 0 and finite R and A, n = |L|.  The median of n values sorted
+ *            ascending, v[0 .. n-1], is v[n / 2] for odd n and 0.5f * (v[(n-1) / 2] + v[n / 2]) for even n.  For x in {R, A}:
+ *              med = median_L(x);  d_s = |x_s - med| (one subtraction);  mad = median_L(d);
+ *              stand s of L is an outlier where d_s > k_x * mad (one multiply, a strict compare), k_x > 0.
+ *            With mad = 0 (more than half of L share one value) every stand with d_s > 0 is an outlier: the rule is kept as it
+ *            stands, since a MAD of 0 between independent stands means test data or a broken digitiser, and both should show.
+ *            If n < 4 no stand test is taken, the (c, p) is channel-flagged, has no y below, and med_R = mad_R = +0.
+ *            y[c][p] = med_R.
+ *   step 3   per p, over the channels that have a y.  b_c = the median of y over the channels of [c - wchan, c + wchan], clipped to
+ *            [0, nfine), that have a y (c is one of them); with wchan = 0 the median over all of them.  r_c = y_c - b_c,
+ *            m = the median of |r_c| over those channels; channel c is flagged where |r_c| > k_chan * m, k_chan > 0 (m = 0: as above).
+ *            b = +0 for a channel without a y.
+ *   mask     u8[nfine][2][nstand]: bit 0 cross-power outlier, bit 1 auto outlier, bit 2 channel flagged (on every stand of the
+ *            (c, p), those of weight 0 included), bit 3 non-finite statistic (w > 0, R or A not finite: it is outside L), bit 4 weight 0
+ *   stats    f32[nfine][2][nstand][2] = {R, A}; 4-byte aligned
+ *   chan     f32[nfine][2][4] = {med_R, mad_R, b, n}; 4-byte aligned
+ *            Nothing past any of the three is written.  Bits 0, 1, 3, 4, stats and chan[0, 1, 3] of a (c, p) depend on that (c, p)'s
+ *            words only; bit 2 and b depend on the other channels of the call by definition.
+ * The state (weights, the tiles' partial sums f32[nfine][2][nstand][ntile], the autos) sits between two guard bands of 64 KiB.
+ * SetWeights and SetControl wait for the context's work in flight and hold from the next Run.
+ * Rejected with INVALID_ARGUMENT at the call that sees it: a non-positive size, nstand < 4, nstand > XENG_FLAG_MAX_NSTAND, nfine >
+ * XENG_FLAG_MAX_NFINE (the channel test's medians are taken in one work-group's LDS) (Initialize); NULL, a negative or non-finite
+ * weight, fewer than 4 stands of weight > 0 (SetWeights); a negative or non-finite nsig, one whose threshold is not finite in
+ * float32, wchan outside [0, XENG_FLAG_MAX_WCHAN] (SetControl); NULL results (GetInfo, GetControl, CheckGuards); NULL pointers, vis
+ * not 16-byte or stats or chan not 4-byte aligned (Run).  Every call without a context: XENG_STATUS_INVALID_STATE. */
+#define XENG_FLAG_MAX_NSTAND 512
+#define XENG_FLAG_MAX_NFINE 8192
+#define XENG_FLAG_MAX_WCHAN 64
+#define XENG_FLAG_DEFAULT_NSIG_CROSS 6.0
+#define XENG_FLAG_DEFAULT_NSIG_AUTO 6.0
+#define XENG_FLAG_DEFAULT_NSIG_CHAN 6.0
+#define XENG_FLAG_DEFAULT_WCHAN 0
+int xengFlagInitialize(int gpu, int nstand, int nfine);
+/* the bytes of mask, stats and chan, and the most LDS bytes a work-group of the three kernels takes */
+int xengFlagGetInfo(long long *mask_bytes, long long *stats_bytes, long long *chan_bytes, int *lds_bytes);
+/* w: f32[nstand] on the host.  Waits for the context's work in flight; holds from the next Run. */
+int xengFlagSetWeights(const float *w);
+/* Waits for the context's work in flight; holds from the next Run. */
+int xengFlagSetControl(double nsig_cross, double nsig_auto, double nsig_chan, int wchan);
+int xengFlagGetControl(double *nsig_cross, double *nsig_auto, double *nsig_chan, int *wchan);
+/* enqueue only: one integration */
+int xengFlagRun(const void *vis_dev, void *mask_dev, void *stats_dev, void *chan_dev);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengFlagCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengFlagMark(unsigned long long *ticket);
+int xengFlagWait(unsigned long long ticket);
+int xengFlagTicketDone(unsigned long long ticket, int *done);
+int xengFlagSync(void);
+int xengFlagDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
