@@ -944,8 +944,64 @@ class HipBackend:
     def flag_sync(self):
         ffi.call("xengFlagSync")
 
+    # ---- component lists subtracted from the visibilities (UpchanPredict; include/xeng.h "Component lists subtracted from the
+    # visibilities"): a context of its own, its kernels on the beamformer's stream
+    PREDICT_SUBTRACT, PREDICT_MODEL = 0, 1
+
+    def predict_initialize(self, gpu, nstand, nfine, nfavg, ndir, ncomp_max, cross):
+        return self._lib.xengPredictInitialize(int(gpu), int(nstand), int(nfine), int(nfavg), int(ndir), int(ncomp_max), int(bool(cross)))
+
+    def predict_set_geometry(self, tau, freq):
+        """tau: host float64 [ndir][nstand] seconds, freq: host float64 [nfine] Hz, both C-contiguous.  Waits for the context's work
+        in flight."""
+        import numpy as np
+        for a in (tau, freq):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags['C_CONTIGUOUS']):
+                raise TypeError("predict_set_geometry: the tables must be C-contiguous float64 arrays")
+        pd = ctypes.POINTER(ctypes.c_double)
+        return self._lib.xengPredictSetGeometry(tau.ctypes.data_as(pd), freq.ctypes.data_as(pd))
+
+    def predict_set_components(self, records):
+        """records: host array of 32-byte records (blocks/imaging.py CLEAN_COMPONENT) [nfine / nfavg][ncomp_max], C-contiguous.
+        Waits for the context's work in flight; holds from the next run."""
+        import numpy as np
+        if not (isinstance(records, np.ndarray) and records.dtype.itemsize == 32 and records.flags['C_CONTIGUOUS']):
+            raise TypeError("predict_set_components: the records must be a C-contiguous array of 32-byte records")
+        return self._lib.xengPredictSetComponents(records.ctypes.data_as(ctypes.c_void_p))
+
+    def predict_set_mode(self, mode):
+        return self._lib.xengPredictSetMode(int(mode))
+
+    def predict_run(self, vis_arr, out_arr):
+        """Enqueue only: cf32 [nfine][nstand][2][nstand][2] in and out (vis_arr may be None in model mode); predict_mark / wait cover
+        it."""
+        return self._enq.xengPredictRun(None if vis_arr is None else vis_arr.ptr, out_arr.ptr)
+
+    def predict_info(self):
+        """(tiles of 32 stands per side, work-groups per run, LDS bytes per work-group, bytes of a span, bytes of state, filled
+        records, mode)"""
+        t, g, l, m = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        b, s, n = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong()
+        ffi.call("xengPredictGetInfo", ctypes.byref(t), ctypes.byref(g), ctypes.byref(l), ctypes.byref(b), ctypes.byref(s), ctypes.byref(n), ctypes.byref(m))
+        return t.value, g.value, l.value, b.value, s.value, n.value, m.value
+
+    def predict_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengPredictCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def predict_mark(self):
+        return self._mark("xengPredictMark")
+
+    def predict_wait(self, ticket):
+        self._wait("xengPredictTicketDone", "xengPredictWait", ticket)
+
+    def predict_sync(self):
+        ffi.call("xengPredictSync")
+
     # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold, Period,
-    # Cdedisp, Image, Gaincal, Calapply, Peel, Clean, Flag)
+    # Cdedisp, Image, Gaincal, Calapply, Peel, Clean, Flag, Predict)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

@@ -28,15 +28,16 @@ from .beam_coherent_dedisperse_block import BeamCoherentDedisperse
 from .coherent_dedisp import cdedisp_plan, chirp_table, smear_samples
 from .upchan_image_block import UpchanImage
 from .upchan_clean_block import UpchanClean
-from .imaging import (clean_components, clean_layout, components_to_model, direction_list, image_norm, patch, pixel_grid, psf, restore,
+from .imaging import (clean_components, clean_layout, component_visibilities, components_to_model, direction_list, image_norm, patch, pixel_grid, psf, restore,
                       steering_delays, stokes_i)
 from .upchan_gaincal_block import UpchanGainCal
 from .upchan_calapply_block import UpchanCalApply
 from .upchan_peel_block import UpchanPeel
 from .upchan_flag_block import UpchanFlag
+from .upchan_predict_block import UpchanPredict
 from .flagging import flag_factors, flag_summary, flag_visibilities, stand_weights
 from .calibration import apply_gains, direction_model_visibilities, inverse_gains, model_flux, model_visibilities, reference_phase
 from .spectral_kurtosis import incoherent_beam, sk_flags, sk_limits, spectral_kurtosis
 
-__all__ = ["Block", "Corr", "CorrAcc", "Beamform", "BeamformSumBeams", "Copy", "CorrSubsel", "CorrOutputFull", "Snap2Ingest", "BeamformOutput", "CorrOutputPart", "BeamformVlbiOutput", "UpchanBeamform", "TbfSource", "UpchanCorr", "UpchanSumBeams", "UpchanSpectra", "BeamDedisperse", "dm_delays", "BeamPulseSearch", "pulse_candidates", "BeamPeriodSearch", "period_candidates", "period_pfa", "BeamFold", "fold_phase", "fold_rotations", "fold_rotations_coherent", "profile_snr", "BeamCoherentDedisperse", "chirp_table", "smear_samples", "cdedisp_plan", "UpchanImage", "pixel_grid", "patch", "steering_delays", "direction_list", "image_norm", "stokes_i", "UpchanClean", "psf", "clean_components", "clean_layout", "restore", "components_to_model", "UpchanGainCal", "UpchanCalApply", "UpchanPeel", "UpchanFlag", "flag_factors", "stand_weights", "flag_visibilities", "flag_summary", "model_visibilities", "direction_model_visibilities", "model_flux", "apply_gains", "inverse_gains", "reference_phase", "spectral_kurtosis", "sk_limits", "sk_flags", "incoherent_beam", "regtile_index", "tri_index",
+__all__ = ["Block", "Corr", "CorrAcc", "Beamform", "BeamformSumBeams", "Copy", "CorrSubsel", "CorrOutputFull", "Snap2Ingest", "BeamformOutput", "CorrOutputPart", "BeamformVlbiOutput", "UpchanBeamform", "TbfSource", "UpchanCorr", "UpchanSumBeams", "UpchanSpectra", "BeamDedisperse", "dm_delays", "BeamPulseSearch", "pulse_candidates", "BeamPeriodSearch", "period_candidates", "period_pfa", "BeamFold", "fold_phase", "fold_rotations", "fold_rotations_coherent", "profile_snr", "BeamCoherentDedisperse", "chirp_table", "smear_samples", "cdedisp_plan", "UpchanImage", "pixel_grid", "patch", "steering_delays", "direction_list", "image_norm", "stokes_i", "UpchanClean", "psf", "clean_components", "clean_layout", "restore", "components_to_model", "UpchanGainCal", "UpchanCalApply", "UpchanPeel", "UpchanFlag", "UpchanPredict", "component_visibilities", "flag_factors", "stand_weights", "flag_visibilities", "flag_summary", "model_visibilities", "direction_model_visibilities", "model_flux", "apply_gains", "inverse_gains", "reference_phase", "spectral_kurtosis", "sk_limits", "sk_flags", "incoherent_beam", "regtile_index", "tri_index",
            "COMMAND_OK", "COMMAND_NOT_RECOGNIZED", "COMMAND_WRONG_TYPE", "COMMAND_INVALID"]

@@ -216,3 +216,43 @@ def components_to_model(components, lmn, nfavg, nsrc_max=32):
     for k, x in enumerate(pix):
         flux[:, k] = np.maximum(per[x], 0.0)
     return np.ascontiguousarray(d[pix].reshape(len(pix), 3)), np.ascontiguousarray(np.repeat(flux, int(nfavg), axis=0), np.float32)
+
+
+# ---- component lists as visibilities (UpchanPredict; include/xeng.h "Component lists subtracted from the visibilities")
+def component_visibilities(freq, tau, components, nfavg, cross=True):
+    """The visibility model of component records, float64 on the host: complex128 [nfine][nstand][2][nstand][2], the whole Hermitian
+    matrix.  components: CLEAN_COMPONENT [nfine / nfavg][n] (clean_components(span, ...)[0], or a catalogue in that layout), `pixel`
+    an index into tau [ndir][nstand], -1 an empty record; each group's list serves its nfavg channels.  With a_ks = exp(-2 pi i
+    frac(freq[c] tau[pixel_k][s])):
+      M[c][s p][t p] = sum_k C_k^pp a_ks conj(a_kt)  (C^00 = C_XX, C^11 = C_YY), and with `cross`
+      M[c][s 0][t 1] = sum_k (C_Re + i C_Im)_k a_ks conj(a_kt),  M[c][s 1][t 0] = sum_k (C_Re - i C_Im)_k a_ks conj(a_kt)
+    the convention under which UpchanImage reads one component at its pixel as [C_XX, C_YY, C_Re, C_Im]: UpchanImage of V - M is
+    UpchanClean's residual."""
+    freq, tau = np.asarray(freq, np.float64).reshape(-1), np.asarray(tau, np.float64)
+    comps = np.asarray(components)
+    if int(nfavg) != nfavg or nfavg <= 0 or freq.size % int(nfavg):
+        raise ValueError("component_visibilities: nfavg %r does not divide %d channels" % (nfavg, freq.size))
+    nfavg = int(nfavg)
+    if tau.ndim != 2 or comps.dtype != CLEAN_COMPONENT or comps.ndim != 2 or comps.shape[0] != freq.size // nfavg:
+        raise ValueError("component_visibilities: delays [ndir][nstand] %r and CLEAN_COMPONENT records [%d][n], got %r %r"
+                         % (tau.shape, freq.size // nfavg, comps.dtype, comps.shape))
+    ndir, nstand = tau.shape
+    M = np.zeros((freq.size, nstand, 2, nstand, 2), np.complex128)
+    for g in range(comps.shape[0]):
+        rec = comps[g][comps[g]['pixel'] != -1]
+        if not rec.size:
+            continue
+        if rec['pixel'].min() < 0 or rec['pixel'].max() >= ndir:
+            raise ValueError("component_visibilities: a pixel of group %d is outside [-1, %d)" % (g, ndir))
+        C = rec['C'].astype(np.float64)
+        if not np.all(np.isfinite(C if cross else C[:, :2])):
+            raise ValueError("component_visibilities: a component of group %d is not finite" % g)
+        ch = slice(g * nfavg, (g + 1) * nfavg)
+        turns = freq[ch, None, None] * tau[rec['pixel']][None]
+        a = np.exp(-2j * np.pi * (turns - np.rint(turns)))                        # [nfavg][k][nstand]
+        M[ch, :, 0, :, 0] = np.einsum('k,cks,ckt->cst', C[:, 0], a, np.conj(a))
+        M[ch, :, 1, :, 1] = np.einsum('k,cks,ckt->cst', C[:, 1], a, np.conj(a))
+        if cross:
+            M[ch, :, 0, :, 1] = np.einsum('k,cks,ckt->cst', C[:, 2] + 1j * C[:, 3], a, np.conj(a))
+            M[ch, :, 1, :, 0] = np.einsum('k,cks,ckt->cst', C[:, 2] - 1j * C[:, 3], a, np.conj(a))
+    return M

@@ -159,6 +159,10 @@ SYMBOLS = {
     "xengFlagGetControl": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _pi],
     "xengFlagRun": [_vp, _vp, _vp, _vp], "xengFlagCheckGuards": [_pi], "xengFlagMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengFlagWait": [ctypes.c_ulonglong],
     "xengFlagTicketDone": [ctypes.c_ulonglong, _pi], "xengFlagSync": [], "xengFlagDestroy": [],
+    "xengPredictInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengPredictGetInfo": [_pi, _pi, _pi, _pll, _pll, _pll, _pi],
+    "xengPredictSetGeometry": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], "xengPredictSetComponents": [_vp], "xengPredictSetMode": [_i],
+    "xengPredictRun": [_vp, _vp], "xengPredictCheckGuards": [_pi], "xengPredictMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengPredictWait": [ctypes.c_ulonglong],
+    "xengPredictTicketDone": [ctypes.c_ulonglong, _pi], "xengPredictSync": [], "xengPredictDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -217,6 +221,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengPeelRun", "xengPeelMark", "xengPeelTicketDone",
                 "xengCleanRun", "xengCleanMark", "xengCleanTicketDone",
                 "xengFlagRun", "xengFlagMark", "xengFlagTicketDone",
+                "xengPredictRun", "xengPredictMark", "xengPredictTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

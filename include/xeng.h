@@ -1356,6 +1356,86 @@ int xengFlagTicketDone(unsigned long long ticket, int *done);
 int xengFlagSync(void);
 int xengFlagDestroy(void);
 
+/* ---------------------------------------------------------------- Component lists subtracted from the visibilities
+ * UpchanPredict (no reference counterpart: the reference leaves deconvolution to offline packages): the visibility model of a list
+ * of point components -- xengCleanRun's own records, or any catalogue -- taken out of UpchanCorr's matrix on all four polarisation
+ * products, written as a matrix of the same format: the major cycle of a Cotton-Schwab CLEAN (xengImageRun of the output is
+ * xengCleanRun's residual), and the subtraction of a sky catalogue of thousands of sources.  A context of its own, independent of all
+ * others, whose kernels run on the beamformer's stream -- rings declared 'beam' cover it, and xengBeamformSync waits for it too.  One
+ * kernel per Run (csrc/predict_kernels.h).
+ *   vis         cf32[nfine][nstand][2][nstand][2], the output of xengUpchanCorrDump, xengCalapplyRun or xengPeelRun, V[c][s p][t q];
+ *               16-byte aligned; never written.  With row i = 2 s + p and column j = 2 t + q only the words i >= j are read: the
+ *               upper triangle may hold anything.
+ *   geometry    tau f64[ndir][nstand] seconds -- the imager's pixel list or any catalogue (blocks/imaging.py steering_delays) --
+ *               and freq f64[nfine] Hz, set once per context (SetGeometry).  ndir <= 2^24 and the table at most
+ *               XENG_IMAGE_MAX_STATE_BYTES, as in xengImage*.
+ *   components  records [ngroup][ncomp_max], ngroup = nfine / nfavg, 1 <= ncomp_max <= XENG_PREDICT_MAX_NCOMP (xengClean*'s niter
+ *               cap), in xengCleanRun's own layout of 32 bytes (blocks/imaging.py CLEAN_COMPONENT): {pixel i32, I f32, C f32[4] =
+ *               XX, YY, Re XY, Im XY, 8 bytes of padding} -- the component area of a Clean span can be handed over as it is.  pixel
+ *               is an index into tau; pixel = -1 is an empty record: zero operands (z = 0, a = 0), its other words are not looked
+ *               at.  I and the padding are ignored.  C must be finite and may be negative.  After Initialize every record is empty.
+ *               SetComponents waits for the context's work in flight and holds from the next Run.
+ *   model       for channel c of group g = c / nfavg, with a_ks = exp(-2 pi i * frac(freq[c] * tau[pixel_k][s])) -- freq*tau
+ *               (__dmul_rn) and its reduction to a fraction of a turn in [-1/2, 1/2] fp64, sincospif of the fraction and everything
+ *               after it fp32: the words of xengImage*, xengGaincal* and xengCalapply*, formed in registers by the lane that uses
+ *               them and never stored (the state beyond the geometry is the records and one count per group) --
+ *                 M_c[s p][t p] = sum_k C_k^pp * a_ks * conj(a_kt),   C^00 = C_XX, C^11 = C_YY
+ *               and with cross = 1 at Initialize
+ *                 M_c[s 0][t 1] = sum_k (C_Re + i C_Im)_k * a_ks * conj(a_kt),   M_c[s 1][t 0] = sum_k (C_Re - i C_Im)_k * a_ks * conj(a_kt)
+ *               the convention under which xengImageRun reads a single component C at its pixel as [C_XX, C_YY, C_Re, C_Im].
+ *               z_ks = C_k * a_ks is one fp32 multiply per part on the parallel hands; on the cross hands, with C = C_Re, D = C_Im:
+ *                 XY:  Re z = fma(C, Re a, -(D Im a)),  Im z = fma(C, Im a, D Re a)
+ *                 YX:  Re z = fma(C, Re a, D Im a),     Im z = fma(C, Im a, -(D Re a))
+ *               Per word of M and per part one chain of fused multiply-adds on f32-input MFMAs, the records two per instruction in
+ *               ascending order: of each pair first Re z Re a (k even, k odd), then Im z Im a (k even, k odd) for the real part; Im z
+ *               Re a, then -Re z Im a for the imaginary part (xengCalapply*'s sequence).  The loop runs to the last filled record
+ *               of the group, rounded up to a pair: the cost follows the list, not ncomp_max.  With cross = 0, C_Re and C_Im are
+ *               ignored and the cross-hand words have no model.
+ *   out         cf32 in vis's layout, not vis itself; 16-byte aligned; nothing past it is written.
+ *                 mode XENG_PREDICT_SUBTRACT (after Initialize):  i > j: out = V - M, one fp32 subtraction per part; with cross = 0
+ *                   the cross-hand words of the lower triangle are V's, bit for bit.
+ *                 mode XENG_PREDICT_MODEL:  out = M; vis may be NULL and is not read; with cross = 0 the cross-hand words are +0.
+ *                 i = j:  the real part of the same expression; the imaginary part is written as +0.
+ *                 i < j:  the conjugate of out[c][j][i]: the same word with the sign of its imaginary part turned, not computed
+ *                   again, so the output is Hermitian bit for bit.
+ *               With no filled record the lower triangle is the input bit for bit (up to the sign of a zero).
+ * There are no per-stand weights: every word of the lower triangle is read, and a NaN in an input word stays in that word and its
+ * mirror.  One owner per Hermitian pair, no atomics, one summation order: a word does not depend on nstand, on the other channels or
+ * groups of the call, on ncomp_max, on earlier settings nor on what else runs on the GPU.  Trailing empty records, and an empty
+ * record in place of one with C = 0, leave every bit unchanged, up to the sign of a zero.
+ * The state (records, freq, tau, counts) sits between two guard bands of 64 KiB.  SetGeometry and SetComponents wait for the context's
+ * work in flight: a call between two Runs applies to the later one only; so does SetMode, which waits for nothing.
+ * Rejected with INVALID_ARGUMENT at the call that sees it: a non-positive size, nfavg not dividing nfine, ncomp_max >
+ * XENG_PREDICT_MAX_NCOMP, nstand > XENG_PREDICT_MAX_NSTAND, more than 65535 channels, ndir or the table above their limits, cross
+ * not 0 or 1 (Initialize); NULL, a non-finite word (SetGeometry); NULL, a pixel outside [-1, ndir), a non-finite word of C in a
+ * filled record -- with cross = 0 of C_XX, C_YY (SetComponents); an unknown mode (SetMode); NULL or misaligned pointers (Run).  Run
+ * before SetGeometry, and every call without a context: XENG_STATUS_INVALID_STATE. */
+#define XENG_PREDICT_MAX_NCOMP 4096
+#define XENG_PREDICT_MAX_NSTAND 512
+#define XENG_PREDICT_SUBTRACT 0
+#define XENG_PREDICT_MODEL 1
+int xengPredictInitialize(int gpu, int nstand, int nfine, int nfavg, int ndir, int ncomp_max, int cross);
+/* the tiles of 32 stands per side, the work-groups of a Run, the LDS bytes of a work-group, the bytes of a span (input = output), the
+ * bytes of state between the guard bands, the filled records of the list in force, the mode of the Runs to come */
+int xengPredictGetInfo(int *ntile, int *ngroup, int *lds_bytes, long long *span_bytes, long long *state_bytes, long long *nfilled, int *mode);
+/* tau: f64[ndir][nstand] seconds, freq: f64[nfine] Hz, on the host.  Waits for the context's work in flight. */
+int xengPredictSetGeometry(const double *tau, const double *freq);
+/* records: [nfine / nfavg][ncomp_max] of 32 bytes on the host, 4-byte aligned.  Waits for the context's work in flight; holds from
+ * the next Run. */
+int xengPredictSetComponents(const void *records);
+/* XENG_PREDICT_SUBTRACT or XENG_PREDICT_MODEL, from the next Run */
+int xengPredictSetMode(int mode);
+/* enqueue only: one integration */
+int xengPredictRun(const void *vis_dev, void *out_dev);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengPredictCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengPredictMark(unsigned long long *ticket);
+int xengPredictWait(unsigned long long ticket);
+int xengPredictTicketDone(unsigned long long ticket, int *done);
+int xengPredictSync(void);
+int xengPredictDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
