@@ -1000,8 +1000,70 @@ class HipBackend:
     def predict_sync(self):
         ffi.call("xengPredictSync")
 
+    # ---- dedispersed transient search of the images (UpchanImageSearch; include/xeng.h "Dedispersed transient search of the
+    # images"): a context of its own, its kernels on the beamformer's stream
+    def imsearch_initialize(self, gpu, npix, ngroup, ndm, max_delay, nwidth, nstat):
+        return self._lib.xengImsearchInitialize(int(gpu), int(npix), int(ngroup), int(ndm), int(max_delay), int(nwidth), int(nstat))
+
+    def imsearch_set_delays(self, delays):
+        """delays: host int32 [ndm][ngroup], C-contiguous, in integrations.  Waits for the context's work in flight; resets."""
+        import numpy as np
+        if not (isinstance(delays, np.ndarray) and delays.dtype == np.int32 and delays.flags['C_CONTIGUOUS']):
+            raise TypeError("imsearch_set_delays: the table must be a C-contiguous int32 array")
+        return self._lib.xengImsearchSetDelays(delays.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+
+    def imsearch_set_weights(self, weights):
+        """weights: host float32 [ngroup], finite and >= 0, one above 0.  Waits for the context's work in flight; resets nothing,
+        but no boxcar reaches back before this call."""
+        import numpy as np
+        if not (isinstance(weights, np.ndarray) and weights.dtype == np.float32 and weights.flags['C_CONTIGUOUS']):
+            raise TypeError("imsearch_set_weights: the weights must be a C-contiguous float32 array")
+        return self._lib.xengImsearchSetWeights(_host_floats(weights))
+
+    def imsearch_run(self, image_arr, out_arr):
+        """Enqueue only: f32 [ngroup][4][npix] in, [npix] records {f32 snr, i16 idm, i16 iw} out; imsearch_mark / wait cover it."""
+        return self._enq.xengImsearchRun(image_arr.ptr, out_arr.ptr)
+
+    def imsearch_reset(self):
+        """The next input counts as integration 0: no baseline, no delayed term, no boxcar reaches back (host state only)."""
+        ffi.check("xengImsearchReset", self._enq.xengImsearchReset())
+
+    def imsearch_info(self):
+        """(integrations taken since the last reset, largest delay of the table in use or -1 without one)"""
+        n, s = ctypes.c_longlong(), ctypes.c_int()
+        ffi.call("xengImsearchGetInfo", ctypes.byref(n), ctypes.byref(s))
+        return n.value, s.value
+
+    def imsearch_baseline(self, ngroup, npix):
+        """Waits for the context's work; (c, m, var) of the last complete block, float32 [ngroup][npix] each."""
+        import numpy as np
+        out = [np.empty((ngroup, npix), np.float32) for _ in range(3)]
+        ffi.call("xengImsearchGetBaseline", *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for a in out])
+        return tuple(out)
+
+    def imsearch_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengImsearchCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def imsearch_mark(self):
+        return self._mark("xengImsearchMark")
+
+    def imsearch_wait(self, ticket):
+        self._wait("xengImsearchTicketDone", "xengImsearchWait", ticket)
+
+    def imsearch_ticket_done(self, ticket):
+        """Never blocks: whether everything enqueued before the ticket has completed."""
+        d = ctypes.c_int()
+        ffi.check("xengImsearchTicketDone", self._enq.xengImsearchTicketDone(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
+        return bool(d.value)
+
+    def imsearch_sync(self):
+        ffi.call("xengImsearchSync")
+
     # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold, Period,
-    # Cdedisp, Image, Gaincal, Calapply, Peel, Clean, Flag, Predict)
+    # Cdedisp, Image, Gaincal, Calapply, Peel, Clean, Flag, Predict, Imsearch)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

@@ -35,9 +35,11 @@ from .upchan_calapply_block import UpchanCalApply
 from .upchan_peel_block import UpchanPeel
 from .upchan_flag_block import UpchanFlag
 from .upchan_predict_block import UpchanPredict
+from .upchan_image_search_block import UpchanImageSearch
+from .image_search import IMSEARCH_RECORD, group_frequencies, image_candidates, image_dm_delays
 from .flagging import flag_factors, flag_summary, flag_visibilities, stand_weights
 from .calibration import apply_gains, direction_model_visibilities, inverse_gains, model_flux, model_visibilities, reference_phase
 from .spectral_kurtosis import incoherent_beam, sk_flags, sk_limits, spectral_kurtosis
 
-__all__ = ["Block", "Corr", "CorrAcc", "Beamform", "BeamformSumBeams", "Copy", "CorrSubsel", "CorrOutputFull", "Snap2Ingest", "BeamformOutput", "CorrOutputPart", "BeamformVlbiOutput", "UpchanBeamform", "TbfSource", "UpchanCorr", "UpchanSumBeams", "UpchanSpectra", "BeamDedisperse", "dm_delays", "BeamPulseSearch", "pulse_candidates", "BeamPeriodSearch", "period_candidates", "period_pfa", "BeamFold", "fold_phase", "fold_rotations", "fold_rotations_coherent", "profile_snr", "BeamCoherentDedisperse", "chirp_table", "smear_samples", "cdedisp_plan", "UpchanImage", "pixel_grid", "patch", "steering_delays", "direction_list", "image_norm", "stokes_i", "UpchanClean", "psf", "clean_components", "clean_layout", "restore", "components_to_model", "UpchanGainCal", "UpchanCalApply", "UpchanPeel", "UpchanFlag", "UpchanPredict", "component_visibilities", "flag_factors", "stand_weights", "flag_visibilities", "flag_summary", "model_visibilities", "direction_model_visibilities", "model_flux", "apply_gains", "inverse_gains", "reference_phase", "spectral_kurtosis", "sk_limits", "sk_flags", "incoherent_beam", "regtile_index", "tri_index",
+__all__ = ["Block", "Corr", "CorrAcc", "Beamform", "BeamformSumBeams", "Copy", "CorrSubsel", "CorrOutputFull", "Snap2Ingest", "BeamformOutput", "CorrOutputPart", "BeamformVlbiOutput", "UpchanBeamform", "TbfSource", "UpchanCorr", "UpchanSumBeams", "UpchanSpectra", "BeamDedisperse", "dm_delays", "BeamPulseSearch", "pulse_candidates", "BeamPeriodSearch", "period_candidates", "period_pfa", "BeamFold", "fold_phase", "fold_rotations", "fold_rotations_coherent", "profile_snr", "BeamCoherentDedisperse", "chirp_table", "smear_samples", "cdedisp_plan", "UpchanImage", "pixel_grid", "patch", "steering_delays", "direction_list", "image_norm", "stokes_i", "UpchanClean", "psf", "clean_components", "clean_layout", "restore", "components_to_model", "UpchanGainCal", "UpchanCalApply", "UpchanPeel", "UpchanFlag", "UpchanPredict", "component_visibilities", "UpchanImageSearch", "IMSEARCH_RECORD", "group_frequencies", "image_dm_delays", "image_candidates", "flag_factors", "stand_weights", "flag_visibilities", "flag_summary", "model_visibilities", "direction_model_visibilities", "model_flux", "apply_gains", "inverse_gains", "reference_phase", "spectral_kurtosis", "sk_limits", "sk_flags", "incoherent_beam", "regtile_index", "tri_index",
            "COMMAND_OK", "COMMAND_NOT_RECOGNIZED", "COMMAND_WRONG_TYPE", "COMMAND_INVALID"]

@@ -163,6 +163,11 @@ SYMBOLS = {
     "xengPredictSetGeometry": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], "xengPredictSetComponents": [_vp], "xengPredictSetMode": [_i],
     "xengPredictRun": [_vp, _vp], "xengPredictCheckGuards": [_pi], "xengPredictMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengPredictWait": [ctypes.c_ulonglong],
     "xengPredictTicketDone": [ctypes.c_ulonglong, _pi], "xengPredictSync": [], "xengPredictDestroy": [],
+    "xengImsearchInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengImsearchSetDelays": [_pi], "xengImsearchSetWeights": [ctypes.POINTER(ctypes.c_float)],
+    "xengImsearchRun": [_vp, _vp], "xengImsearchReset": [], "xengImsearchGetInfo": [_pll, _pi],
+    "xengImsearchGetBaseline": [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)],
+    "xengImsearchCheckGuards": [_pi], "xengImsearchMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengImsearchWait": [ctypes.c_ulonglong],
+    "xengImsearchTicketDone": [ctypes.c_ulonglong, _pi], "xengImsearchSync": [], "xengImsearchDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -222,6 +227,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengCleanRun", "xengCleanMark", "xengCleanTicketDone",
                 "xengFlagRun", "xengFlagMark", "xengFlagTicketDone",
                 "xengPredictRun", "xengPredictMark", "xengPredictTicketDone",
+                "xengImsearchRun", "xengImsearchReset", "xengImsearchMark", "xengImsearchTicketDone",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",

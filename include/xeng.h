@@ -1436,6 +1436,109 @@ int xengPredictTicketDone(unsigned long long ticket, int *done);
 int xengPredictSync(void);
 int xengPredictDestroy(void);
 
+/* ---------------------------------------------------------------- Dedispersed transient search of the images
+ * UpchanImageSearch (no reference counterpart: the reference has no detection stage): the image's channel groups are the
+ * frequency axis and the integrations the time axis of a per-pixel dedispersed boxcar search (csrc/imsearch_kernels.h).
+ * A context of its own, xengImsearch*.  It is independent of all others.  Its kernels run on the beamformer's stream, as
+ * xengImage* and xengPulse* do.  One Run takes one integration.
+ *   in
+ *     - f32 [ngroup][4][npix], the span of xengImageRun.  The front of xengCleanRun's span has the same layout.
+ *     - Only words 0 and 1 of a group are read.
+ *     - The span is never written.
+ *   series
+ *     - I[n][g][x] = fl(XX + YY).
+ *     - n counts integrations since the last reset: Initialize, Reset, SetDelays.
+ *   baseline per (g, x): exactly xengPulse's.
+ *     - Block k is the integrations [k*nstat, (k+1)*nstat).
+ *     - The pivot is c_k, the block's first value.
+ *     - For every integration: delta = fl(I - c_k), a = fl(a + delta), q = fmaf(delta, delta, q).
+ *     - At the block's end: m_k = fl(a*r), v_k = fmaf(-m_k, m_k, fl(q*r)), with r = 1.0f/nstat from the host.
+ *     - The block is valid iff 0 < v_k < inf.  Then g_k = 1.0f/sqrtf(v_k).
+ *     - Every group is ingested, whatever its weight.
+ *   normalised series
+ *     - u[n][g][x] = fl(fl(fl(I - c_{k-1}) - m_{k-1}) * g_{k-1}) for n in a block k >= 1 that follows a valid block.
+ *     - Otherwise there is "no u".
+ *   delays
+ *     - s[d][g], int32 [ndm][ngroup] on the host, 0 <= s <= max_delay, in integrations.
+ *     - S = max s.  The back-delay is b[d][g] = S - s[d][g], xengDedisp's convention.
+ *     - Output n is the event that reached the top of the band at integration n - S.
+ *   weights
+ *     - w[g], f32 [ngroup], finite and >= 0, at least one > 0.
+ *     - A group of weight exactly 0 is left out of z, not multiplied.  A NaN in that group never reaches an output.
+ *   dedispersed series
+ *     - z[n][d][x] starts from +0.
+ *     - The groups with w_g != 0 are taken in ascending g: z = fl(z + fl(w_g * u[n - b[d][g]][g][x])).
+ *     - There is no fused multiply-add.  That keeps a numpy float32 restatement exact.
+ *     - z[n] exists iff n >= n_w and every term has a u.  n_w is the integration count when the weights were last set.
+ *     - A term needs n - b >= nstat as well as a valid block behind it.
+ *     - kappa = (float)(1/sqrt(sum w^2)), float64 on the host, rounded once.
+ *   boxcars
+ *     - B_1 = z.
+ *     - B_{2w}[n] = fl(B_w[n] + B_w[n - w]).
+ *     - Widths are 1, 2, ... 2^(nwidth-1).
+ *   score
+ *     - fl(fl(B_w[n]*kappa)*rho_iw), with rho_iw = (float)2^(-iw/2).
+ *     - It is scored iff every z under the boxcar exists and the score is not NaN.
+ *   out
+ *     - Per call [npix] x {f32 snr, i16 idm, i16 iw}, one 8-byte store per pixel, 16-byte aligned base.
+ *     - The record holds the largest score over (d, iw), then the smallest d, then the smallest iw.
+ *     - It is {+0, -1, -1} when nothing is scored.
+ *     - Nothing past the plane is written.
+ *   state, between two 64 KiB guard bands (xengImsearchCheckGuards)
+ *     - f32 [7][ngroup][npix]: c, m, v, g of the last complete block and c, a, q of the running one.
+ *     - A ring U[S + 1][ngroup][npitch], integration n at slot n mod (S+1).  "No u" is stored as a NaN.
+ *     - A ring Z[T + 1][ndm][npitch], T = 2^(nwidth-1) - 1.
+ *     - npitch is npix rounded up for aligned rows.
+ *     - Whether a slot below the live range counts is taken from its index, never from what the buffer holds.
+ *     - Reset moves only host counters.
+ *     - SetDelays resets, because S moves the time axis.
+ *     - SetWeights resets nothing but sets n_w.
+ *   numerics
+ *     - fp32, #pragma clang fp contract(off), no atomics.
+ *     - Every word is one fixed-order chain.
+ *     - A pixel's record depends on that pixel's words alone.  It does not depend on npix, on the pixel's place in the list,
+ *       on the rings' wrap positions, or on what else runs on the GPU.
+ *   entry points
+ *     - xengImsearchInitialize(gpu, npix, ngroup, ndm, max_delay, nwidth, nstat)
+ *     - SetDelays, SetWeights
+ *     - Run(image_dev, out_dev)
+ *     - Reset
+ *     - GetInfo(&nintegrations, &S)
+ *     - GetBaseline(c, m, v)
+ *     - CheckGuards
+ *     - Mark / Wait / TicketDone / Sync
+ *     - Destroy
+ *   rejected at Initialize, before a device is touched:
+ *     - a non-positive size;
+ *     - npix > 2^24, ndm > 1024, nwidth outside 1..6, nstat outside 2..2^20 or below the widest boxcar;
+ *     - state above XENG_IMSEARCH_MAX_STATE_BYTES (1LL << 32).
+ *   rejected by setters and Run, without a launch:
+ *     - NULL or misaligned pointers, a delay outside 0..max_delay, a bad weight;
+ *     - Run before SetDelays, and any call without a context: XENG_STATUS_INVALID_STATE.
+ * The weights are all ones until SetWeights; max_delay may be 0 (one trial at DM 0), a negative one is rejected. */
+#define XENG_IMSEARCH_MAX_STATE_BYTES (1LL << 32)
+int xengImsearchInitialize(int gpu, int npix, int ngroup, int ndm, int max_delay, int nwidth, int nstat);
+/* Both setters wait for the context's work in flight and upload from the host: int32 [ndm][ngroup], f32 [ngroup] */
+int xengImsearchSetDelays(const int *delays);
+int xengImsearchSetWeights(const float *weights);
+/* enqueue only: one integration in, one record plane out */
+int xengImsearchRun(const void *image_dev, void *out_dev);
+/* host state only, nothing is launched and nothing cleared: the next input counts as integration 0 */
+int xengImsearchReset(void);
+/* integrations taken since the last reset, and S of the table in use (-1 before SetDelays) */
+int xengImsearchGetInfo(long long *nintegrations, int *max_delay_in_use);
+/* c, m and v of the last complete block into host f32[ngroup][npix] each; waits for the context's work in flight;
+ * XENG_STATUS_INVALID_STATE before a block has completed */
+int xengImsearchGetBaseline(float *c, float *m, float *var);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengImsearchCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengImsearchMark(unsigned long long *ticket);
+int xengImsearchWait(unsigned long long ticket);
+int xengImsearchTicketDone(unsigned long long ticket, int *done);
+int xengImsearchSync(void);
+int xengImsearchDestroy(void);
+
 /* ---------------------------------------------------------------- bifrost-named adapters
  * Exact argument shapes of the reference's call sites; data pointers are taken from the
  * BFarray-like structs, sizes from the configured context. */
