@@ -22,6 +22,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import xeng_oracle as orc  # noqa: E402,F401
+from tests import input_pins  # noqa: E402
 from tests.slab_parts import SEQ0, CHAN0, _slab, _beam_init, _beam_weights, gpu, part_gulp, part_packets, voltages  # noqa: E402,F401
 
 NSTAND, NCHAN, NTIME, NBEAM = 64, 4, 224, 32
@@ -79,10 +80,13 @@ def test_parts_that_split_a_wave_in_every_mix_of_kinds(gpu, cases, mode, tables)
     parts, w, stride = cases
     _beam_init(ffi, mode, NINPUT, NCHAN, NTIME, NBEAM, tables=tables)
     nout = NCHAN * NBEAM * NTIME * 8
-    dw = ffi.DeviceBuffer(w.nbytes).upload(w)
+    wpin = input_pins.upload("weights", ffi.DeviceBuffer(w.nbytes), w)
+    dw = wpin.buf
     o1, o2 = ffi.DeviceBuffer(nout), ffi.DeviceBuffer(nout + GUARD)
     dfull = ffi.DeviceBuffer(NTIME * NCHAN * NINPUT)
-    dev = {key: ffi.DeviceBuffer(raw.size).upload(raw) for key, (raw, _, _) in parts.items()}
+    pin = {key: input_pins.upload("part %d of split %d, kind %s" % (key[1], key[0], key[2]), ffi.DeviceBuffer(raw.size), raw)
+           for key, (raw, _, _) in parts.items()}
+    dev = {key: p.buf for key, p in pin.items()}
     index_next = tables == "1" and mode != "f32"             # (the default context goes over to the indices once a part was not regular)
     seen_loss_matter = False
     ncall = 0
@@ -93,7 +97,7 @@ def test_parts_that_split_a_wave_in_every_mix_of_kinds(gpu, cases, mode, tables)
                 (_, n0, g0), (_, n1, g1) = parts[split, 0, pair[0]], parts[split, 1, pair[1]]
                 unpacked = np.concatenate([g0, g1])
                 assert unpacked.shape == (NTIME, NCHAN, NINPUT)
-                dfull.upload(unpacked.reshape(-1))
+                full_pin = input_pins.upload("unpacked gulp", dfull, unpacked.reshape(-1))
                 ffi.call("xengMemset", o2.ptr, 0x5A, o2.nbytes)
                 ffi.call("xengBeamformRunVersioned", dfull.ptr, o1.ptr, dw.ptr, 1)
                 ffi.call("xengBeamformRunSlabs", dev[split, 0, pair[0]].ptr, n0, split, dev[split, 1, pair[1]].ptr, n1, stride, SEQ0, CHAN0,
@@ -103,6 +107,8 @@ def test_parts_that_split_a_wave_in_every_mix_of_kinds(gpu, cases, mode, tables)
                 ffi.call("xengBeamformGetSlabStats", ctypes.byref(ns), ctypes.byref(ni))
                 a, b = o1.download(np.uint32), o2.download(np.uint32)
                 tag = (mode, tables, split, pair, ncall)
+                for p in (full_pin, wpin, pin[split, 0, pair[0]], pin[split, 1, pair[1]]):      # what this call was given
+                    p.check()
                 assert np.all(b[nout // 4:] == 0x5A5A5A5A), ("guard band", tag)
                 nbad = int(np.count_nonzero(a != b[:nout // 4]))
                 print("beam slab parts", tag, "words that differ:", nbad, "counters:", (ns.value, ni.value))
@@ -118,6 +124,8 @@ def test_parts_that_split_a_wave_in_every_mix_of_kinds(gpu, cases, mode, tables)
                 seen_loss_matter = True
         assert seen_loss_matter, "the losses changed no beam: the comparison would pass with the parts ignored"
         assert ncall == len(SPLITS) * len(PAIRS)
+        for p in pin.values():                               # ... and every part once more: no call wrote into another call's part
+            p.check()
     finally:
         ffi.call("xengBeamformDestroy")
         for d in list(dev.values()) + [dw, o1, o2, dfull]:

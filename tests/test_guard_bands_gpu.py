@@ -14,6 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import xeng_oracle as orc  # noqa: E402
+from tests import input_pins  # noqa: E402
 
 G = 2 << 20
 PATTERN = 0xA5
@@ -117,6 +118,7 @@ def test_contraction_stays_inside_its_output_and_accumulator(gpu, nstand, nchan,
         out.check("dump with the long accumulation fused in")
         acc.check("long accumulator of the fused dump")
     din.check("input gulps")
+    input_pins.assert_same_bytes("input gulps", vin, din.payload(np.uint8))      # ... and the payload between them is as uploaded
     # the consumers of the span
     bl, cj = orc.xgpu_get_order(np.arange(nstand * 2, dtype=np.int32).reshape(nstand, 2))
     if nchan % 4 == 0:
@@ -156,6 +158,7 @@ def test_map_stays_inside_its_accumulator(gpu, n):
     assert np.array_equal(a.payload(np.int32), (2 * b.astype(np.int64)).astype(np.int32))
     a.check("map a = b / a += b")
     db.check("map source")
+    input_pins.assert_same_bytes("map source", b, db.payload(np.uint8))
     a.free()
     db.free()
 
@@ -220,6 +223,8 @@ def test_beamformer_stays_inside_its_outputs(gpu, ninput, nchan, ntime, nbeam, n
             pw.free()
     din.check("beamformer input")
     dw.check("beamformer weights")
+    input_pins.assert_same_bytes("beamformer input", vin, din.payload(np.uint8))
+    input_pins.assert_same_bytes("beamformer weights", w, dw.payload(np.uint8))
     ffi.call("xengBeamformDestroy")
     din.free()
     dw.free()
@@ -251,5 +256,6 @@ def test_ingest_scatter_stays_inside_the_gulp(gpu, T, C, S, nchan_blocks, nstand
         ffi.call("xengSnap2UnpackAsync", dpk.ptr, len(pk), stride, out.ptr, seq0, T, chan0, C, S * 2, clear)
         ffi.call("xengStreamSynchronize")
         out.check("Snap2UnpackAsync clear=%d" % clear)
+    input_pins.assert_same_bytes("packets", raw, dpk.download(np.uint8))
     dpk.free()
     out.free()

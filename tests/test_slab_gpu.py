@@ -14,6 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import xeng_oracle as orc  # noqa: E402
+from tests import input_pins  # noqa: E402
 from tests.slab_parts import SEQ0, CHAN0, _slab, _beam_init, _beam_weights, gpu, part_gulp, part_packets  # noqa: E402,F401
 
 
@@ -67,14 +68,15 @@ def _run(gpu, pkt_lists, nstand, nchan, ntime, acc_mode=0, tables=None):
     ffi.call("xengMemset", out.ptr, 0x5A, out.nbytes)
     if acc:
         ffi.call("xengMemset", acc.ptr, 0, acc.nbytes)
-    bufs = []
+    bufs, pins = [], input_pins.Pins()
     for g, pk in enumerate(pkt_lists):
         raw, stride = _slab(pk)
-        d = ffi.DeviceBuffer(raw.size).upload(raw)
+        d = pins.upload("slab %d of %d (%d packets, tables=%r)" % (g, len(pkt_lists), len(pk), tables), ffi.DeviceBuffer(raw.size), raw)
         bufs.append(d)
         ffi.call("xengXgpuKernelAsyncSlab", d.ptr, len(pk), stride, SEQ0 + g * ntime, CHAN0, out.ptr, int(g == len(pkt_lists) - 1),
                  acc.ptr if acc else None, acc_mode)
     ffi.call("xengXgpuSync")
+    pins.check_all()                            # (round 5 scattered table gulps into the receiver's slab: DESIGN.md 4.8)
     nfb, nirr = ctypes.c_int(-1), ctypes.c_int(-1)
     ffi.call("xengXgpuGetSlabStats", ctypes.byref(nfb), ctypes.byref(nirr))
     again = ctypes.c_int(-1)
@@ -191,14 +193,17 @@ def test_the_contraction_follows_the_tables_on_a_lossy_link(gpu):
     _init(ffi, None, nstand, 2, nchan, ntime, 3)
     _need_fused(ffi)
     out = ffi.DeviceBuffer(orc.per_chan(nstand) * nchan * 8)
-    bufs = {}
+    bufs, pins = {}, input_pins.Pins()
 
     def integrate(lists):
         for g, pk in enumerate(lists):
             raw, stride = _slab(pk)
-            d = bufs.setdefault(id(pk), ffi.DeviceBuffer(raw.size).upload(raw))
+            if id(pk) not in bufs:
+                bufs[id(pk)] = pins.upload("slab %d (%d packets)" % (g, len(pk)), ffi.DeviceBuffer(raw.size), raw)
+            d = bufs[id(pk)]
             ffi.call("xengXgpuKernelAsyncSlab", d.ptr, len(pk), stride, SEQ0 + g * ntime, CHAN0, out.ptr, int(g == 2), None, 0)
         ffi.call("xengXgpuSync")
+        pins.check_all()
         ns, ni = ctypes.c_int(-1), ctypes.c_int(-1)
         ffi.call("xengXgpuGetSlabStats", ctypes.byref(ns), ctypes.byref(ni))
         return out.download(np.int32), ns.value, ni.value
@@ -250,13 +255,14 @@ def test_an_integration_longer_than_the_staging_depth_on_lossy_slabs(gpu, tables
     _need_fused(ffi)
     out = ffi.DeviceBuffer(orc.per_chan(nstand) * nchan * 8)
     ffi.call("xengMemset", out.ptr, 0x5A, out.nbytes)
-    bufs = []
+    bufs, pins = [], input_pins.Pins()
     for g, pk in enumerate(lists):
         raw, stride = _slab(pk)
-        d = ffi.DeviceBuffer(raw.size).upload(raw)
+        d = pins.upload("slab %d of %d (%d packets, tables=%r)" % (g, ng, len(pk), tables), ffi.DeviceBuffer(raw.size), raw)
         bufs.append(d)
         ffi.call("xengXgpuKernelAsyncSlab", d.ptr, len(pk), stride, SEQ0 + g * ntime, CHAN0, out.ptr, int(g == ng - 1), None, 0)
     ffi.call("xengXgpuSync")
+    pins.check_all()
     ns, ni = ctypes.c_int(-1), ctypes.c_int(-1)
     ffi.call("xengXgpuGetSlabStats", ctypes.byref(ns), ctypes.byref(ni))
     assert ns.value + ni.value == 3 and (ns.value == 0 if tables else ns.value >= 1)
@@ -288,7 +294,9 @@ def test_slabs_and_plain_gulps_do_not_mix_inside_an_integration(gpu):
     ffi.call("xengXgpuConfigure", nstand, 2, nchan, ntime, 4)
     ffi.call("xengXgpuInitialize", 0)
     _need_fused(ffi)
-    dslab, dgulp = ffi.DeviceBuffer(raw.size).upload(raw), ffi.DeviceBuffer(vin[ntime:].size).upload(vin[ntime:])
+    pins = input_pins.Pins()
+    dslab = pins.upload("slab", ffi.DeviceBuffer(raw.size), raw)
+    dgulp = pins.upload("plain gulp", ffi.DeviceBuffer(vin[ntime:].size), vin[ntime:])
     out = ffi.DeviceBuffer(orc.per_chan(nstand) * nchan * 8)
     ffi.call("xengXgpuKernelAsyncSlab", dslab.ptr, raw.size // stride, stride, SEQ0, CHAN0, out.ptr, 0, None, 0)
     with pytest.raises(ffi.XengError):
@@ -301,6 +309,7 @@ def test_slabs_and_plain_gulps_do_not_mix_inside_an_integration(gpu):
     # ... and after the reset a whole integration of either kind is fine
     ffi.call("xengXgpuKernelAsync", dgulp.ptr, out.ptr, 1)
     ffi.call("xengXgpuSync")
+    pins.check_all()
     assert np.array_equal(out.download(np.int32), orc.xgpu_correlate(vin[ntime:], nstand, nchan))
     ffi.call("xengXgpuDestroy")
     for b in (dslab, dgulp, out):
@@ -318,7 +327,7 @@ def test_streaming_slabs_with_alternating_outputs(gpu):
     matlen = orc.per_chan(nstand) * nchan
     outs = [ffi.DeviceBuffer(matlen * 8) for _ in range(2)]
     rng = np.random.default_rng(9)
-    slabs, wants = [], []
+    slabs, wants, pins = [], [], input_pins.Pins()
     for n in range(6):
         vin = gpu.synth_voltages(ng * ntime, nchan, nstand, "full", seed=100 + n)
         lists = []
@@ -328,7 +337,8 @@ def test_streaming_slabs_with_alternating_outputs(gpu):
                 pk = [pk[i] for i in rng.permutation(len(pk))]
             lists.append(pk)
         wants.append(_expected(lists, ntime, nchan, nstand))
-        slabs.append([(ffi.DeviceBuffer(_slab(pk)[0].size).upload(_slab(pk)[0]), len(pk), _slab(pk)[1]) for pk in lists])
+        slabs.append([(pins.upload("slab %d of integration %d" % (g, n), ffi.DeviceBuffer(_slab(pk)[0].size), _slab(pk)[0]), len(pk), _slab(pk)[1])
+                      for g, pk in enumerate(lists)])
     got = []
     for n in range(6):
         for g, (d, npk, stride) in enumerate(slabs[n]):
@@ -337,6 +347,7 @@ def test_streaming_slabs_with_alternating_outputs(gpu):
         if n >= 1:
             got.append(outs[(n - 1) & 1].download(np.int32))
     ffi.call("xengXgpuSync")
+    pins.check_all()
     got.append(outs[5 & 1].download(np.int32))
     for n in range(6):
         assert np.array_equal(got[n], wants[n]), n
@@ -366,9 +377,10 @@ def test_beamformer_reads_regular_slabs_in_place(gpu, mode, nstand, nchan, ntime
     mk = lambda lo, hi: _slab(orc.snap2_packets(vin[lo:hi], seq0=SEQ0 + lo, sync_time=1, nchan_blocks=1, nstand_per_pkt=32, chan0_pipeline=CHAN0))
     parts = [mk(0, ntime0), mk(ntime0, ntime)] if ntime0 else [mk(0, ntime)]
     stride = parts[0][1]
-    bufs = [ffi.DeviceBuffer(raw.size).upload(raw) for raw, _ in parts]
-    dfull = ffi.DeviceBuffer(vin.size).upload(vin.reshape(-1))
-    dw = ffi.DeviceBuffer(w.nbytes).upload(w)
+    pins = input_pins.Pins()
+    bufs = [pins.upload("part %d" % i, ffi.DeviceBuffer(raw.size), raw) for i, (raw, _) in enumerate(parts)]
+    dfull = pins.upload("unpacked gulp", ffi.DeviceBuffer(vin.size), vin.reshape(-1))
+    dw = pins.upload("weights", ffi.DeviceBuffer(w.nbytes), w)
     o1, o2 = ffi.DeviceBuffer(nchan * nbeam * ntime * 8), ffi.DeviceBuffer(nchan * nbeam * ntime * 8)
     ffi.call("xengMemset", o2.ptr, 0x5A, o2.nbytes)
     ffi.call("xengBeamformRunVersioned", dfull.ptr, o1.ptr, dw.ptr, 1)
@@ -378,6 +390,7 @@ def test_beamformer_reads_regular_slabs_in_place(gpu, mode, nstand, nchan, ntime
     else:
         ffi.call("xengBeamformRunSlabs", bufs[0].ptr, parts[0][0].size // stride, ntime, None, 0, stride, SEQ0, CHAN0, o2.ptr, dw.ptr, 1)
     ffi.call("xengBeamformSync")
+    pins.check_all()
     nfb, nir = ctypes.c_int(-1), ctypes.c_int(-1)
     ffi.call("xengBeamformGetSlabStats", ctypes.byref(nfb), ctypes.byref(nir))
     assert nfb.value == 0 and nir.value == 0
@@ -408,19 +421,24 @@ def test_beamformer_irregular_slabs_give_the_unpacked_result(gpu, mode, tables):
     bad1 += [bad1[0]] * 3                                                          # (same count again: duplicates)
     bad0 = list(p0)
     bad0[11] = bad0[12]
-    dw = ffi.DeviceBuffer(w.nbytes).upload(w)
+    wpin = input_pins.Pins()
+    dw = wpin.upload("weights", ffi.DeviceBuffer(w.nbytes), w)
     o1, o2 = ffi.DeviceBuffer(nchan * nbeam * ntime * 8), ffi.DeviceBuffer(nchan * nbeam * ntime * 8)
     ncall = 0
     for first, second, nexp in ((p0, bad1, 1), (bad0, bad1, 2), (p0, p1, 0)):       # (the last: the scratch gulp of earlier calls is not read)
         g0, _, _ = orc.snap2_unpack(first, SEQ0, ntime0, CHAN0, nchan, ninput)
         g1, _, _ = orc.snap2_unpack(second, SEQ0 + ntime0, ntime - ntime0, CHAN0, nchan, ninput)
         unpacked = np.concatenate([g0, g1])
-        dfull = ffi.DeviceBuffer(unpacked.size).upload(unpacked.reshape(-1))
+        pins = input_pins.Pins()
+        dfull = pins.upload("unpacked gulp, call %d" % ncall, ffi.DeviceBuffer(unpacked.size), unpacked.reshape(-1))
         (r0, stride), (r1, _) = _slab(first), _slab(second)
-        d0, d1 = ffi.DeviceBuffer(r0.size).upload(r0), ffi.DeviceBuffer(r1.size).upload(r1)
+        d0 = pins.upload("part 0, call %d" % ncall, ffi.DeviceBuffer(r0.size), r0)
+        d1 = pins.upload("part 1, call %d" % ncall, ffi.DeviceBuffer(r1.size), r1)
         ffi.call("xengBeamformRunVersioned", dfull.ptr, o1.ptr, dw.ptr, 1)
         ffi.call("xengBeamformRunSlabs", d0.ptr, r0.size // stride, ntime0, d1.ptr, r1.size // stride, stride, SEQ0, CHAN0, o2.ptr, dw.ptr, 1)
         ffi.call("xengBeamformSync")
+        pins.check_all()
+        wpin.check_all()
         nfb, nir = ctypes.c_int(-1), ctypes.c_int(-1)
         ffi.call("xengBeamformGetSlabStats", ctypes.byref(nfb), ctypes.byref(nir))
         # (the shipped default goes over to the indices once a part was not regular: the first call scatters, the later ones do not)
@@ -462,9 +480,10 @@ def test_beamformer_shifted_and_lossy_parts_through_the_indices(gpu):
     (r0, stride), (r1, _) = _slab(q0), _slab(q1)
     for mode, tables in (("", "1"), ("bf16x3", "1"), ("", None)):
         _beam_init(ffi, mode, ninput, nchan, ntime, nbeam, tables=tables)
-        dfull = ffi.DeviceBuffer(unpacked.size).upload(unpacked.reshape(-1))
-        d0, d1 = ffi.DeviceBuffer(r0.size).upload(r0), ffi.DeviceBuffer(r1.size).upload(r1)
-        dw = ffi.DeviceBuffer(w.nbytes).upload(w)
+        pins = input_pins.Pins()
+        dfull = pins.upload("unpacked gulp", ffi.DeviceBuffer(unpacked.size), unpacked.reshape(-1))
+        d0, d1 = pins.upload("part 0", ffi.DeviceBuffer(r0.size), r0), pins.upload("part 1", ffi.DeviceBuffer(r1.size), r1)
+        dw = pins.upload("weights", ffi.DeviceBuffer(w.nbytes), w)
         o1, o2 = ffi.DeviceBuffer(nchan * nbeam * ntime * 8), ffi.DeviceBuffer(nchan * nbeam * ntime * 8)
         ffi.call("xengBeamformRunVersioned", dfull.ptr, o1.ptr, dw.ptr, 1)
         seen = []
@@ -472,6 +491,7 @@ def test_beamformer_shifted_and_lossy_parts_through_the_indices(gpu):
             ffi.call("xengMemset", o2.ptr, 0x5A, o2.nbytes)
             ffi.call("xengBeamformRunSlabs", d0.ptr, r0.size // stride, ntime0, d1.ptr, r1.size // stride, stride, SEQ0, CHAN0, o2.ptr, dw.ptr, 1)
             ffi.call("xengBeamformSync")
+            pins.check_all()
             nfb, nir = ctypes.c_int(-1), ctypes.c_int(-1)
             ffi.call("xengBeamformGetSlabStats", ctypes.byref(nfb), ctypes.byref(nir))
             seen.append((nfb.value, nir.value))
@@ -499,7 +519,8 @@ def test_beamformer_index_generations_wrap(gpu):
     os.environ["XENG_SLAB_GEN0"] = str(4095 - 3)
     try:
         _beam_init(ffi, "", ninput, nchan, ntime, nbeam, tables="1")
-        dw = ffi.DeviceBuffer(w.nbytes).upload(w)
+        pins = input_pins.Pins()
+        dw = pins.upload("weights", ffi.DeviceBuffer(w.nbytes), w)
         o1, o2 = ffi.DeviceBuffer(nchan * nbeam * ntime * 8), ffi.DeviceBuffer(nchan * nbeam * ntime * 8)
         wants, bufs = {}, {}
         for name, pk in (("full", full), ("holed", holed)):
@@ -509,7 +530,7 @@ def test_beamformer_index_generations_wrap(gpu):
             ffi.call("xengBeamformSync")
             wants[name] = o1.download(np.uint32)
             raw, stride = _slab(pk)
-            bufs[name] = (ffi.DeviceBuffer(raw.size).upload(raw), len(pk), stride)
+            bufs[name] = (pins.upload("slab '%s'" % name, ffi.DeviceBuffer(raw.size), raw), len(pk), stride)
             d.free()
         assert not np.array_equal(wants["full"], wants["holed"])
         for call in range(8):                                 # generations 4093, 4094, 4095, (wrap) 1, 2, ...
@@ -517,6 +538,7 @@ def test_beamformer_index_generations_wrap(gpu):
             d, npk, stride = bufs[name]
             ffi.call("xengBeamformRunSlabs", d.ptr, npk, ntime, None, 0, stride, SEQ0, CHAN0, o2.ptr, dw.ptr, 1)
             ffi.call("xengBeamformSync")
+            pins.check_all()
             assert np.array_equal(o2.download(np.uint32), wants[name]), (call, name)
     finally:
         os.environ.pop("XENG_SLAB_GEN0", None)
@@ -536,15 +558,17 @@ def test_beamformer_slabs_in_the_integrated_power_mode(gpu):
     _beam_init(ffi, "", ninput, nchan, ntime, nbeam, nblocks)
     mk = lambda lo, hi: _slab(orc.snap2_packets(vin[lo:hi], seq0=SEQ0 + lo, sync_time=1, nchan_blocks=1, nstand_per_pkt=32, chan0_pipeline=CHAN0))
     (r0, stride), (r1, _) = mk(0, ntime0), mk(ntime0, ntime)
-    d0, d1 = ffi.DeviceBuffer(r0.size).upload(r0), ffi.DeviceBuffer(r1.size).upload(r1)
-    dfull = ffi.DeviceBuffer(vin.size).upload(vin.reshape(-1))
-    dw = ffi.DeviceBuffer(w.nbytes).upload(w)
+    pins = input_pins.Pins()
+    d0, d1 = pins.upload("part 0", ffi.DeviceBuffer(r0.size), r0), pins.upload("part 1", ffi.DeviceBuffer(r1.size), r1)
+    dfull = pins.upload("unpacked gulp", ffi.DeviceBuffer(vin.size), vin.reshape(-1))
+    dw = pins.upload("weights", ffi.DeviceBuffer(w.nbytes), w)
     nout = (nbeam // 2) * nblocks * nchan * 4 * 4
     o1, o2 = ffi.DeviceBuffer(nout), ffi.DeviceBuffer(nout)
     for _ in range(2):        # (the second pass: the routing answer is known, the fused epilogue forms the sums)
         ffi.call("xengBeamformRunVersioned", dfull.ptr, o1.ptr, dw.ptr, 1)
         ffi.call("xengBeamformRunSlabs", d0.ptr, r0.size // stride, ntime0, d1.ptr, r1.size // stride, stride, SEQ0, CHAN0, o2.ptr, dw.ptr, 1)
         ffi.call("xengBeamformSync")
+        pins.check_all()
         a, b = o1.download(np.float32), o2.download(np.float32)
         assert np.allclose(a, b, rtol=1e-6, atol=0) and np.abs(a).max() > 0      # (sums added atomically across work-groups: order may differ in the last bit)
     ffi.call("xengBeamformDestroy")
@@ -563,7 +587,8 @@ def test_beamformer_integrated_power_mode_through_the_indices_on_mixed_parts(gpu
     vin = gpu.synth_voltages(ntime, nchan, nstand, "full", seed=10)
     w = (rng.uniform(-17, 17, (nchan, nbeam, ninput)) + 1j * rng.uniform(-17, 17, (nchan, nbeam, ninput))).astype(np.complex64)
     _beam_init(ffi, "", ninput, nchan, ntime, nbeam, nblocks, tables="1")
-    dw = ffi.DeviceBuffer(w.nbytes).upload(w)
+    wpin = input_pins.Pins()
+    dw = wpin.upload("weights", ffi.DeviceBuffer(w.nbytes), w)
     nout = (nbeam // 2) * nblocks * nchan * 4 * 4
     o1, o2 = ffi.DeviceBuffer(nout), ffi.DeviceBuffer(nout)
     for pair in (("L", "F"), ("F", "L")):
@@ -571,12 +596,16 @@ def test_beamformer_integrated_power_mode_through_the_indices_on_mixed_parts(gpu
         p1, _ = part_packets(pair[1], vin, ntime0, ntime, seed=1)
         unpacked = np.concatenate([part_gulp(p0, 0, ntime0, nchan, ninput), part_gulp(p1, ntime0, ntime, nchan, ninput)])
         (r0, stride), (r1, _) = _slab(p0), _slab(p1)
-        d0, d1 = ffi.DeviceBuffer(r0.size).upload(r0), ffi.DeviceBuffer(r1.size).upload(r1)
-        dfull = ffi.DeviceBuffer(unpacked.size).upload(unpacked.reshape(-1))
+        pins = input_pins.Pins()
+        d0 = pins.upload("part 0 (%s)" % pair[0], ffi.DeviceBuffer(r0.size), r0)
+        d1 = pins.upload("part 1 (%s)" % pair[1], ffi.DeviceBuffer(r1.size), r1)
+        dfull = pins.upload("unpacked gulp", ffi.DeviceBuffer(unpacked.size), unpacked.reshape(-1))
         for _ in range(2):        # (the second pass: the routing answer is known, the fused epilogue forms the sums)
             ffi.call("xengBeamformRunVersioned", dfull.ptr, o1.ptr, dw.ptr, 1)
             ffi.call("xengBeamformRunSlabs", d0.ptr, len(p0), ntime0, d1.ptr, len(p1), stride, SEQ0, CHAN0, o2.ptr, dw.ptr, 1)
             ffi.call("xengBeamformSync")
+            pins.check_all()
+            wpin.check_all()
             nfb, nir = ctypes.c_int(-1), ctypes.c_int(-1)
             ffi.call("xengBeamformGetSlabStats", ctypes.byref(nfb), ctypes.byref(nir))
             assert (nfb.value, nir.value) == (1, 1), pair
@@ -587,3 +616,44 @@ def test_beamformer_integrated_power_mode_through_the_indices_on_mixed_parts(gpu
     ffi.call("xengBeamformDestroy")
     for d in (dw, o1, o2):
         d.free()
+
+
+def test_beamformer_on_a_lossy_two_part_slab_against_the_oracle(gpu):
+    """The slab-path beams held to the float64 oracle itself, not to xengBeamformRun (the other tests of this file compare HIP with HIP):
+    a two-part gulp split at 112 = 16 mod 32, part 0 what a lossy link leaves (tests/slab_parts.part_packets 'L', read through its
+    packet index), part 1 a regular slab; 96 stands, 8 channels, 256 samples, 32 beams; plain well-conditioned weights, uniform in
+    [-1, 1].  Reference: orc.beamform on part_gulp of the packets.  The bar is the one tests/test_beamform_gpu.py holds xengBeamformRun to
+    against the same oracle (check_beams: max error over the RMS of the beams <= BEAM_RTOL; and its per-row form)."""
+    from tests.beam_route_ref import check_beams_rows
+    from tests.test_beamform_gpu import check_beams
+    ffi = gpu.ffi
+    nstand, nchan, ntime, nbeam, ntime0 = 96, 8, 256, 32, 112
+    ninput = nstand * 2
+    rng = np.random.default_rng(112)
+    vin = gpu.synth_voltages(ntime, nchan, nstand, "full", seed=112)
+    w = (rng.uniform(-1, 1, (nchan, nbeam, ninput)) + 1j * rng.uniform(-1, 1, (nchan, nbeam, ninput))).astype(np.complex64)
+    p0, info = part_packets("L", vin, 0, ntime0, seed=0)
+    p1, _ = part_packets("R", vin, ntime0, ntime, seed=1)
+    unpacked = np.concatenate([part_gulp(p0, 0, ntime0, nchan, ninput), part_gulp(p1, ntime0, ntime, nchan, ninput)])
+    assert not np.array_equal(unpacked, vin.reshape(ntime, nchan, ninput)) and not unpacked[info["tmiss"]].any()     # (the losses are in play)
+    exp = orc.beamform(unpacked, w, ntime, nchan, ninput, nbeam)
+    _beam_init(ffi, "", ninput, nchan, ntime, nbeam, tables="1")
+    (r0, stride), (r1, _) = _slab(p0), _slab(p1)
+    pins = input_pins.Pins()
+    d0, d1 = pins.upload("part 0 (L)", ffi.DeviceBuffer(r0.size), r0), pins.upload("part 1 (R)", ffi.DeviceBuffer(r1.size), r1)
+    dw = pins.upload("weights", ffi.DeviceBuffer(w.nbytes), w)
+    out = ffi.DeviceBuffer(nchan * nbeam * ntime * 8)
+    ffi.call("xengMemset", out.ptr, 0x5A, out.nbytes)
+    ffi.call("xengBeamformRunSlabs", d0.ptr, len(p0), ntime0, d1.ptr, len(p1), stride, SEQ0, CHAN0, out.ptr, dw.ptr, 1)
+    ffi.call("xengBeamformSync")
+    nfb, nir = ctypes.c_int(-1), ctypes.c_int(-1)
+    ffi.call("xengBeamformGetSlabStats", ctypes.byref(nfb), ctypes.byref(nir))
+    got = out.download(np.complex64).reshape(nchan, nbeam, ntime)
+    ffi.call("xengBeamformDestroy")
+    pins.check_all()
+    for d in (d0, d1, dw, out):
+        d.free()
+    assert (nfb.value, nir.value) == (0, 1)          # nothing scattered: part 0 by its index, part 1 in place
+    print("slab beams against the oracle: max err / rms = %.3e" % (np.max(np.abs(got - exp)) / np.sqrt(np.mean(np.abs(exp) ** 2))))
+    check_beams(got, exp)
+    check_beams_rows(got, exp)

@@ -265,9 +265,12 @@ def test_consumers_do_not_wait_for_the_contraction(gpu):
     While the Corr thread sits in a synchronous dump (xengXgpuKernel(..., doDump=1)) behind a queue of contractions,
     a second thread's xengXgpuSubSelect on the PREVIOUS, completed span must return without waiting for that dump: the
     library holds its context lock only while enqueueing, and SubSelect is ordered behind the producer of its own input
-    span alone.  Also: SubSelect on a span whose contraction is still queued waits for exactly that contraction."""
+    span alone.  Also: SubSelect on a span whose contraction is still queued waits for exactly that contraction.
+
+    Observed by state, not by the clock: the SubSelect thread starts once the Corr thread has signalled that it is about to make its
+    synchronous dump call, and right after xengXgpuSubSelect returns it asks xengXgpuDumpDone(0).  The answer 0 says that SubSelect came
+    back while the latest dump of the queue it must not wait for was still pending; after the dump call has returned the answer is 1."""
     import threading
-    import time
     nstand, nchan, ntime, ngulp = 352, 96, 480, 5
     x = gpu.Xgpu(nstand, nchan, ntime, max_gulps=ngulp)
     vin = gpu.synth_voltages(ntime * ngulp, nchan, nstand, "random", seed=5)
@@ -289,7 +292,7 @@ def test_consumers_do_not_wait_for_the_contraction(gpu):
     L = gpu.ffi.lib()
     gb = x.gulp_bytes
     nint = 150                                        # ~35 ms of queued contractions into x.out
-    t = {}
+    t = {"rc": []}
     entered = threading.Event()
 
     def corr_thread():
@@ -297,27 +300,29 @@ def test_consumers_do_not_wait_for_the_contraction(gpu):
             for g in range(ngulp):
                 last = n == nint - 1 and g == ngulp - 1
                 if last:
-                    entered.set()
-                    t["dump_call"] = time.perf_counter()
+                    entered.set()                     # about to make the synchronous dump call
                     rc = L.xengXgpuKernel(x.inbuf.ptr + g * gb, x.out.ptr, 1)        # synchronous dump: waits for the whole queue
+                    t["dump_rc"] = rc
                 else:
                     rc = L.xengXgpuKernelAsync(x.inbuf.ptr + g * gb, x.out.ptr, int(g == ngulp - 1))
-                assert rc == 0
-        t["dump_done"] = time.perf_counter()
+                t["rc"].append(rc)
 
     def subsel_thread():
         entered.wait()
-        time.sleep(0.002)                             # the Corr thread is inside its dump call now
-        t["sub_call"] = time.perf_counter()
-        assert L.xengXgpuSubSelect(prev.ptr, do.ptr, dv.ptr, dc.ptr, nvis, 4) == 0
-        t["sub_done"] = time.perf_counter()
+        done = ctypes.c_int(-1)
+        t["sub_rc"] = L.xengXgpuSubSelect(prev.ptr, do.ptr, dv.ptr, dc.ptr, nvis, 4)
+        t["query_rc"] = L.xengXgpuDumpDone(0, ctypes.byref(done))
+        t["dump_done_at_sub_return"] = done.value
 
     a, b = threading.Thread(target=corr_thread), threading.Thread(target=subsel_thread)
     a.start(); b.start(); a.join(); b.join()
+    assert t["sub_rc"] == 0 and t["query_rc"] == 0
     assert np.array_equal(do.download(np.int32).reshape(nchan // 4, nvis, 2), exp)
-    dump_wait = t["dump_done"] - t["dump_call"]
-    assert dump_wait > 0.010, dump_wait               # the dump really was waiting behind the queue
-    assert t["sub_done"] < t["dump_done"] - 0.005, (t["sub_done"] - t["sub_call"], dump_wait)
+    assert t["dump_done_at_sub_return"] == 0          # SubSelect came back while the dump it must not wait for was still queued
+    assert t["dump_rc"] == 0 and t["rc"] == [0] * (nint * ngulp)      # ... and the dump call then completed
+    done = ctypes.c_int(-1)
+    gpu.ffi.call("xengXgpuDumpDone", 0, ctypes.byref(done))
+    assert done.value == 1
     # ordering with its own producer: enqueue one integration into `prev` asynchronously and sub-select it at once
     vin2 = gpu.synth_voltages(ntime * ngulp, nchan, nstand, "random", seed=6)
     x.inbuf.upload(vin2.reshape(-1))
