@@ -631,6 +631,51 @@ class HipBackend:
     def cdedisp_sync(self):
         ffi.call("xengCdedispSync")
 
+    # ---- coherent dedispersion with long transforms (BeamCoherentDedisperseLong; include/xeng.h "Coherent dedispersion with long
+    # transforms"): xengCdedisp*'s contract for 2^14 to 2^20 points, a context of its own, its kernels on the beamformer's stream
+    def cdlong_initialize(self, gpu, nchan, nbeam, ntime, pair0, npair, nfft, overlap):
+        return self._lib.xengCdlongInitialize(int(gpu), int(nchan), int(nbeam), int(ntime), int(pair0), int(npair), int(nfft), int(overlap))
+
+    def cdlong_set_chirp(self, pair, table):
+        """table: host complex64 [nchan][nfft] of pair `pair`, C-contiguous, natural DFT order, 1/nfft included.  Waits for the
+        context's work in flight; holds from the next block to complete."""
+        import numpy as np
+        if not (isinstance(table, np.ndarray) and table.dtype == np.complex64 and table.flags['C_CONTIGUOUS']):
+            raise TypeError("cdlong_set_chirp: the table must be a C-contiguous complex64 array")
+        return self._lib.xengCdlongSetChirp(int(pair), table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+
+    def cdlong_run(self, in_arr, out_arr):
+        """Enqueue only: cf32 [nchan][nbeam][ntime] in; (status, nblocks).  out_arr gets cf32 [nblocks][nchan][2 npair][L] and may be
+        None on a call that completes no block; cdlong_mark / wait cover it."""
+        n = ctypes.c_int(0)
+        rv = self._enq.xengCdlongRun(in_arr.ptr, None if out_arr is None else out_arr.ptr, ctypes.byref(n))
+        return rv, n.value
+
+    def cdlong_reset(self):
+        """The next input sample counts as sample 0 (host state only)."""
+        ffi.check("xengCdlongReset", self._enq.xengCdlongReset())
+
+    def cdlong_info(self):
+        """(the step L, the most blocks a call completes, samples taken since the last reset, blocks completed since the reset)"""
+        s, m, n, b = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong()
+        ffi.call("xengCdlongGetInfo", ctypes.byref(s), ctypes.byref(m), ctypes.byref(n), ctypes.byref(b))
+        return s.value, m.value, n.value, b.value
+
+    def cdlong_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengCdlongCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def cdlong_mark(self):
+        return self._mark("xengCdlongMark")
+
+    def cdlong_wait(self, ticket):
+        self._wait("xengCdlongTicketDone", "xengCdlongWait", ticket)
+
+    def cdlong_sync(self):
+        ffi.call("xengCdlongSync")
+
     # ---- dirty images of the fine-channel visibilities (UpchanImage; include/xeng.h "Dirty images of the fine-channel
     # visibilities"): a context of its own, its kernel on the beamformer's stream
     def image_initialize(self, gpu, nstand, nfine, nfavg, npix):
@@ -1063,7 +1108,7 @@ class HipBackend:
         ffi.call("xengImsearchSync")
 
     # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold, Period,
-    # Cdedisp, Image, Gaincal, Calapply, Peel, Clean, Flag, Predict, Imsearch)
+    # Cdedisp, Cdlong, Image, Gaincal, Calapply, Peel, Clean, Flag, Predict, Imsearch)
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))

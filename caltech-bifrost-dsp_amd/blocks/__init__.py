@@ -25,7 +25,8 @@ from .period_search import period_candidates, period_pfa
 from .beam_fold_block import BeamFold
 from .fold import fold_phase, fold_rotations, fold_rotations_coherent, profile_snr
 from .beam_coherent_dedisperse_block import BeamCoherentDedisperse
-from .coherent_dedisp import cdedisp_plan, chirp_table, smear_samples
+from .beam_coherent_dedisperse_long_block import BeamCoherentDedisperseLong
+from .coherent_dedisp import cdedisp_plan, cdedisp_plan_long, chirp_table, smear_samples
 from .upchan_image_block import UpchanImage
 from .upchan_clean_block import UpchanClean
 from .imaging import (clean_components, clean_layout, component_visibilities, components_to_model, direction_list, image_norm, patch, pixel_grid, psf, restore,
@@ -41,5 +42,5 @@ from .flagging import flag_factors, flag_summary, flag_visibilities, stand_weigh
 from .calibration import apply_gains, direction_model_visibilities, inverse_gains, model_flux, model_visibilities, reference_phase
 from .spectral_kurtosis import incoherent_beam, sk_flags, sk_limits, spectral_kurtosis
 
-__all__ = ["Block", "Corr", "CorrAcc", "Beamform", "BeamformSumBeams", "Copy", "CorrSubsel", "CorrOutputFull", "Snap2Ingest", "BeamformOutput", "CorrOutputPart", "BeamformVlbiOutput", "UpchanBeamform", "TbfSource", "UpchanCorr", "UpchanSumBeams", "UpchanSpectra", "BeamDedisperse", "dm_delays", "BeamPulseSearch", "pulse_candidates", "BeamPeriodSearch", "period_candidates", "period_pfa", "BeamFold", "fold_phase", "fold_rotations", "fold_rotations_coherent", "profile_snr", "BeamCoherentDedisperse", "chirp_table", "smear_samples", "cdedisp_plan", "UpchanImage", "pixel_grid", "patch", "steering_delays", "direction_list", "image_norm", "stokes_i", "UpchanClean", "psf", "clean_components", "clean_layout", "restore", "components_to_model", "UpchanGainCal", "UpchanCalApply", "UpchanPeel", "UpchanFlag", "UpchanPredict", "component_visibilities", "UpchanImageSearch", "IMSEARCH_RECORD", "group_frequencies", "image_dm_delays", "image_candidates", "flag_factors", "stand_weights", "flag_visibilities", "flag_summary", "model_visibilities", "direction_model_visibilities", "model_flux", "apply_gains", "inverse_gains", "reference_phase", "spectral_kurtosis", "sk_limits", "sk_flags", "incoherent_beam", "regtile_index", "tri_index",
+__all__ = ["Block", "Corr", "CorrAcc", "Beamform", "BeamformSumBeams", "Copy", "CorrSubsel", "CorrOutputFull", "Snap2Ingest", "BeamformOutput", "CorrOutputPart", "BeamformVlbiOutput", "UpchanBeamform", "TbfSource", "UpchanCorr", "UpchanSumBeams", "UpchanSpectra", "BeamDedisperse", "dm_delays", "BeamPulseSearch", "pulse_candidates", "BeamPeriodSearch", "period_candidates", "period_pfa", "BeamFold", "fold_phase", "fold_rotations", "fold_rotations_coherent", "profile_snr", "BeamCoherentDedisperse", "BeamCoherentDedisperseLong", "chirp_table", "smear_samples", "cdedisp_plan", "cdedisp_plan_long", "UpchanImage", "pixel_grid", "patch", "steering_delays", "direction_list", "image_norm", "stokes_i", "UpchanClean", "psf", "clean_components", "clean_layout", "restore", "components_to_model", "UpchanGainCal", "UpchanCalApply", "UpchanPeel", "UpchanFlag", "UpchanPredict", "component_visibilities", "UpchanImageSearch", "IMSEARCH_RECORD", "group_frequencies", "image_dm_delays", "image_candidates", "flag_factors", "stand_weights", "flag_visibilities", "flag_summary", "model_visibilities", "direction_model_visibilities", "model_flux", "apply_gains", "inverse_gains", "reference_phase", "spectral_kurtosis", "sk_limits", "sk_flags", "incoherent_beam", "regtile_index", "tri_index",
            "COMMAND_OK", "COMMAND_NOT_RECOGNIZED", "COMMAND_WRONG_TYPE", "COMMAND_INVALID"]

@@ -23,7 +23,8 @@ reader never saw) resets the context, and after a gap the output restarts in a s
 it holds.  A `dms` command (npair finite numbers) uploads a new table, which takes effect at the next block; the output restarts in
 a sequence of its own there too, so that every sequence's cdedisp_dm is the DM its samples were filtered with.
 
-Not built: a bandpass taper, transforms above 2^13 points (the sweep below about 28 MHz at DM 10 needs them), barycentring.
+Transforms above 2^13 points (the sweep below about 28 MHz at DM 10 needs them) are BeamCoherentDedisperseLong's
+(beam_coherent_dedisperse_long_block.py), a subclass of this block on an engine of its own.  Not built: a bandpass taper, barycentring.
 BeamDedisperse's single delay table cannot express a coherent DM per pair: behind this block it is right for one DM only."""
 import json
 import math
@@ -46,6 +47,13 @@ def _dms_ok(v, npair):
 
 class BeamCoherentDedisperse(Block):
     STREAM_DEPTH = 4        # gulps whose kernels may be in flight behind the one being enqueued (in-repo rings)
+    # what BeamCoherentDedisperseLong changes: the name in messages, the backend's methods (ENGINE + '_run' ...), the entry point
+    # named when a run fails, the transform lengths and the planner
+    WHO = WHO
+    ENGINE = 'cdedisp'
+    RUN_NAME = "xengCdedispRun"
+    NFFT_RANGE = (NFFT_MIN, NFFT_MAX, "2^8 to 2^13")
+    plan = staticmethod(cdedisp_plan)
 
     def __init__(self, log, iring, oring, nchan, nbeam, ntime_gulp, dms, pair0=0, npair=None, nfft=None, overlap=None, multiple_of=1,
                  guarantee=True, core=-1, gpu=-1, etcd_client=None, backend=None):
@@ -53,15 +61,15 @@ class BeamCoherentDedisperse(Block):
         if npair is None:
             npair = nbeam // 2 - pair0
         if min(nchan, nbeam, ntime_gulp) <= 0:
-            raise ValueError("%s: sizes nchan=%r nbeam=%r ntime_gulp=%r must be positive" % (WHO, nchan, nbeam, ntime_gulp))
+            raise ValueError("%s: sizes nchan=%r nbeam=%r ntime_gulp=%r must be positive" % (self.WHO, nchan, nbeam, ntime_gulp))
         if pair0 < 0 or npair <= 0 or pair0 + npair > nbeam // 2:
-            raise ValueError("%s: pairs [%d, %d) not a non-empty range of the %d pairs of %d beams" % (WHO, pair0, pair0 + npair, nbeam // 2, nbeam))
+            raise ValueError("%s: pairs [%d, %d) not a non-empty range of the %d pairs of %d beams" % (self.WHO, pair0, pair0 + npair, nbeam // 2, nbeam))
         if not _dms_ok(dms, npair):
-            raise ValueError("%s: `dms` must be %d finite numbers, one per pair: %r" % (WHO, npair, dms))
+            raise ValueError("%s: `dms` must be %d finite numbers, one per pair: %r" % (self.WHO, npair, dms))
         if (nfft is None) != (overlap is None):
-            raise ValueError("%s: give both nfft and overlap, or neither" % WHO)
+            raise ValueError("%s: give both nfft and overlap, or neither" % self.WHO)
         if not isinstance(multiple_of, int) or multiple_of < 1:
-            raise ValueError("%s: multiple_of %r is not a positive integer" % (WHO, multiple_of))
+            raise ValueError("%s: multiple_of %r is not a positive integer" % (self.WHO, multiple_of))
         if nfft is not None:
             self._check_plan(nfft, overlap, multiple_of)
         self.nchan, self.nbeam, self.ntime_gulp, self.pair0, self.npair, self.gpu = nchan, nbeam, ntime_gulp, pair0, npair, gpu
@@ -80,24 +88,28 @@ class BeamCoherentDedisperse(Block):
         if nfft is not None:
             self._initialize()
 
-    @staticmethod
-    def _check_plan(nfft, overlap, multiple_of):
-        if not isinstance(nfft, int) or not NFFT_MIN <= nfft <= NFFT_MAX or nfft & (nfft - 1):
-            raise ValueError("%s: nfft %r is not a power of two from 2^8 to 2^13" % (WHO, nfft))
+    def _engine(self, name):
+        return getattr(self._bf, '%s_%s' % (self.ENGINE, name))
+
+    @classmethod
+    def _check_plan(self, nfft, overlap, multiple_of):
+        lo, hi, text = self.NFFT_RANGE
+        if not isinstance(nfft, int) or not lo <= nfft <= hi or nfft & (nfft - 1):
+            raise ValueError("%s: nfft %r is not a power of two from %s" % (self.WHO, nfft, text))
         if not isinstance(overlap, int) or overlap < 0 or overlap & 1 or overlap > nfft // 2:
-            raise ValueError("%s: overlap %r is not an even number from 0 to nfft/2 = %d" % (WHO, overlap, nfft // 2))
+            raise ValueError("%s: overlap %r is not an even number from 0 to nfft/2 = %d" % (self.WHO, overlap, nfft // 2))
         if (nfft - overlap) % multiple_of:
-            raise ValueError("%s: the step %d is not a multiple of %d" % (WHO, nfft - overlap, multiple_of))
+            raise ValueError("%s: the step %d is not a multiple of %d" % (self.WHO, nfft - overlap, multiple_of))
 
     def _initialize(self):
-        self._call('cdedisp_initialize', self.gpu, self.nchan, self.nbeam, self.ntime_gulp, self.pair0, self.npair, self.nfft, self.overlap)
+        self._call(self.ENGINE + '_initialize', self.gpu, self.nchan, self.nbeam, self.ntime_gulp, self.pair0, self.npair, self.nfft, self.overlap)
         self.step = self.nfft - self.overlap
         self.max_blocks = -(-self.ntime_gulp // self.step)
         self._live = True
         self._nsamples = self._nblocks = 0
 
     def _reset(self, first):
-        self._bf.cdedisp_reset()
+        self._engine('reset')()
         self._nsamples = self._nblocks = 0
         self._first = first
 
@@ -109,7 +121,10 @@ class BeamCoherentDedisperse(Block):
         freqs, chan_bw = self._freqs(ihdr)
         sweep = max(float(np.max(smear_samples(freqs, chan_bw, d))) for d in self.dms)
         if sweep > self.overlap:
-            self.log.warning("%s >> a sweep of %.0f samples is longer than the overlap of %d: the pulses wrap" % (WHO, sweep, self.overlap))
+            self.log.warning("%s >> a sweep of %.0f samples is longer than the overlap of %d: the pulses wrap" % (self.WHO, sweep, self.overlap))
+        self._upload_chirp(freqs, chan_bw)
+
+    def _upload_chirp(self, freqs, chan_bw):
         self._call('cdedisp_set_chirp', np.ascontiguousarray(chirp_table(freqs, chan_bw, self.dms, self.nfft)))
 
     def output_header(self, ihdr, start):
@@ -121,17 +136,17 @@ class BeamCoherentDedisperse(Block):
     def _check_header(self, ihdr):
         """Beamform's voltage output only (UpchanSumBeams' check): not the products of another reader."""
         if ihdr.get('nchan') != self.nchan or ihdr.get('nbeam') != self.nbeam:
-            raise ValueError("%s: %r channels x %r beams in the header, %d x %d configured" % (WHO, ihdr.get('nchan'), ihdr.get('nbeam'), self.nchan, self.nbeam))
+            raise ValueError("%s: %r channels x %r beams in the header, %d x %d configured" % (self.WHO, ihdr.get('nchan'), ihdr.get('nbeam'), self.nchan, self.nbeam))
         if ihdr.get('nbit') != 32 or not ihdr.get('complex') or ihdr.get('npol') != 1:
             raise ValueError("%s: the input is not single-pol cf32 voltage beams (nbit %r, complex %r, npol %r)"
-                             % (WHO, ihdr.get('nbit'), ihdr.get('complex'), ihdr.get('npol')))
+                             % (self.WHO, ihdr.get('nbit'), ihdr.get('complex'), ihdr.get('npol')))
         for k in ('acc_len', 'ntime_sum', 'nupchan'):
             if k in ihdr:
-                raise ValueError("%s: the input carries '%s': integrated or channelised products, not voltage beams" % (WHO, k))
+                raise ValueError("%s: the input carries '%s': integrated or channelised products, not voltage beams" % (self.WHO, k))
         for k in ('bw_hz', 'sfreq'):
             v = ihdr.get(k)
             if not isinstance(v, (int, float)) or isinstance(v, bool) or not math.isfinite(v) or v <= 0:
-                raise ValueError("%s: the header's '%s' is %r: the chirp needs the band" % (WHO, k, v))
+                raise ValueError("%s: the header's '%s' is %r: the chirp needs the band" % (self.WHO, k, v))
 
     def main(self):
         self.bind()
@@ -142,7 +157,7 @@ class BeamCoherentDedisperse(Block):
         can_copy = hasattr(self._bf, 'copy_async')
         self._staged = streaming and self.oring.space == 'cuda_host' and can_copy
         self._dev = None
-        with InFlight(self._bf.cdedisp_wait, self._bf.cdedisp_sync, self._bf, outstanding=lambda: 2 * self.max_blocks) as inflight, \
+        with InFlight(self._engine('wait'), self._engine('sync'), self._bf, outstanding=lambda: 2 * self.max_blocks) as inflight, \
                 self.oring.begin_writing() as oring:
             for iseq in self.iring.read(guarantee=self.guarantee):
                 self._sequence(iseq, oring, streaming, can_copy, inflight)
@@ -154,8 +169,8 @@ class BeamCoherentDedisperse(Block):
         inflight.retire(0)
         if self.nfft is None:
             freqs, chan_bw = self._freqs(ihdr)
-            self.nfft, self.overlap = cdedisp_plan(freqs, chan_bw, max(abs(d) for d in self.dms), self.multiple_of)
-            self.log.info("%s >> planned nfft %d, overlap %d" % (WHO, self.nfft, self.overlap))
+            self.nfft, self.overlap = self.plan(freqs, chan_bw, max(abs(d) for d in self.dms), self.multiple_of)
+            self.log.info("%s >> planned nfft %d, overlap %d" % (self.WHO, self.nfft, self.overlap))
         if not self._live:
             self._initialize()
         unit = self.nchan * 2 * self.npair * self.step * 8
@@ -178,7 +193,7 @@ class BeamCoherentDedisperse(Block):
                     # samples this reader never saw: the block in progress does not line up with what comes now
                     if self._nsamples > self._nblocks * self.step:
                         self.update_stats({'ndropped': self.stats['ndropped'] + 1})
-                    self.log.warning("%s >> samples [%d, %d) were not read: the stream starts again" % (WHO, expected, this_gulp_time))
+                    self.log.warning("%s >> samples [%d, %d) were not read: the stream starts again" % (self.WHO, expected, this_gulp_time))
                     self._reset(this_gulp_time)
                     restart = True
                 if self.update_pending:
@@ -221,21 +236,21 @@ class BeamCoherentDedisperse(Block):
                         if self._dev is None or self._dev.nbytes != self.max_blocks * unit:
                             self._dev = XArray(shape=(self.max_blocks * unit,), dtype=np.uint8, space=self._bf.space_in)
                         target = self._dev
-                    rv, done = self._bf.cdedisp_run(held, target)
+                    rv, done = self._engine('run')(held, target)
                     if rv != self._bf.BF_STATUS_SUCCESS:
-                        raise RuntimeError("xengCdedispRun returned %d: %s" % (rv, self._bf.last_error()))
+                        raise RuntimeError("%s returned %d: %s" % (self.RUN_NAME, rv, self._bf.last_error()))
                     if done != nb:
-                        raise RuntimeError("%s: the context completed %d block(s) where the block counted %d" % (WHO, done, nb))
+                        raise RuntimeError("%s: the context completed %d block(s) where the block counted %d" % (self.WHO, done, nb))
                     self._nsamples, self._nblocks = after, self._nblocks + nb
                     if nb:
                         self.update_stats({'nblock': self.stats['nblock'] + nb, 'last_end_sample': self._first + self._nblocks * self.step + self.overlap // 2})
                     if direct or staged or (streaming and nb == 0):
                         osps, ospans = ospans, []
-                        inflight.push(self._bf.cdedisp_mark(), osps, held, stage)
+                        inflight.push(self._engine('mark')(), osps, held, stage)
                         inflight.retire(self.STREAM_DEPTH)
                     else:
                         inflight.retire(0)      # (spans are committed in order)
-                        self._bf.cdedisp_sync()
+                        self._engine('sync')()
                         while ospans:
                             k = nb - len(ospans)
                             copy_array(ospans[0].data, self._dev.byte_slice(k * unit, unit))   # (synchronous copy)

@@ -16,6 +16,7 @@ import numpy as np
 from .dedisp import KDM
 
 NFFT_MIN, NFFT_MAX = 1 << 8, 1 << 13
+NFFT_LONG_MIN, NFFT_LONG_MAX = 1 << 14, 1 << 20     # BeamCoherentDedisperseLong (cdedisp_plan_long)
 GUARD_FACTOR = 1.5      # overlap / largest sweep (cdedisp_plan)
 
 
@@ -62,11 +63,22 @@ def cdedisp_plan(freqs_hz, chan_bw_hz, dm_max, multiple_of=1):
     Why 1.5: the chirp's response is as long as the sweep, but its spectrum is cut off at the channel's edges, which rings beyond
     that.  With half of M discarded on either side, 1.5 sweeps bring an impulse dispersed in float64 back with 0.9999 of its energy
     in one sample wherever it falls in a block (tests/test_cdedisp_cpu.py states the figures)."""
+    return _plan("cdedisp_plan", NFFT_MIN, NFFT_MAX, freqs_hz, chan_bw_hz, dm_max, multiple_of)
+
+
+def cdedisp_plan_long(freqs_hz, chan_bw_hz, dm_max, multiple_of=1):
+    """(nfft, overlap) for BeamCoherentDedisperseLong: cdedisp_plan's rule over the powers of two from 2^14 to 2^20 (xengCdlong*),
+    for the sweeps that cdedisp_plan refuses -- at 23.9 kHz channels and DM 10, 2^14 at 25 MHz, 2^15 at 20 MHz and 2^16 at 15 MHz.
+    A sweep that would fit a shorter transform still gets 2^14 here.  ValueError when there is none."""
+    return _plan("cdedisp_plan_long", NFFT_LONG_MIN, NFFT_LONG_MAX, freqs_hz, chan_bw_hz, dm_max, multiple_of)
+
+
+def _plan(who, nfft_min, nfft_max, freqs_hz, chan_bw_hz, dm_max, multiple_of):
     if not isinstance(multiple_of, (int, np.integer)) or multiple_of < 1:
-        raise ValueError("cdedisp_plan: multiple_of %r is not a positive integer" % (multiple_of,))
+        raise ValueError("%s: multiple_of %r is not a positive integer" % (who, multiple_of))
     need = GUARD_FACTOR * float(np.max(smear_samples(freqs_hz, chan_bw_hz, dm_max)))
-    nfft = NFFT_MIN
-    while nfft <= NFFT_MAX:
+    nfft = nfft_min
+    while nfft <= nfft_max:
         m = int(np.ceil(need))
         m += m & 1
         while m <= nfft // 2:
@@ -74,5 +86,5 @@ def cdedisp_plan(freqs_hz, chan_bw_hz, dm_max, multiple_of=1):
                 return nfft, m
             m += 2
         nfft *= 2
-    raise ValueError("cdedisp_plan: a sweep of %.0f samples needs an overlap of %.0f, more than half of the longest transform (%d points)%s"
-                     % (need / GUARD_FACTOR, need, NFFT_MAX, "" if multiple_of == 1 else ", with a step that is a multiple of %d" % multiple_of))
+    raise ValueError("%s: a sweep of %.0f samples needs an overlap of %.0f, more than half of the longest transform (%d points)%s"
+                     % (who, need / GUARD_FACTOR, need, nfft_max, "" if multiple_of == 1 else ", with a step that is a multiple of %d" % multiple_of))

@@ -130,6 +130,10 @@ SYMBOLS = {
     "xengCdedispRun": [_vp, _vp, _pi], "xengCdedispReset": [], "xengCdedispGetInfo": [_pi, _pi, _pll, _pll], "xengCdedispCheckGuards": [_pi],
     "xengCdedispMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCdedispWait": [ctypes.c_ulonglong],
     "xengCdedispTicketDone": [ctypes.c_ulonglong, _pi], "xengCdedispSync": [], "xengCdedispDestroy": [],
+    "xengCdlongInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdlongSetChirp": [_i, ctypes.POINTER(ctypes.c_float)],
+    "xengCdlongRun": [_vp, _vp, _pi], "xengCdlongReset": [], "xengCdlongGetInfo": [_pi, _pi, _pll, _pll], "xengCdlongCheckGuards": [_pi],
+    "xengCdlongMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCdlongWait": [ctypes.c_ulonglong],
+    "xengCdlongTicketDone": [ctypes.c_ulonglong, _pi], "xengCdlongSync": [], "xengCdlongDestroy": [],
     "xengImageInitialize": [_i, _i, _i, _i, _i], "xengImageGetInfo": [_pi, _pi, _pi, ctypes.POINTER(ctypes.c_double)],
     "xengImageSetGeometry": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], "xengImageSetWeights": [ctypes.POINTER(ctypes.c_float), _i],
     "xengImageRun": [_vp, _vp], "xengImageCheckGuards": [_pi], "xengImageMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengImageWait": [ctypes.c_ulonglong],
@@ -220,6 +224,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengFoldRun", "xengFoldReset", "xengFoldMark", "xengFoldTicketDone",
                 "xengPeriodRun", "xengPeriodReset", "xengPeriodMark", "xengPeriodTicketDone",
                 "xengCdedispRun", "xengCdedispReset", "xengCdedispMark", "xengCdedispTicketDone",
+                "xengCdlongRun", "xengCdlongReset", "xengCdlongMark", "xengCdlongTicketDone",
                 "xengImageRun", "xengImageMark", "xengImageTicketDone",
                 "xengGaincalRun", "xengGaincalMark", "xengGaincalTicketDone",
                 "xengCalapplyRun", "xengCalapplyMark", "xengCalapplyTicketDone",

@@ -928,6 +928,61 @@ int xengCdedispTicketDone(unsigned long long ticket, int *done);
 int xengCdedispSync(void);
 int xengCdedispDestroy(void);
 
+/* ---------------------------------------------------------------- Coherent dedispersion with long transforms
+ * BeamCoherentDedisperseLong (no reference counterpart): xengCdedisp* for transforms of 2^14 to 2^20 points, which no work-group's
+ * LDS holds -- the sweeps of the band below about 47 MHz at the DMs of known pulsars.  A second engine beside xengCdedisp*, which
+ * stays what it is; a context of its own, independent of all others, whose kernels run on the beamformer's stream -- rings
+ * declared 'beam' cover them, and xengBeamformSync waits for them too.  An ingest kernel per call (one more where a call straddles
+ * a block boundary) and, per completed block, a four-step FFT through a scratch buffer in device memory: column transforms, the
+ * overlap copy, row transforms with the table between them, column transforms (csrc/cdlong_kernels.h).
+ *   in       cf32[nchan][nbeam][ntime], the output of xengBeamformRun unchanged; 16-byte aligned; never written.  ntime is fixed
+ *            per context.  The selected beams are 2*pair0 .. 2*(pair0 + npair) - 1; a row is one (c, selected beam b),
+ *            nrow = nchan * 2*npair.  Samples are counted from the last reset (xengCdlongReset, Initialize).
+ *   sizes    NFFT = nfft, a power of two, 2^14 <= NFFT <= 2^20.  M = overlap: even, 0 <= M <= NFFT/2.  L = NFFT - M, the step.
+ *   block    Block j covers the input samples [j*L, j*L + NFFT) and runs in the call that brings its last sample.  Per row:
+ *              X[k] = sum_n x[n] * exp(-2 pi i k n / NFFT),  Y[k] = X[k] * T[p][c][k],  y[n] = sum_k Y[k] * exp(+2 pi i k n / NFFT)
+ *            with p = b div 2 (both beams of a pair share a filter) and nothing else scaled: the table carries the 1/NFFT.  The
+ *            block's output is y[M/2 .. M/2 + L): output sample i of the stream is input sample i + M/2, and the blocks tile the
+ *            time axis without a gap.  fp32, held to a tolerance; no atomics, one owner per word.
+ *   out      cf32[nblk][nchan][2*npair][L], one unit per block the call completes, 16-byte aligned; nothing past nblk units is
+ *            written.  A call completes at most ceil(ntime / L) blocks (xengCdlongGetInfo).
+ *   table    per pair, cf32[nchan][NFFT] on the host in natural DFT order: bin k is the offset k*D/NFFT from the channel's centre
+ *            for k < NFFT/2 and (k - NFFT)*D/NFFT above, D the channel width.  The upload is pair by pair: the whole table of 96
+ *            channels x 16 pairs at 2^17 points is 1.6 GB, and twice that in the float64 it is built from.  After Initialize it is
+ *            1/NFFT everywhere: a pure latency of M/2 samples.
+ *   state    between two guard bands of 64 KiB: the time buffer cf32[nrow][NFFT], the scratch buffer cf32[nrow][NFFT], the table
+ *            cf32[npair][nchan][NFFT] (in the kernels' order) and the twiddles exp(-2 pi i k / n) for n = NFFT and its two factors
+ *            (float64 on the host, rounded once).  xengCdlongReset moves only the host's counts.
+ * The output is a fixed function of the sample stream and the table: bit-identical whatever ntime, however the stream falls on
+ * calls, after a Reset as in a fresh context, and whatever else runs on the GPU.  A non-finite input sample makes the blocks of
+ * its own row that contain it non-finite and changes no other word.
+ * Rejected at Initialize, before any device is touched: a non-positive size, pairs outside [0, nbeam/2), nfft not a power of two
+ * in 2^14..2^20 (2^13 and 2^21 among them), overlap odd, negative or above nfft/2, nchan*2*npair > 65535, an input or a state
+ * above XENG_CDLONG_MAX_STATE_BYTES; after the device is known, an LDS need (64 KiB at most) above what a work-group may take.
+ * Rejected by SetChirp: a NULL table, a pair outside [0, npair), a non-finite word.  Rejected by Run without a launch: a NULL input
+ * or result, a misaligned pointer, a NULL output on a call that completes a block.  Every call without a context:
+ * XENG_STATUS_INVALID_STATE. */
+#define XENG_CDLONG_MAX_STATE_BYTES (1LL << 35)
+int xengCdlongInitialize(int gpu, int nchan, int nbeam, int ntime, int pair0, int npair, int nfft, int overlap);
+/* table: cf32[nchan][nfft] on the host, the filter of pair `pair` (0 <= pair < npair; see above).  Waits for the context's work in
+ * flight, uploads the pair's table and does not touch the time buffer: it holds from the next block to complete. */
+int xengCdlongSetChirp(int pair, const float *table);
+/* enqueue only.  *nblocks is the number of blocks the call completes; the host's sample count decides it before anything is
+ * enqueued, and out_dev is written for those blocks only.  out_dev may be NULL on a call that completes none. */
+int xengCdlongRun(const void *in_dev, void *out_dev, int *nblocks);
+/* host state only, nothing is launched and nothing cleared: the next input sample counts as sample 0 */
+int xengCdlongReset(void);
+/* the step L, the most blocks one call completes, samples taken and blocks completed since the last reset */
+int xengCdlongGetInfo(int *step, int *max_blocks_per_call, long long *nsamples_since_reset, long long *nblocks_since_reset);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengCdlongCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengCdlongMark(unsigned long long *ticket);
+int xengCdlongWait(unsigned long long ticket);
+int xengCdlongTicketDone(unsigned long long ticket, int *done);
+int xengCdlongSync(void);
+int xengCdlongDestroy(void);
+
 /* ---------------------------------------------------------------- Dirty images of the fine-channel visibilities
  * UpchanImage (no reference counterpart: the reference writes its visibilities to disk): the direct Fourier sum of UpchanCorr's
  * matrix over a list of directions -- the matrix beamformed onto every pixel, exact for a non-coplanar array, no grid and no FFT.
