@@ -586,6 +586,58 @@ class HipBackend:
     def period_sync(self):
         ffi.call("xengPeriodSync")
 
+    # ---- fast-folding search of the dedispersed beams (BeamFfaSearch; include/xeng.h "Fast-folding search of the dedispersed
+    # beams"): a context of its own, its kernels on the beamformer's stream
+    def ffa_initialize(self, gpu, npair, ndm, nwin, nprod, nds, nt, noct, pmin, pmax, nwidth):
+        return self._lib.xengFfaInitialize(int(gpu), int(npair), int(ndm), int(nwin), int(nprod), int(nds), int(nt), int(noct), int(pmin), int(pmax),
+                                           int(nwidth))
+
+    def ffa_run(self, in_arr, nwin_call, out_arr):
+        """Enqueue only: f32 [nwin_call][npair][ndm][nprod] in; (status, completed).  out_arr, [npair][ndm][noct][nwidth] records
+        {f32 snr, i32 p, i32 i, i32 j}, is written only when the call completes a segment (completed = 1) and may be None on
+        every other call; ffa_mark / wait cover it."""
+        done = ctypes.c_int(0)
+        rv = self._enq.xengFfaRun(in_arr.ptr, int(nwin_call), None if out_arr is None else out_arr.ptr, ctypes.byref(done))
+        return rv, done.value
+
+    def ffa_reset(self):
+        """The next input counts as window 0 of a new segment (host state only)."""
+        ffi.check("xengFfaReset", self._enq.xengFfaReset())
+
+    def ffa_info(self):
+        """(windows taken since the last reset, segments completed since the reset)"""
+        n, k = ctypes.c_longlong(), ctypes.c_longlong()
+        ffi.call("xengFfaGetInfo", ctypes.byref(n), ctypes.byref(k))
+        return n.value, k.value
+
+    def ffa_stats(self, npair, ndm, noct):
+        """Waits for the context's work; {c, m, v, g} of the last completed segment, float32 [npair][ndm][noct][4]."""
+        import numpy as np
+        st = np.empty((npair, ndm, noct, 4), np.float32)
+        ffi.call("xengFfaGetStats", st.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+        return st
+
+    def ffa_guards_intact(self):
+        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
+        ok = ctypes.c_int()
+        ffi.call("xengFfaCheckGuards", ctypes.byref(ok))
+        return bool(ok.value)
+
+    def ffa_mark(self):
+        return self._mark("xengFfaMark")
+
+    def ffa_wait(self, ticket):
+        self._wait("xengFfaTicketDone", "xengFfaWait", ticket)
+
+    def ffa_ticket_done(self, ticket):
+        """Never blocks: whether everything enqueued before the ticket has completed."""
+        d = ctypes.c_int()
+        ffi.check("xengFfaTicketDone", self._enq.xengFfaTicketDone(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
+        return bool(d.value)
+
+    def ffa_sync(self):
+        ffi.call("xengFfaSync")
+
     # ---- coherent dedispersion of the voltage beams (BeamCoherentDedisperse; include/xeng.h "Coherent dedispersion of the voltage
     # beams"): a context of its own, its kernels on the beamformer's stream
     def cdedisp_initialize(self, gpu, nchan, nbeam, ntime, pair0, npair, nfft, overlap):

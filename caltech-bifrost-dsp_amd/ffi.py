@@ -126,6 +126,10 @@ SYMBOLS = {
     "xengPeriodGetSpectrum": [ctypes.POINTER(ctypes.c_float), _pi], "xengPeriodCheckGuards": [_pi],
     "xengPeriodMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengPeriodWait": [ctypes.c_ulonglong],
     "xengPeriodTicketDone": [ctypes.c_ulonglong, _pi], "xengPeriodSync": [], "xengPeriodDestroy": [],
+    "xengFfaInitialize": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i], "xengFfaRun": [_vp, _i, _vp, _pi], "xengFfaReset": [],
+    "xengFfaGetInfo": [_pll, _pll], "xengFfaGetStats": [ctypes.POINTER(ctypes.c_float)], "xengFfaCheckGuards": [_pi],
+    "xengFfaMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengFfaWait": [ctypes.c_ulonglong],
+    "xengFfaTicketDone": [ctypes.c_ulonglong, _pi], "xengFfaSync": [], "xengFfaDestroy": [],
     "xengCdedispInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdedispSetChirp": [ctypes.POINTER(ctypes.c_float)],
     "xengCdedispRun": [_vp, _vp, _pi], "xengCdedispReset": [], "xengCdedispGetInfo": [_pi, _pi, _pll, _pll], "xengCdedispCheckGuards": [_pi],
     "xengCdedispMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCdedispWait": [ctypes.c_ulonglong],
@@ -223,6 +227,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengPulseRun", "xengPulseReset", "xengPulseMark", "xengPulseTicketDone",
                 "xengFoldRun", "xengFoldReset", "xengFoldMark", "xengFoldTicketDone",
                 "xengPeriodRun", "xengPeriodReset", "xengPeriodMark", "xengPeriodTicketDone",
+                "xengFfaRun", "xengFfaReset", "xengFfaMark", "xengFfaTicketDone",
                 "xengCdedispRun", "xengCdedispReset", "xengCdedispMark", "xengCdedispTicketDone",
                 "xengCdlongRun", "xengCdlongReset", "xengCdlongMark", "xengCdlongTicketDone",
                 "xengImageRun", "xengImageMark", "xengImageTicketDone",

@@ -875,6 +875,78 @@ int xengPeriodTicketDone(unsigned long long ticket, int *done);
 int xengPeriodSync(void);
 int xengPeriodDestroy(void);
 
+/* ---------------------------------------------------------------- Fast-folding search of the dedispersed beams
+ * BeamFfaSearch (no reference counterpart: the reference has no detection stage): the fast folding algorithm (Staelin 1969) for
+ * the long periods and small duty cycles the FFT search above is blind to.  Per series a segment of NT downsampled samples is
+ * folded at every integer base period and at the fractional periods between, in octaves of the time resolution; a circular boxcar
+ * matched filter runs over every folded profile; one peak record per series, octave and width comes out.  A context of its own,
+ * independent of all others, whose kernels run on the beamformer's stream -- rings declared 'beam' cover them, and
+ * xengBeamformSync waits for them too.  An ingest kernel per call; per completed segment a prepare kernel, a fold kernel per
+ * octave and a reduce kernel (csrc/ffa_kernels.h).
+ * Everything below is fp32 and fl() is one rounding to fp32; no product is contracted into a sum except where fmaf is written.
+ *   in       f32[nwin_call][npair][ndm][nprod], the output span of xengDedispRun unchanged; 16-byte aligned; never written.
+ *            1 <= nwin_call <= nwin.  A series is one (p, d), nser = npair*ndm.  z[n] as xengPeriodRun takes it: nprod = 1 the
+ *            word, nprod = 4 fl(XX + YY).  n counts windows since the last reset (xengFfaReset, Initialize).
+ *   downsample  u_0[k] = ((z[k*nds] + z[k*nds+1]) + ...) + z[k*nds+nds-1], one sequential chain of fp32 adds over nds windows,
+ *            1 <= nds <= XENG_FFA_MAX_NDS.  The running sum of a sample whose windows a call cuts is kept per series on the
+ *            device and taken up by the next call: a sample may straddle calls.
+ *   segment  NT = nt samples of u_0, 2^8 <= NT <= 2^14, a multiple of 2^(noct-1) and not necessarily a power of two.
+ *            nwin <= NT*nds, so that a call completes at most one segment.  Window n goes to slot (n div nds) mod NT of a time
+ *            buffer f32[nser][NT], filled by index.
+ *   octaves  o = 0 .. noct-1, 1 <= noct <= 6: u_o[k] = fl(u_{o-1}[2k] + u_{o-1}[2k+1]), of length N_o = NT >> o.
+ *   statistics  per (series, octave), the pivoted one-pass form of xengPulse*, the pivot c = u_o[0]: a = sum of fl(u_o[k] - c),
+ *            q = sum of its squares, m = fl(a*r), v = fmaf(-m, m, fl(q*r)) with r = (float)(1/N_o) from the host,
+ *            g = fl(1 / fl(sqrt(v))).  The summation order of a and q is the library's: they are held to a tolerance.  The
+ *            (series, octave) is VALID iff m is finite and 0 < v < +inf.  x_o[k] = fl(fl(u_o[k] - c) - m).
+ *   fold     for every integer base period p, pmin <= p <= pmax, 16 <= pmin <= pmax, 2*pmax <= N_{noct-1}: M is the largest
+ *            power of two with M*p <= N_o (M >= 2).  Row r is x_o[r*p .. r*p+p); samples past M*p are not read.  Stages
+ *            L = 2, 4 .. M: in every block of L rows, A its first L/2 rows and B its last, for i < L and j < p
+ *              out[i][j] = fl(A[i>>1][j] + B[i>>1][(j + ((i+1)>>1)) mod p])
+ *            After the last stage profile i of M is the fold at a period of p + i/(M-1) samples.  Every word is one add of two
+ *            fixed words: the bits do not depend on the schedule.
+ *   boxcars  circular, widths w = 2^iw, iw < nwidth, 1 <= nwidth <= 8, 2^(nwidth-1) <= pmin/2: B_1 = the profile,
+ *            B_{2w}[j] = fl(B_w[j] + B_w[(j+w) mod p]).
+ *   score    S = fl(fl(B_w[j] * g) * rho), rho = (float)(1/sqrt(w*M)) from a host table indexed [iw][log2 M].
+ *   out      [npair][ndm][noct][nwidth] records {f32 snr, i32 p, i32 i, i32 j}, each one 16-byte store, out_dev 16-byte
+ *            aligned, written only by the call that completes a segment (*completed = 1); nothing past
+ *            npair*ndm*noct*nwidth*16 bytes is written.  The record is the largest S over (p, i, j); among equals the
+ *            smallest p, then i, then j.  A NaN is never a maximum.  An invalid (series, octave) reads {+0.0f, -1, -1, -1} at
+ *            every width and disturbs no neighbour.
+ *   state    between two guard bands of 64 KiB: the time buffer, the carried partial sums, x_o of every octave (fewer than
+ *            2*NT words a series), the statistics {c, m, v, g}, the score table and one record per (series, octave, base period,
+ *            width).  xengFfaReset moves only the host's counts: the partial segment and the partial sample are dropped by
+ *            index, and nothing is cleared.
+ * The records are a fixed function of the segment and of {c, m, g}: bit-identical however a run is split over calls, whatever
+ * nwin_call (one that cuts a downsample group included), after a Reset as in a fresh context, and whatever else runs on the GPU.
+ * Rejected at Initialize, before any device is touched: every size outside the ranges above, nprod outside {1, 4},
+ * npair*ndm > 2^24, a state above XENG_FFA_MAX_STATE_BYTES.  Rejected by Run without a launch: a NULL input or result, a
+ * misaligned pointer, nwin_call outside 1..nwin, a NULL output on the call that completes a segment.  Every call without a
+ * context, and GetStats before a segment has completed: XENG_STATUS_INVALID_STATE.
+ * Not built: general M (the head / tail FFA; up to half a segment is unread where N_o/p is just under a power of two), red-noise
+ * detrending, more than one peak per (series, octave, width), segments above 2^14 samples. */
+#define XENG_FFA_MAX_STATE_BYTES (1LL << 32)
+#define XENG_FFA_MAX_NDS 65536
+int xengFfaInitialize(int gpu, int npair, int ndm, int nwin, int nprod, int nds, int nt, int noct, int pmin, int pmax, int nwidth);
+/* enqueue only.  out_dev is written only by a call that completes a segment (*completed = 1); the host's window count decides
+ * that before anything is enqueued.  Such a call with out_dev NULL is INVALID_ARGUMENT and enqueues nothing; on every other call
+ * out_dev may be NULL and is not touched. */
+int xengFfaRun(const void *in_dev, int nwin_call, void *out_dev, int *completed);
+/* host state only, nothing is launched and nothing cleared: the next input counts as window 0 of a new segment */
+int xengFfaReset(void);
+/* windows taken and segments completed since the last reset */
+int xengFfaGetInfo(long long *nwindows_since_reset, long long *nsegments_complete);
+/* waits for the context's work in flight; {c, m, v, g} of the last completed segment into host f32[npair][ndm][noct][4]: what
+ * the exact test of the records reads */
+int xengFfaGetStats(float *stats_host);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengFfaCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengFfaMark(unsigned long long *ticket);
+int xengFfaWait(unsigned long long ticket);
+int xengFfaTicketDone(unsigned long long ticket, int *done);
+int xengFfaSync(void);
+int xengFfaDestroy(void);
+
 /* ---------------------------------------------------------------- Coherent dedispersion of the voltage beams
  * BeamCoherentDedisperse (no reference counterpart): every (coarse channel, selected beam) row of the voltage beams is filtered by
  * overlap-save with a table given in the frequency domain, and comes out in the format it came in.  The library knows nothing of
