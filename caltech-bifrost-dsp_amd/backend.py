@@ -7,6 +7,8 @@ state machines without a GPU -- that is test infrastructure, never a fallback.
 """
 import ctypes
 
+import numpy as np
+
 from . import ffi
 
 
@@ -21,6 +23,14 @@ def _host_floats(a):
     if a is None:
         return None
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+def _host_array(who, what, a, dtype):
+    """What the setters of host tables ask of an argument before they hand its address to the library: a C-contiguous numpy
+    array of `dtype`.  `who` is the calling method, `what` names the argument in the TypeError."""
+    if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.flags['C_CONTIGUOUS']):
+        raise TypeError("%s: %s must be a C-contiguous %s array" % (who, what, np.dtype(dtype).name))
+    return a
 
 
 class HipBackend:
@@ -244,15 +254,6 @@ class HipBackend:
         """One gulp out of two consecutive spans of the input ring (samples [0, ntime0) in part0), one launch, no gathered copy."""
         return self._enq.xengUpchanRunParts(part0.ptr, int(ntime0), part1.ptr, out_arr.ptr, weights.ptr, int(version))
 
-    def upchan_mark(self):
-        return self._mark("xengUpchanMark")
-
-    def upchan_wait(self, ticket):
-        self._wait("xengUpchanTicketDone", "xengUpchanWait", ticket)
-
-    def upchan_sync(self):
-        ffi.call("xengUpchanSync")
-
     def upchan_set_pfb(self, ntap, coeffs):
         """The PFB front end (include/xeng.h xengUpchanSetPfb): coeffs float32 [ntap * nupchan] on the host, or None with ntap 1
         (the plain FFT).  Waits for the context's work in flight; the history starts empty."""
@@ -294,15 +295,6 @@ class HipBackend:
     def upchan_corr_prime_parts(self, part0, ntime0, part1):
         return self._enq.xengUpchanCorrPrimeParts(part0.ptr, int(ntime0), part1.ptr)
 
-    def upchan_corr_mark(self):
-        return self._mark("xengUpchanCorrMark")
-
-    def upchan_corr_wait(self, ticket):
-        self._wait("xengUpchanCorrTicketDone", "xengUpchanCorrWait", ticket)
-
-    def upchan_corr_sync(self):
-        ffi.call("xengUpchanCorrSync")
-
     # ---- fine-channel power beams from live beams (UpchanSumBeams; include/xeng.h "Fine-channel power beams from live beams"):
     # a context of its own, its kernels on the beamformer's stream
     def upchan_sum_beams_initialize(self, gpu, nchan, nbeam, ntime, nupchan, pair0, npair, nframe_sum):
@@ -330,15 +322,6 @@ class HipBackend:
     def upchan_sum_beams_reset(self):
         """Drops the window in progress and the PFB history (host state only)."""
         ffi.check("xengUpchanSumBeamsReset", self._enq.xengUpchanSumBeamsReset())
-
-    def upchan_sum_beams_mark(self):
-        return self._mark("xengUpchanSumBeamsMark")
-
-    def upchan_sum_beams_wait(self, ticket):
-        self._wait("xengUpchanSumBeamsTicketDone", "xengUpchanSumBeamsWait", ticket)
-
-    def upchan_sum_beams_sync(self):
-        ffi.call("xengUpchanSumBeamsSync")
 
     # ---- per-input fine-channel spectra (UpchanSpectra; include/xeng.h "Per-input fine-channel spectra"): a context of its own,
     # its kernel on the beamformer's stream
@@ -375,15 +358,6 @@ class HipBackend:
         """Drops the window in progress and the PFB history (host state only)."""
         ffi.check("xengUpchanSpectraReset", self._enq.xengUpchanSpectraReset())
 
-    def upchan_spectra_mark(self):
-        return self._mark("xengUpchanSpectraMark")
-
-    def upchan_spectra_wait(self, ticket):
-        self._wait("xengUpchanSpectraTicketDone", "xengUpchanSpectraWait", ticket)
-
-    def upchan_spectra_sync(self):
-        ffi.call("xengUpchanSpectraSync")
-
     # ---- incoherent dedispersion of fine-channel power beams (BeamDedisperse; include/xeng.h "Incoherent dedispersion of
     # fine-channel power beams"): a context of its own, its kernels on the beamformer's stream
     def dedisp_initialize(self, gpu, npair, nfine, nwin, ndm, max_delay, nprod):
@@ -411,21 +385,6 @@ class HipBackend:
         ffi.call("xengDedispGetInfo", ctypes.byref(s), ctypes.byref(n))
         return s.value, n.value
 
-    def dedisp_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the history hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengDedispCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def dedisp_mark(self):
-        return self._mark("xengDedispMark")
-
-    def dedisp_wait(self, ticket):
-        self._wait("xengDedispTicketDone", "xengDedispWait", ticket)
-
-    def dedisp_sync(self):
-        ffi.call("xengDedispSync")
-
     # ---- boxcar single-pulse search of the dedispersed beams (BeamPulseSearch; include/xeng.h "Boxcar single-pulse search of the
     # dedispersed beams"): a context of its own, its kernel on the beamformer's stream
     def pulse_initialize(self, gpu, npair, ndm, nwin, nprod, nwidth, nstat):
@@ -448,31 +407,9 @@ class HipBackend:
 
     def pulse_baseline(self, npair, ndm):
         """Waits for the context's work; (c, m, var) of the last complete block, float32 [npair][ndm] each."""
-        import numpy as np
         out = [np.empty((npair, ndm), np.float32) for _ in range(3)]
         ffi.call("xengPulseGetBaseline", *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for a in out])
         return tuple(out)
-
-    def pulse_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengPulseCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def pulse_mark(self):
-        return self._mark("xengPulseMark")
-
-    def pulse_wait(self, ticket):
-        self._wait("xengPulseTicketDone", "xengPulseWait", ticket)
-
-    def pulse_ticket_done(self, ticket):
-        """Never blocks: whether everything enqueued before the ticket has completed."""
-        d = ctypes.c_int()
-        ffi.check("xengPulseTicketDone", self._enq.xengPulseTicketDone(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
-        return bool(d.value)
-
-    def pulse_sync(self):
-        ffi.call("xengPulseSync")
 
     # ---- phase-folded profiles of the fine-channel power beams (BeamFold; include/xeng.h "Phase-folded profiles of the
     # fine-channel power beams"): a context of its own, its kernels on the beamformer's stream
@@ -514,21 +451,6 @@ class HipBackend:
         ffi.call("xengFoldGetInfo", ctypes.byref(n), ctypes.byref(f))
         return n.value, f.value
 
-    def fold_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the profile hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengFoldCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def fold_mark(self):
-        return self._mark("xengFoldMark")
-
-    def fold_wait(self, ticket):
-        self._wait("xengFoldTicketDone", "xengFoldWait", ticket)
-
-    def fold_sync(self):
-        ffi.call("xengFoldSync")
-
     # ---- FFT periodicity search of the dedispersed beams (BeamPeriodSearch; include/xeng.h "FFT periodicity search of the
     # dedispersed beams"): a context of its own, its kernels on the beamformer's stream
     def period_initialize(self, gpu, npair, ndm, nwin, nprod, nt, nstack, nlevel, nwhite, kmin):
@@ -560,31 +482,9 @@ class HipBackend:
 
     def period_spectrum(self, npair, ndm, nt):
         """Waits for the context's work; (A, nseg): the stack as it stands, float32 [npair][ndm][nt/2], and the segments in it."""
-        import numpy as np
         A, nseg = np.empty((npair, ndm, nt // 2), np.float32), ctypes.c_int()
         ffi.call("xengPeriodGetSpectrum", A.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(nseg))
         return A, nseg.value
-
-    def period_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengPeriodCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def period_mark(self):
-        return self._mark("xengPeriodMark")
-
-    def period_wait(self, ticket):
-        self._wait("xengPeriodTicketDone", "xengPeriodWait", ticket)
-
-    def period_ticket_done(self, ticket):
-        """Never blocks: whether everything enqueued before the ticket has completed."""
-        d = ctypes.c_int()
-        ffi.check("xengPeriodTicketDone", self._enq.xengPeriodTicketDone(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
-        return bool(d.value)
-
-    def period_sync(self):
-        ffi.call("xengPeriodSync")
 
     # ---- fast-folding search of the dedispersed beams (BeamFfaSearch; include/xeng.h "Fast-folding search of the dedispersed
     # beams"): a context of its own, its kernels on the beamformer's stream
@@ -612,31 +512,9 @@ class HipBackend:
 
     def ffa_stats(self, npair, ndm, noct):
         """Waits for the context's work; {c, m, v, g} of the last completed segment, float32 [npair][ndm][noct][4]."""
-        import numpy as np
         st = np.empty((npair, ndm, noct, 4), np.float32)
         ffi.call("xengFfaGetStats", st.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
         return st
-
-    def ffa_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengFfaCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def ffa_mark(self):
-        return self._mark("xengFfaMark")
-
-    def ffa_wait(self, ticket):
-        self._wait("xengFfaTicketDone", "xengFfaWait", ticket)
-
-    def ffa_ticket_done(self, ticket):
-        """Never blocks: whether everything enqueued before the ticket has completed."""
-        d = ctypes.c_int()
-        ffi.check("xengFfaTicketDone", self._enq.xengFfaTicketDone(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
-        return bool(d.value)
-
-    def ffa_sync(self):
-        ffi.call("xengFfaSync")
 
     # ---- coherent dedispersion of the voltage beams (BeamCoherentDedisperse; include/xeng.h "Coherent dedispersion of the voltage
     # beams"): a context of its own, its kernels on the beamformer's stream
@@ -646,9 +524,7 @@ class HipBackend:
     def cdedisp_set_chirp(self, table):
         """table: host complex64 [npair][nchan][nfft], C-contiguous, natural DFT order, 1/nfft included.  Waits for the context's
         work in flight; holds from the next block to complete."""
-        import numpy as np
-        if not (isinstance(table, np.ndarray) and table.dtype == np.complex64 and table.flags['C_CONTIGUOUS']):
-            raise TypeError("cdedisp_set_chirp: the table must be a C-contiguous complex64 array")
+        _host_array("cdedisp_set_chirp", "the table", table, np.complex64)
         return self._lib.xengCdedispSetChirp(table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
 
     def cdedisp_run(self, in_arr, out_arr):
@@ -668,21 +544,6 @@ class HipBackend:
         ffi.call("xengCdedispGetInfo", ctypes.byref(s), ctypes.byref(m), ctypes.byref(n), ctypes.byref(b))
         return s.value, m.value, n.value, b.value
 
-    def cdedisp_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengCdedispCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def cdedisp_mark(self):
-        return self._mark("xengCdedispMark")
-
-    def cdedisp_wait(self, ticket):
-        self._wait("xengCdedispTicketDone", "xengCdedispWait", ticket)
-
-    def cdedisp_sync(self):
-        ffi.call("xengCdedispSync")
-
     # ---- coherent dedispersion with long transforms (BeamCoherentDedisperseLong; include/xeng.h "Coherent dedispersion with long
     # transforms"): xengCdedisp*'s contract for 2^14 to 2^20 points, a context of its own, its kernels on the beamformer's stream
     def cdlong_initialize(self, gpu, nchan, nbeam, ntime, pair0, npair, nfft, overlap):
@@ -691,9 +552,7 @@ class HipBackend:
     def cdlong_set_chirp(self, pair, table):
         """table: host complex64 [nchan][nfft] of pair `pair`, C-contiguous, natural DFT order, 1/nfft included.  Waits for the
         context's work in flight; holds from the next block to complete."""
-        import numpy as np
-        if not (isinstance(table, np.ndarray) and table.dtype == np.complex64 and table.flags['C_CONTIGUOUS']):
-            raise TypeError("cdlong_set_chirp: the table must be a C-contiguous complex64 array")
+        _host_array("cdlong_set_chirp", "the table", table, np.complex64)
         return self._lib.xengCdlongSetChirp(int(pair), table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
 
     def cdlong_run(self, in_arr, out_arr):
@@ -713,21 +572,6 @@ class HipBackend:
         ffi.call("xengCdlongGetInfo", ctypes.byref(s), ctypes.byref(m), ctypes.byref(n), ctypes.byref(b))
         return s.value, m.value, n.value, b.value
 
-    def cdlong_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengCdlongCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def cdlong_mark(self):
-        return self._mark("xengCdlongMark")
-
-    def cdlong_wait(self, ticket):
-        self._wait("xengCdlongTicketDone", "xengCdlongWait", ticket)
-
-    def cdlong_sync(self):
-        ffi.call("xengCdlongSync")
-
     # ---- dirty images of the fine-channel visibilities (UpchanImage; include/xeng.h "Dirty images of the fine-channel
     # visibilities"): a context of its own, its kernel on the beamformer's stream
     def image_initialize(self, gpu, nstand, nfine, nfavg, npix):
@@ -736,18 +580,14 @@ class HipBackend:
     def image_set_geometry(self, tau, freq):
         """tau: host float64 [npix][nstand] seconds, freq: host float64 [nfine] Hz, both C-contiguous.  Waits for the context's work
         in flight."""
-        import numpy as np
-        for a in (tau, freq):
-            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags['C_CONTIGUOUS']):
-                raise TypeError("image_set_geometry: the tables must be C-contiguous float64 arrays")
+        _host_array("image_set_geometry", "tau", tau, np.float64)
+        _host_array("image_set_geometry", "freq", freq, np.float64)
         pd = ctypes.POINTER(ctypes.c_double)
         return self._lib.xengImageSetGeometry(tau.ctypes.data_as(pd), freq.ctypes.data_as(pd))
 
     def image_set_weights(self, weights, autos):
         """weights: host float32 [nstand], finite and >= 0.  Waits for the context's work in flight; holds from the next run."""
-        import numpy as np
-        if not (isinstance(weights, np.ndarray) and weights.dtype == np.float32 and weights.flags['C_CONTIGUOUS']):
-            raise TypeError("image_set_weights: the weights must be a C-contiguous float32 array")
+        _host_array("image_set_weights", "the weights", weights, np.float32)
         return self._lib.xengImageSetWeights(_host_floats(weights), int(bool(autos)))
 
     def image_run(self, vis_arr, out_arr):
@@ -760,21 +600,6 @@ class HipBackend:
         ffi.call("xengImageGetInfo", ctypes.byref(g), ctypes.byref(t), ctypes.byref(l), ctypes.byref(n))
         return g.value, t.value, l.value, n.value
 
-    def image_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengImageCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def image_mark(self):
-        return self._mark("xengImageMark")
-
-    def image_wait(self, ticket):
-        self._wait("xengImageTicketDone", "xengImageWait", ticket)
-
-    def image_sync(self):
-        ffi.call("xengImageSync")
-
     # ---- per-stand gains from the fine-channel visibilities (UpchanGainCal; include/xeng.h "Per-stand gains from the fine-channel
     # visibilities"): a context of its own, its kernel on the beamformer's stream
     def gaincal_initialize(self, gpu, nstand, nfine, nsrc):
@@ -783,19 +608,15 @@ class HipBackend:
     def gaincal_set_model(self, tau, freq, flux):
         """tau: host float64 [nsrc][nstand] seconds, freq: host float64 [nfine] Hz, flux: host float32 [nfine][nsrc], all
         C-contiguous.  Waits for the context's work in flight; forgets the warm start."""
-        import numpy as np
-        for a, t in ((tau, np.float64), (freq, np.float64), (flux, np.float32)):
-            if not (isinstance(a, np.ndarray) and a.dtype == t and a.flags['C_CONTIGUOUS']):
-                raise TypeError("gaincal_set_model: the tables must be C-contiguous float64, float64 and float32 arrays")
+        for what, a, t in (("tau", tau, np.float64), ("freq", freq, np.float64), ("flux", flux, np.float32)):
+            _host_array("gaincal_set_model", what, a, t)
         pd = ctypes.POINTER(ctypes.c_double)
         return self._lib.xengGaincalSetModel(tau.ctypes.data_as(pd), freq.ctypes.data_as(pd), _host_floats(flux))
 
     def gaincal_set_weights(self, weights, refant):
         """weights: host float32 [nstand], finite and >= 0, that of `refant` > 0.  Waits for the context's work in flight; holds from
         the next run; forgets the warm start."""
-        import numpy as np
-        if not (isinstance(weights, np.ndarray) and weights.dtype == np.float32 and weights.flags['C_CONTIGUOUS']):
-            raise TypeError("gaincal_set_weights: the weights must be a C-contiguous float32 array")
+        _host_array("gaincal_set_weights", "the weights", weights, np.float32)
         return self._lib.xengGaincalSetWeights(_host_floats(weights), int(refant))
 
     def gaincal_set_solver(self, niter, tol):
@@ -812,21 +633,6 @@ class HipBackend:
         ffi.call("xengGaincalGetInfo", ctypes.byref(l), ctypes.byref(n), ctypes.byref(t), ctypes.byref(r))
         return l.value, n.value, t.value, r.value
 
-    def gaincal_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengGaincalCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def gaincal_mark(self):
-        return self._mark("xengGaincalMark")
-
-    def gaincal_wait(self, ticket):
-        self._wait("xengGaincalTicketDone", "xengGaincalWait", ticket)
-
-    def gaincal_sync(self):
-        ffi.call("xengGaincalSync")
-
     # ---- calibrated, source-subtracted visibilities (UpchanCalApply; include/xeng.h "Calibrated, source-subtracted visibilities"): a
     # context of its own, its kernels on the beamformer's stream
     def calapply_initialize(self, gpu, nstand, nfine, nsrc):
@@ -835,12 +641,9 @@ class HipBackend:
     def calapply_set_model(self, tau, freq, flux):
         """tau: host float64 [nsrc][nstand] seconds, freq: host float64 [nfine] Hz, flux: host float32 [nfine][nsrc], all
         C-contiguous; tau and flux may be None in a context without sources.  Waits for the context's work in flight."""
-        import numpy as np
-        for a, t, optional in ((tau, np.float64, True), (freq, np.float64, False), (flux, np.float32, True)):
-            if a is None and optional:
-                continue
-            if not (isinstance(a, np.ndarray) and a.dtype == t and a.flags['C_CONTIGUOUS']):
-                raise TypeError("calapply_set_model: the tables must be C-contiguous float64, float64 and float32 arrays")
+        for what, a, t, optional in (("tau", tau, np.float64, True), ("freq", freq, np.float64, False), ("flux", flux, np.float32, True)):
+            if not (a is None and optional):
+                _host_array("calapply_set_model", what, a, t)
         pd = ctypes.POINTER(ctypes.c_double)
         return self._lib.xengCalapplySetModel(None if tau is None or not tau.size else tau.ctypes.data_as(pd), freq.ctypes.data_as(pd),
                                               None if flux is None or not flux.size else _host_floats(flux))
@@ -848,9 +651,7 @@ class HipBackend:
     def calapply_set_factors(self, h):
         """h: host complex64 [nfine][2][nstand], finite, 0 where a (stand, polarisation) is left out.  Waits for the context's work
         in flight; holds from the next run."""
-        import numpy as np
-        if not (isinstance(h, np.ndarray) and h.dtype == np.complex64 and h.flags['C_CONTIGUOUS']):
-            raise TypeError("calapply_set_factors: the factors must be a C-contiguous complex64 array")
+        _host_array("calapply_set_factors", "the factors", h, np.complex64)
         return self._lib.xengCalapplySetFactors(h.ctypes.data_as(ctypes.c_void_p))
 
     def calapply_run(self, vis_arr, out_arr):
@@ -863,21 +664,6 @@ class HipBackend:
         ffi.call("xengCalapplyGetInfo", ctypes.byref(t), ctypes.byref(g), ctypes.byref(l), ctypes.byref(b))
         return t.value, g.value, l.value, b.value
 
-    def calapply_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengCalapplyCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def calapply_mark(self):
-        return self._mark("xengCalapplyMark")
-
-    def calapply_wait(self, ticket):
-        self._wait("xengCalapplyTicketDone", "xengCalapplyWait", ticket)
-
-    def calapply_sync(self):
-        ffi.call("xengCalapplySync")
-
     # ---- direction-dependent gains and peeling (UpchanPeel; include/xeng.h "Direction-dependent gains and peeling"): a context of
     # its own, its kernels on the beamformer's stream
     def peel_initialize(self, gpu, nstand, nfine, ndir):
@@ -886,19 +672,15 @@ class HipBackend:
     def peel_set_model(self, tau, freq, flux):
         """tau: host float64 [ndir][nstand] seconds, freq: host float64 [nfine] Hz, flux: host float32 [nfine][ndir], all
         C-contiguous.  Waits for the context's work in flight; forgets the warm start."""
-        import numpy as np
-        for a, t in ((tau, np.float64), (freq, np.float64), (flux, np.float32)):
-            if not (isinstance(a, np.ndarray) and a.dtype == t and a.flags['C_CONTIGUOUS']):
-                raise TypeError("peel_set_model: the tables must be C-contiguous float64, float64 and float32 arrays")
+        for what, a, t in (("tau", tau, np.float64), ("freq", freq, np.float64), ("flux", flux, np.float32)):
+            _host_array("peel_set_model", what, a, t)
         pd = ctypes.POINTER(ctypes.c_double)
         return self._lib.xengPeelSetModel(tau.ctypes.data_as(pd), freq.ctypes.data_as(pd), _host_floats(flux))
 
     def peel_set_weights(self, weights, refant):
         """weights: host float32 [nstand], finite and >= 0, that of `refant` > 0.  Waits for the context's work in flight; holds from
         the next run; forgets the warm start."""
-        import numpy as np
-        if not (isinstance(weights, np.ndarray) and weights.dtype == np.float32 and weights.flags['C_CONTIGUOUS']):
-            raise TypeError("peel_set_weights: the weights must be a C-contiguous float32 array")
+        _host_array("peel_set_weights", "the weights", weights, np.float32)
         return self._lib.xengPeelSetWeights(_host_floats(weights), int(refant))
 
     def peel_set_solver(self, niter, tol):
@@ -915,21 +697,6 @@ class HipBackend:
         ffi.call("xengPeelGetInfo", ctypes.byref(l), ctypes.byref(n), ctypes.byref(t), ctypes.byref(r), ctypes.byref(b))
         return l.value, n.value, t.value, r.value, b.value
 
-    def peel_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengPeelCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def peel_mark(self):
-        return self._mark("xengPeelMark")
-
-    def peel_wait(self, ticket):
-        self._wait("xengPeelTicketDone", "xengPeelWait", ticket)
-
-    def peel_sync(self):
-        ffi.call("xengPeelSync")
-
     # ---- Hogbom CLEAN of the dirty images (UpchanClean; include/xeng.h "Hogbom CLEAN of the dirty images"): a context of its own,
     # its kernel on the beamformer's stream
     def clean_initialize(self, gpu, nstand, nfine, nfavg, npix, niter_max):
@@ -938,28 +705,22 @@ class HipBackend:
     def clean_set_geometry(self, tau, freq):
         """tau: host float64 [npix][nstand] seconds, freq: host float64 [nfine] Hz, both C-contiguous.  Waits for the context's work
         in flight."""
-        import numpy as np
-        for a in (tau, freq):
-            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags['C_CONTIGUOUS']):
-                raise TypeError("clean_set_geometry: the tables must be C-contiguous float64 arrays")
+        _host_array("clean_set_geometry", "tau", tau, np.float64)
+        _host_array("clean_set_geometry", "freq", freq, np.float64)
         pd = ctypes.POINTER(ctypes.c_double)
         return self._lib.xengCleanSetGeometry(tau.ctypes.data_as(pd), freq.ctypes.data_as(pd))
 
     def clean_set_weights(self, weights, autos):
         """weights: host float32 [nstand], finite and >= 0.  Waits for the context's work in flight; holds from the next run."""
-        import numpy as np
-        if not (isinstance(weights, np.ndarray) and weights.dtype == np.float32 and weights.flags['C_CONTIGUOUS']):
-            raise TypeError("clean_set_weights: the weights must be a C-contiguous float32 array")
+        _host_array("clean_set_weights", "the weights", weights, np.float32)
         return self._lib.xengCleanSetWeights(_host_floats(weights), int(bool(autos)))
 
     def clean_set_window(self, mask):
         """mask: host uint8 [npix] (non-zero: a component may sit there), or None for every pixel.  Waits for the context's work in
         flight; holds from the next run."""
-        import numpy as np
         if mask is None:
             return self._lib.xengCleanSetWindow(None)
-        if not (isinstance(mask, np.ndarray) and mask.dtype == np.uint8 and mask.flags['C_CONTIGUOUS']):
-            raise TypeError("clean_set_window: the window must be a C-contiguous uint8 array")
+        _host_array("clean_set_window", "the window", mask, np.uint8)
         return self._lib.xengCleanSetWindow(mask.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
 
     def clean_set_control(self, niter, gain, threshold, fraction):
@@ -977,21 +738,6 @@ class HipBackend:
         ffi.call("xengCleanGetInfo", ctypes.byref(g), ctypes.byref(t), ctypes.byref(c), ctypes.byref(s), ctypes.byref(b), ctypes.byref(n))
         return g.value, t.value, c.value, s.value, b.value, n.value
 
-    def clean_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengCleanCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def clean_mark(self):
-        return self._mark("xengCleanMark")
-
-    def clean_wait(self, ticket):
-        self._wait("xengCleanTicketDone", "xengCleanWait", ticket)
-
-    def clean_sync(self):
-        ffi.call("xengCleanSync")
-
     # ---- outlier flags from the fine-channel visibilities (UpchanFlag; include/xeng.h "Outlier flags from the fine-channel
     # visibilities"): a context of its own, its kernels on the beamformer's stream
     def flag_initialize(self, gpu, nstand, nfine):
@@ -1000,9 +746,7 @@ class HipBackend:
     def flag_set_weights(self, weights):
         """weights: host float32 [nstand], finite and >= 0, at least 4 of them > 0.  Waits for the context's work in flight; holds
         from the next run."""
-        import numpy as np
-        if not (isinstance(weights, np.ndarray) and weights.dtype == np.float32 and weights.flags['C_CONTIGUOUS']):
-            raise TypeError("flag_set_weights: the weights must be a C-contiguous float32 array")
+        _host_array("flag_set_weights", "the weights", weights, np.float32)
         return self._lib.xengFlagSetWeights(_host_floats(weights))
 
     def flag_set_control(self, nsig_cross, nsig_auto, nsig_chan, wchan):
@@ -1026,21 +770,6 @@ class HipBackend:
         ffi.call("xengFlagGetControl", ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(w))
         return a.value, b.value, c.value, w.value
 
-    def flag_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengFlagCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def flag_mark(self):
-        return self._mark("xengFlagMark")
-
-    def flag_wait(self, ticket):
-        self._wait("xengFlagTicketDone", "xengFlagWait", ticket)
-
-    def flag_sync(self):
-        ffi.call("xengFlagSync")
-
     # ---- component lists subtracted from the visibilities (UpchanPredict; include/xeng.h "Component lists subtracted from the
     # visibilities"): a context of its own, its kernels on the beamformer's stream
     PREDICT_SUBTRACT, PREDICT_MODEL = 0, 1
@@ -1051,17 +780,14 @@ class HipBackend:
     def predict_set_geometry(self, tau, freq):
         """tau: host float64 [ndir][nstand] seconds, freq: host float64 [nfine] Hz, both C-contiguous.  Waits for the context's work
         in flight."""
-        import numpy as np
-        for a in (tau, freq):
-            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags['C_CONTIGUOUS']):
-                raise TypeError("predict_set_geometry: the tables must be C-contiguous float64 arrays")
+        _host_array("predict_set_geometry", "tau", tau, np.float64)
+        _host_array("predict_set_geometry", "freq", freq, np.float64)
         pd = ctypes.POINTER(ctypes.c_double)
         return self._lib.xengPredictSetGeometry(tau.ctypes.data_as(pd), freq.ctypes.data_as(pd))
 
     def predict_set_components(self, records):
         """records: host array of 32-byte records (blocks/imaging.py CLEAN_COMPONENT) [nfine / nfavg][ncomp_max], C-contiguous.
         Waits for the context's work in flight; holds from the next run."""
-        import numpy as np
         if not (isinstance(records, np.ndarray) and records.dtype.itemsize == 32 and records.flags['C_CONTIGUOUS']):
             raise TypeError("predict_set_components: the records must be a C-contiguous array of 32-byte records")
         return self._lib.xengPredictSetComponents(records.ctypes.data_as(ctypes.c_void_p))
@@ -1082,21 +808,6 @@ class HipBackend:
         ffi.call("xengPredictGetInfo", ctypes.byref(t), ctypes.byref(g), ctypes.byref(l), ctypes.byref(b), ctypes.byref(s), ctypes.byref(n), ctypes.byref(m))
         return t.value, g.value, l.value, b.value, s.value, n.value, m.value
 
-    def predict_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengPredictCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def predict_mark(self):
-        return self._mark("xengPredictMark")
-
-    def predict_wait(self, ticket):
-        self._wait("xengPredictTicketDone", "xengPredictWait", ticket)
-
-    def predict_sync(self):
-        ffi.call("xengPredictSync")
-
     # ---- dedispersed transient search of the images (UpchanImageSearch; include/xeng.h "Dedispersed transient search of the
     # images"): a context of its own, its kernels on the beamformer's stream
     def imsearch_initialize(self, gpu, npix, ngroup, ndm, max_delay, nwidth, nstat):
@@ -1104,17 +815,13 @@ class HipBackend:
 
     def imsearch_set_delays(self, delays):
         """delays: host int32 [ndm][ngroup], C-contiguous, in integrations.  Waits for the context's work in flight; resets."""
-        import numpy as np
-        if not (isinstance(delays, np.ndarray) and delays.dtype == np.int32 and delays.flags['C_CONTIGUOUS']):
-            raise TypeError("imsearch_set_delays: the table must be a C-contiguous int32 array")
+        _host_array("imsearch_set_delays", "the table", delays, np.int32)
         return self._lib.xengImsearchSetDelays(delays.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
 
     def imsearch_set_weights(self, weights):
         """weights: host float32 [ngroup], finite and >= 0, one above 0.  Waits for the context's work in flight; resets nothing,
         but no boxcar reaches back before this call."""
-        import numpy as np
-        if not (isinstance(weights, np.ndarray) and weights.dtype == np.float32 and weights.flags['C_CONTIGUOUS']):
-            raise TypeError("imsearch_set_weights: the weights must be a C-contiguous float32 array")
+        _host_array("imsearch_set_weights", "the weights", weights, np.float32)
         return self._lib.xengImsearchSetWeights(_host_floats(weights))
 
     def imsearch_run(self, image_arr, out_arr):
@@ -1133,48 +840,71 @@ class HipBackend:
 
     def imsearch_baseline(self, ngroup, npix):
         """Waits for the context's work; (c, m, var) of the last complete block, float32 [ngroup][npix] each."""
-        import numpy as np
         out = [np.empty((ngroup, npix), np.float32) for _ in range(3)]
         ffi.call("xengImsearchGetBaseline", *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for a in out])
         return tuple(out)
 
-    def imsearch_guards_intact(self):
-        """Waits for the context's work; True while the guard bands around the state hold their pattern."""
-        ok = ctypes.c_int()
-        ffi.call("xengImsearchCheckGuards", ctypes.byref(ok))
-        return bool(ok.value)
-
-    def imsearch_mark(self):
-        return self._mark("xengImsearchMark")
-
-    def imsearch_wait(self, ticket):
-        self._wait("xengImsearchTicketDone", "xengImsearchWait", ticket)
-
-    def imsearch_ticket_done(self, ticket):
-        """Never blocks: whether everything enqueued before the ticket has completed."""
-        d = ctypes.c_int()
-        ffi.check("xengImsearchTicketDone", self._enq.xengImsearchTicketDone(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
-        return bool(d.value)
-
-    def imsearch_sync(self):
-        ffi.call("xengImsearchSync")
-
-    # ---- completion tickets of the contexts without a native binding (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp, Pulse, Fold, Period,
-    # Cdedisp, Cdlong, Image, Gaincal, Calapply, Peel, Clean, Flag, Predict, Imsearch)
+    # ---- completion tickets and guard bands of the engines of ffi.ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
+    # _guards_intact are made from these below the class
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
         ffi.check(mark, getattr(self._enq, mark)(ctypes.byref(t)))
         return t.value
 
-    def _wait(self, ticket_done, wait, ticket):
-        # ask first, without giving up the interpreter lock; only a ticket the GPU has not reached yet is worth a blocking call
+    def _ticket_done(self, ticket_done, ticket):
         d = ctypes.c_int()
         ffi.check(ticket_done, getattr(self._enq, ticket_done)(ctypes.c_ulonglong(ticket), ctypes.byref(d)))
-        if not d.value:
+        return bool(d.value)
+
+    def _wait(self, ticket_done, wait, ticket):
+        # ask first, without giving up the interpreter lock; only a ticket the GPU has not reached yet is worth a blocking call
+        if not self._ticket_done(ticket_done, ticket):
             ffi.call(wait, ctypes.c_ulonglong(ticket))
+
+    def _guards_intact(self, check_guards):
+        ok = ctypes.c_int()
+        ffi.call(check_guards, ctypes.byref(ok))
+        return bool(ok.value)
 
     def last_error(self):
         return self._lib.xengGetLastError().decode()
+
+
+def _engine_methods(cname, prefix, guards):
+    """The HipBackend methods every row of ffi.ENGINES gets, by name."""
+    x = "xeng" + cname
+
+    def mark(self):
+        return self._mark(x + "Mark")
+    mark.__doc__ = "Ticket for everything enqueued in the %s context so far (%s_wait waits for it)." % (cname, prefix)
+
+    def wait(self, ticket):
+        self._wait(x + "TicketDone", x + "Wait", ticket)
+    wait.__doc__ = "Returns when everything enqueued before %s_mark gave `ticket` has completed." % prefix
+
+    def ticket_done(self, ticket):
+        return self._ticket_done(x + "TicketDone", ticket)
+    ticket_done.__doc__ = "Never blocks: whether everything enqueued before the ticket has completed."
+
+    def sync(self):
+        ffi.call(x + "Sync")
+    sync.__doc__ = "Waits for everything enqueued in the %s context." % cname
+
+    def guards_intact(self):
+        return self._guards_intact(x + "CheckGuards")
+    guards_intact.__doc__ = "Waits for the context's work; True while the guard bands around the %s state hold their pattern." % cname
+
+    fs = {"mark": mark, "wait": wait, "ticket_done": ticket_done, "sync": sync}
+    if guards:
+        fs["guards_intact"] = guards_intact
+    return {"%s_%s" % (prefix, k): f for k, f in fs.items()}
+
+
+for _row in ffi.ENGINES:
+    for _name, _f in _engine_methods(*_row).items():
+        _f.__name__ = _name
+        _f.__qualname__ = "HipBackend." + _name
+        setattr(HipBackend, _name, _f)
 
 
 _default = None

@@ -1,6 +1,5 @@
-// Host side of the calibration stage (UpchanCalApply; calapply_kernels.h): a process-global context of its own, beside the Beamform,
-// Upchan*, Dedisp, Pulse, Fold, Period, Cdedisp, Image and Gaincal contexts, whose kernels run on the beamformer's stream (STREAM_BEAM)
-// and tick its clock, so that rings declared 'beam' and their span stamps cover it unchanged.
+// Host side of the calibration stage (UpchanCalApply; calapply_kernels.h): a process-global context of its own on the
+// beamformer's stream (BeamStreamContext, xeng_common.h).
 #include <cmath>
 #include <mutex>
 #include <vector>
@@ -14,7 +13,7 @@ static_assert(XENG_CALAPPLY_MAX_NSRC == CA_K && XENG_CALAPPLY_MAX_NSTAND == CA_M
 
 struct CalapplyContext : BeamStreamContext {
     int nstand = 0, nfine = 0, nsrc = 0;
-    uint8_t* alloc = nullptr;           // CA_GUARD bytes of CA_GUARD_BYTE, the state, CA_GUARD bytes of CA_GUARD_BYTE
+    GuardedState alloc;                 // the state between its guard bands (xengCalapplyCheckGuards)
     double* freq = nullptr;             // f64[nfine], inside alloc
     double* tau = nullptr;              // f64[nsrc][nstand], behind it
     float2* a = nullptr;                // cf32[nfine][nsrc][nstand]: the steering factors (calapply_steer_kernel)
@@ -29,15 +28,13 @@ struct CalapplyContext : BeamStreamContext {
     }
     int ntile() const { return (nstand + CA_T - 1) / CA_T; }
 };
-constexpr size_t CA_GUARD = 64 << 10;   // guard bands around the state (xengCalapplyCheckGuards)
-constexpr int CA_GUARD_BYTE = 0xA5;
 static std::mutex g_camu;
 static CalapplyContext g_ca;
 
 static int calapply_destroy_locked() {
     if (!g_ca.live) return XENG_STATUS_SUCCESS;
     beam_context_close(g_ca);
-    if (g_ca.alloc) (void)hipFree(g_ca.alloc);
+    g_ca.alloc.free();
     g_ca = CalapplyContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -63,9 +60,8 @@ int xengCalapplyInitialize(int gpu, int nstand, int nfine, int nsrc) {
     x.nstand = nstand; x.nfine = nfine; x.nsrc = nsrc;
     const std::vector<float2> ones((size_t)nfine * 2 * nstand, make_float2(1.f, 0.f));
     float2* h = nullptr;
-    if (hipMalloc(&x.alloc, x.state_bytes() + 2 * CA_GUARD) == hipSuccess && hip_memset_now(x.alloc, CA_GUARD_BYTE, x.state_bytes() + 2 * CA_GUARD) == hipSuccess &&
-        hip_memset_now(x.alloc + CA_GUARD, 0, x.state_bytes()) == hipSuccess) {
-        x.freq = (double*)(x.alloc + CA_GUARD);
+    if (x.alloc.open(x.state_bytes()) == hipSuccess) {
+        x.freq = (double*)x.alloc.data();
         x.tau = x.freq + nfine;
         x.a = (float2*)(x.tau + (size_t)nsrc * nstand);
         x.h = x.a + (size_t)nfine * nsrc * nstand;
@@ -74,7 +70,7 @@ int xengCalapplyInitialize(int gpu, int nstand, int nfine, int nsrc) {
     }
     if (!h) {
         (void)hipGetLastError();
-        if (x.alloc) (void)hipFree(x.alloc);
+        x.alloc.free();
         x = CalapplyContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Calapply: cannot allocate %.3g MB of state", (double)nfine * nstand * (nsrc + 2) * 8e-6);
     }
@@ -154,22 +150,7 @@ int xengCalapplyRun(const void* vis_dev, void* out_dev) {
     return XENG_STATUS_SUCCESS;
 }
 
-int xengCalapplyCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "CalapplyCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_camu);
-    CalapplyContext& x = g_ca;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Calapply: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * CA_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.alloc, CA_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + CA_GUARD, x.alloc + CA_GUARD + x.state_bytes(), CA_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != CA_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengCalapplyCheckGuards(int* intact) { return beam_context_check_guards(g_camu, g_ca, g_ca.alloc, "Calapply", intact); }
 int xengCalapplyMark(unsigned long long* ticket) { return beam_context_mark(g_camu, g_ca, "Calapply", ticket); }
 int xengCalapplyWait(unsigned long long ticket) { return beam_context_wait(g_camu, g_ca, "Calapply", ticket); }
 int xengCalapplyTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_camu, g_ca, "Calapply", ticket, done); }

@@ -1,6 +1,5 @@
-// Host side of the coherent dedisperser (BeamCoherentDedisperse; cdedisp_kernels.h): a process-global context of its own, beside the
-// Beamform, Upchan*, Dedisp, Pulse, Fold and Period contexts, whose kernels run on the beamformer's stream (STREAM_BEAM) and tick
-// its clock, so that rings declared 'beam' and their span stamps cover them unchanged.
+// Host side of the coherent dedisperser (BeamCoherentDedisperse; cdedisp_kernels.h): a process-global context of its own on the
+// beamformer's stream (BeamStreamContext, xeng_common.h).
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -14,7 +13,7 @@ namespace xeng {
 struct CdedispContext : BeamStreamContext {
     int nchan = 0, nbeam = 0, ntime = 0, pair0 = 0, npair = 0, nfft = 0, overlap = 0;
     int nrow = 0, step = 0, LN = 0;     // nchan * 2 npair, nfft - overlap, log2 nfft
-    uint8_t* alloc = nullptr;           // CD_GUARD bytes of CD_GUARD_BYTE, the state, CD_GUARD bytes of CD_GUARD_BYTE
+    GuardedState alloc;                 // the state between its guard bands (xengCdedispCheckGuards)
     float2* tbuf = nullptr;             // cf32[nrow][nfft], inside alloc
     float2* tab = nullptr;              // cf32[npair][nchan][nfft], bit-reversed along the last axis, behind it
     float2* tw = nullptr;               // float2[nfft / 2]
@@ -25,15 +24,13 @@ struct CdedispContext : BeamStreamContext {
     size_t table_words() const { return (size_t)npair * nchan * nfft; }
     size_t state_bytes() const { return ((size_t)nrow * nfft + table_words() + (size_t)nfft / 2) * sizeof(float2); }
 };
-constexpr size_t CD_GUARD = 64 << 10;   // guard bands around the state (xengCdedispCheckGuards)
-constexpr int CD_GUARD_BYTE = 0xA5;
 static std::mutex g_cdmu;
 static CdedispContext g_cd;
 
 static int cdedisp_destroy_locked() {
     if (!g_cd.live) return XENG_STATUS_SUCCESS;
     beam_context_close(g_cd);
-    if (g_cd.alloc) (void)hipFree(g_cd.alloc);
+    g_cd.alloc.free();
     g_cd = CdedispContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -99,20 +96,17 @@ int xengCdedispInitialize(int gpu, int nchan, int nbeam, int ntime, int pair0, i
     std::vector<float2> tw((size_t)nfft / 2);
     const double step = -2.0 * 3.14159265358979323846 / (double)nfft;
     for (int k = 0; k < nfft / 2; k++) tw[k] = make_float2((float)std::cos(step * k), (float)std::sin(step * k));
-    if (hipMalloc(&x.alloc, x.state_bytes() + 2 * CD_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc, CD_GUARD_BYTE, x.state_bytes() + 2 * CD_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc + CD_GUARD, 0, x.state_bytes()) != hipSuccess) {
+    if (x.alloc.open(x.state_bytes()) != hipSuccess) {
         (void)hipGetLastError();
-        if (x.alloc) (void)hipFree(x.alloc);
         x = CdedispContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Cdedisp: cannot allocate %.3g MB of state", (double)nchan * 3 * npair * nfft * 8e-6);
     }
-    x.tbuf = (float2*)(x.alloc + CD_GUARD);
+    x.tbuf = (float2*)x.alloc.data();
     x.tab = x.tbuf + (size_t)x.nrow * nfft;
     x.tw = x.tab + x.table_words();
     if (hipMemcpy(x.tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess || cdedisp_upload_table(x, nullptr) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(x.alloc);
+        x.alloc.free();
         x = CdedispContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Cdedisp: cannot upload the twiddles and the table");
     }
@@ -190,22 +184,7 @@ int xengCdedispGetInfo(int* step, int* max_blocks_per_call, long long* nsamples_
     return XENG_STATUS_SUCCESS;
 }
 
-int xengCdedispCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "CdedispCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_cdmu);
-    CdedispContext& x = g_cd;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Cdedisp: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * CD_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.alloc, CD_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + CD_GUARD, x.alloc + CD_GUARD + x.state_bytes(), CD_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != CD_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengCdedispCheckGuards(int* intact) { return beam_context_check_guards(g_cdmu, g_cd, g_cd.alloc, "Cdedisp", intact); }
 int xengCdedispMark(unsigned long long* ticket) { return beam_context_mark(g_cdmu, g_cd, "Cdedisp", ticket); }
 int xengCdedispWait(unsigned long long ticket) { return beam_context_wait(g_cdmu, g_cd, "Cdedisp", ticket); }
 int xengCdedispTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_cdmu, g_cd, "Cdedisp", ticket, done); }

@@ -1,6 +1,5 @@
 // Host side of the long-transform coherent dedisperser (BeamCoherentDedisperseLong; cdlong_kernels.h): a process-global context of
-// its own, beside the Cdedisp context and the others, whose kernels run on the beamformer's stream (STREAM_BEAM) and tick its clock,
-// so that rings declared 'beam' and their span stamps cover them unchanged.
+// its own on the beamformer's stream (BeamStreamContext, xeng_common.h).
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -14,7 +13,7 @@ namespace xeng {
 struct CdlongContext : BeamStreamContext {
     int nchan = 0, nbeam = 0, ntime = 0, pair0 = 0, npair = 0, nfft = 0, overlap = 0;
     int nrow = 0, step = 0, LN = 0, LN1 = 0, LN2 = 0;   // nchan * 2 npair, nfft - overlap, log2 nfft = LN1 + LN2
-    uint8_t* alloc = nullptr;           // CL_GUARD bytes of CL_GUARD_BYTE, the state, CL_GUARD bytes of CL_GUARD_BYTE
+    GuardedState alloc;                 // the state between its guard bands (xengCdlongCheckGuards)
     float2* tbuf = nullptr;             // cf32[nrow][nfft], inside alloc
     float2* scr = nullptr;              // cf32[nrow][nfft], the matrix between the passes, behind it
     float2* tab = nullptr;              // cf32[npair][nchan][nfft] in pass B's order
@@ -29,15 +28,13 @@ struct CdlongContext : BeamStreamContext {
     size_t twiddle_words() const { return ((size_t)nfft + ((size_t)1 << LN1) + ((size_t)1 << LN2)) / 2; }
     size_t state_bytes() const { return (2 * (size_t)nrow * nfft + (size_t)npair * pair_words() + twiddle_words()) * sizeof(float2); }
 };
-constexpr size_t CL_GUARD = 64 << 10;   // guard bands around the state (xengCdlongCheckGuards)
-constexpr int CL_GUARD_BYTE = 0xA5;
 static std::mutex g_clmu;
 static CdlongContext g_cl;
 
 static int cdlong_destroy_locked() {
     if (!g_cl.live) return XENG_STATUS_SUCCESS;
     beam_context_close(g_cl);
-    if (g_cl.alloc) (void)hipFree(g_cl.alloc);
+    g_cl.alloc.free();
     g_cl = CdlongContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -114,15 +111,12 @@ int xengCdlongInitialize(int gpu, int nchan, int nbeam, int ntime, int pair0, in
         const double step = -2.0 * 3.14159265358979323846 / (double)n;
         for (size_t k = 0; k < n / 2; k++) tw.push_back(make_float2((float)std::cos(step * (double)k), (float)std::sin(step * (double)k)));
     }
-    if (hipMalloc(&x.alloc, x.state_bytes() + 2 * CL_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc, CL_GUARD_BYTE, x.state_bytes() + 2 * CL_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc + CL_GUARD, 0, x.state_bytes()) != hipSuccess) {
+    if (x.alloc.open(x.state_bytes()) != hipSuccess) {
         (void)hipGetLastError();
-        if (x.alloc) (void)hipFree(x.alloc);
         x = CdlongContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Cdlong: cannot allocate %.3g MB of state", state * 1e-6);
     }
-    x.tbuf = (float2*)(x.alloc + CL_GUARD);
+    x.tbuf = (float2*)x.alloc.data();
     x.scr = x.tbuf + (size_t)x.nrow * nfft;
     x.tab = x.scr + (size_t)x.nrow * nfft;
     x.tws = x.tab + (size_t)npair * x.pair_words();
@@ -132,7 +126,7 @@ int xengCdlongInitialize(int gpu, int nchan, int nbeam, int ntime, int pair0, in
     for (int p = 0; p < npair && e == hipSuccess; p++) e = cdlong_upload_pair(x, p, nullptr);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(x.alloc);
+        x.alloc.free();
         x = CdlongContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Cdlong: cannot upload the twiddles and the table");
     }
@@ -222,22 +216,7 @@ int xengCdlongGetInfo(int* step, int* max_blocks_per_call, long long* nsamples_s
     return XENG_STATUS_SUCCESS;
 }
 
-int xengCdlongCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "CdlongCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_clmu);
-    CdlongContext& x = g_cl;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Cdlong: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * CL_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.alloc, CL_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + CL_GUARD, x.alloc + CL_GUARD + x.state_bytes(), CL_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != CL_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengCdlongCheckGuards(int* intact) { return beam_context_check_guards(g_clmu, g_cl, g_cl.alloc, "Cdlong", intact); }
 int xengCdlongMark(unsigned long long* ticket) { return beam_context_mark(g_clmu, g_cl, "Cdlong", ticket); }
 int xengCdlongWait(unsigned long long ticket) { return beam_context_wait(g_clmu, g_cl, "Cdlong", ticket); }
 int xengCdlongTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_clmu, g_cl, "Cdlong", ticket, done); }

@@ -1,7 +1,5 @@
-// Host side of the deconvolver (UpchanClean; clean_kernels.h): a process-global context of its own, beside the Beamform, Upchan*,
-// Dedisp, Pulse, Fold, Period, Cdedisp, Image, Gaincal and Calapply contexts, whose kernel runs on the beamformer's stream
-// (STREAM_BEAM) and ticks its clock, so that rings declared 'beam' and their span stamps cover it unchanged.  A Run enqueues
-// niter + 2 launches of the one kernel and reads nothing back.
+// Host side of the deconvolver (UpchanClean; clean_kernels.h): a process-global context of its own on the beamformer's stream
+// (BeamStreamContext, xeng_common.h).  A Run enqueues niter + 2 launches of the one kernel and reads nothing back.
 #include <cmath>
 #include <mutex>
 #include <vector>
@@ -15,7 +13,7 @@ static size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 struct CleanContext : BeamStreamContext {
     int nstand = 0, nfine = 0, nfavg = 0, npix = 0, niter_max = 0;
-    uint8_t* alloc = nullptr;           // CLN_GUARD bytes of CLN_GUARD_BYTE, the state, CLN_GUARD bytes of CLN_GUARD_BYTE
+    GuardedState alloc;                 // the state between its guard bands (xengCleanCheckGuards)
     double* freq = nullptr;             // f64[nfine], inside alloc
     double* tauT = nullptr;             // f64[nstand][npix], behind it
     float* w = nullptr;                 // f32[nstand]
@@ -39,15 +37,13 @@ struct CleanContext : BeamStreamContext {
     long long stats_offset() const { return comp_offset() + (long long)ngroup() * niter * CLN_REC * 4; }
     long long span_bytes() const { return stats_offset() + (long long)ngroup() * 16; }
 };
-constexpr size_t CLN_GUARD = 64 << 10;  // guard bands around the state (xengCleanCheckGuards)
-constexpr int CLN_GUARD_BYTE = 0xA5;
 static std::mutex g_clmu;
 static CleanContext g_cl;
 
 static int clean_destroy_locked() {
     if (!g_cl.live) return XENG_STATUS_SUCCESS;
     beam_context_close(g_cl);
-    if (g_cl.alloc) (void)hipFree(g_cl.alloc);
+    g_cl.alloc.free();
     g_cl = CleanContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -87,15 +83,12 @@ int xengCleanInitialize(int gpu, int nstand, int nfine, int nfavg, int npix, int
     if (rc) return rc;
     x.nstand = nstand; x.nfine = nfine; x.nfavg = nfavg; x.npix = npix; x.niter_max = niter_max;
     std::vector<float> ones((size_t)nstand, 1.0f);
-    if (hipMalloc(&x.alloc, x.state_bytes() + 2 * CLN_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc, CLN_GUARD_BYTE, x.state_bytes() + 2 * CLN_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc + CLN_GUARD, 0, x.state_bytes()) != hipSuccess) {
+    if (x.alloc.open(x.state_bytes()) != hipSuccess) {
         (void)hipGetLastError();
-        if (x.alloc) (void)hipFree(x.alloc);
         x = CleanContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Clean: cannot allocate %.3g MB of state", (double)npix * nstand * 8e-6);
     }
-    x.freq = (double*)(x.alloc + CLN_GUARD);
+    x.freq = (double*)x.alloc.data();
     x.tauT = x.freq + nfine;
     x.w = (float*)(x.tauT + (size_t)npix * nstand);
     x.mask = (uint8_t*)x.w + pad16((size_t)nstand * sizeof(float));
@@ -104,7 +97,7 @@ int xengCleanInitialize(int gpu, int nstand, int nfine, int nfavg, int npix, int
     if (hipMemcpy(x.w, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
         hip_memset_now(x.mask, 1, (size_t)npix) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(x.alloc);
+        x.alloc.free();
         x = CleanContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Clean: cannot upload the weights and the window");
     }
@@ -214,22 +207,7 @@ int xengCleanRun(const void* image_dev, void* out_dev) {
     return XENG_STATUS_SUCCESS;
 }
 
-int xengCleanCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "CleanCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_clmu);
-    CleanContext& x = g_cl;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Clean: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * CLN_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.alloc, CLN_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + CLN_GUARD, x.alloc + CLN_GUARD + x.state_bytes(), CLN_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != CLN_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengCleanCheckGuards(int* intact) { return beam_context_check_guards(g_clmu, g_cl, g_cl.alloc, "Clean", intact); }
 int xengCleanMark(unsigned long long* ticket) { return beam_context_mark(g_clmu, g_cl, "Clean", ticket); }
 int xengCleanWait(unsigned long long ticket) { return beam_context_wait(g_clmu, g_cl, "Clean", ticket); }
 int xengCleanTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_clmu, g_cl, "Clean", ticket, done); }

@@ -1,6 +1,5 @@
-// Host side of the incoherent dedisperser (BeamDedisperse; dedisp_kernels.h): a process-global context of its own, beside the
-// Beamform, Upchan* contexts, whose kernels run on the beamformer's stream (STREAM_BEAM) and tick its clock, so that rings
-// declared 'beam' and their span stamps cover them unchanged.
+// Host side of the incoherent dedisperser (BeamDedisperse; dedisp_kernels.h): a process-global context of its own on the
+// beamformer's stream (BeamStreamContext, xeng_common.h).
 #include <cmath>
 #include <mutex>
 #include <vector>
@@ -13,7 +12,7 @@ namespace xeng {
 struct DedispContext : BeamStreamContext {
     int npair = 0, nfine = 0, nwin = 0, ndm = 0, max_delay = 0, nprod = 0;
     int L = 0;                          // windows of the history ring: max_delay + nwin
-    uint8_t* hist_alloc = nullptr;      // DD_GUARD bytes of DD_GUARD_BYTE, the history, DD_GUARD bytes of DD_GUARD_BYTE
+    GuardedState hist_alloc;            // the history between its guard bands (xengDedispCheckGuards)
     float* hist = nullptr;              // f32[npair][nfine][nprod][L], inside hist_alloc
     int* bt = nullptr;                  // i32[nfine][ndm]: back-delays S - s[d][q]
     float* w = nullptr;                 // f32[nfine]
@@ -23,15 +22,13 @@ struct DedispContext : BeamStreamContext {
 
     size_t hist_bytes() const { return (size_t)npair * nfine * nprod * (size_t)L * sizeof(float); }
 };
-constexpr size_t DD_GUARD = 64 << 10;   // guard bands around the history (xengDedispCheckGuards)
-constexpr int DD_GUARD_BYTE = 0xA5;
 static std::mutex g_ddmu;
 static DedispContext g_dd;
 
 static int dedisp_destroy_locked() {
     if (!g_dd.live) return XENG_STATUS_SUCCESS;
     beam_context_close(g_dd);
-    if (g_dd.hist_alloc) (void)hipFree(g_dd.hist_alloc);
+    g_dd.hist_alloc.free();
     if (g_dd.bt) (void)hipFree(g_dd.bt);
     if (g_dd.w) (void)hipFree(g_dd.w);
     g_dd = DedispContext();
@@ -78,18 +75,17 @@ int xengDedispInitialize(int gpu, int npair, int nfine, int nwin, int ndm, int m
     x.npair = npair; x.nfine = nfine; x.nwin = nwin; x.ndm = ndm; x.max_delay = max_delay; x.nprod = nprod;
     x.L = (int)L;
     const std::vector<float> ones((size_t)nfine, 1.f);
-    if (hipMalloc(&x.hist_alloc, x.hist_bytes() + 2 * DD_GUARD) != hipSuccess || hipMalloc(&x.bt, (size_t)ndm * nfine * sizeof(int)) != hipSuccess ||
-        hipMalloc(&x.w, (size_t)nfine * sizeof(float)) != hipSuccess || hip_memset_now(x.hist_alloc, DD_GUARD_BYTE, x.hist_bytes() + 2 * DD_GUARD) != hipSuccess ||
-        hip_memset_now(x.hist_alloc + DD_GUARD, 0, x.hist_bytes()) != hipSuccess ||
+    if (x.hist_alloc.open(x.hist_bytes()) != hipSuccess || hipMalloc(&x.bt, (size_t)ndm * nfine * sizeof(int)) != hipSuccess ||
+        hipMalloc(&x.w, (size_t)nfine * sizeof(float)) != hipSuccess ||
         hipMemcpy(x.w, ones.data(), (size_t)nfine * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
-        if (x.hist_alloc) (void)hipFree(x.hist_alloc);
+        x.hist_alloc.free();
         if (x.bt) (void)hipFree(x.bt);
         if (x.w) (void)hipFree(x.w);
         x = DedispContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Dedisp: cannot allocate %.3g MB of history and %.3g MB of delays", bytes * 1e-6, (double)ndm * nfine * 4e-6);
     }
-    x.hist = (float*)(x.hist_alloc + DD_GUARD);
+    x.hist = (float*)x.hist_alloc.data();
     x.live = true;
     return XENG_STATUS_SUCCESS;
 }
@@ -178,22 +174,7 @@ int xengDedispGetInfo(int* max_delay_in_use, long long* nwindows_since_reset) {
     return XENG_STATUS_SUCCESS;
 }
 
-int xengDedispCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "DedispCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_ddmu);
-    DedispContext& x = g_dd;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Dedisp: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * DD_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.hist_alloc, DD_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + DD_GUARD, x.hist_alloc + DD_GUARD + x.hist_bytes(), DD_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != DD_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengDedispCheckGuards(int* intact) { return beam_context_check_guards(g_ddmu, g_dd, g_dd.hist_alloc, "Dedisp", intact); }
 int xengDedispMark(unsigned long long* ticket) { return beam_context_mark(g_ddmu, g_dd, "Dedisp", ticket); }
 int xengDedispWait(unsigned long long ticket) { return beam_context_wait(g_ddmu, g_dd, "Dedisp", ticket); }
 int xengDedispTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_ddmu, g_dd, "Dedisp", ticket, done); }

@@ -1,6 +1,5 @@
-// Host side of the fast-folding search (BeamFfaSearch; ffa_kernels.h): a process-global context of its own, beside the Beamform,
-// Upchan*, Dedisp, Pulse, Fold and Period contexts, whose kernels run on the beamformer's stream (STREAM_BEAM) and tick its clock,
-// so that rings declared 'beam' and their span stamps cover them unchanged.
+// Host side of the fast-folding search (BeamFfaSearch; ffa_kernels.h): a process-global context of its own on the
+// beamformer's stream (BeamStreamContext, xeng_common.h).
 #include <cmath>
 #include <mutex>
 #include <vector>
@@ -17,7 +16,7 @@ struct FfaContext : BeamStreamContext {
     int xw = 0;                         // words of a series in xbuf: N_0 + ... + N_{noct-1}
     size_t lds[FA_MAX_OCT] = {};        // bytes of dynamic LDS of the fold kernel, per octave
     FfaRinv rinv;
-    uint8_t* alloc = nullptr;           // FA_GUARD bytes of FA_GUARD_BYTE, the state, FA_GUARD bytes of FA_GUARD_BYTE
+    GuardedState alloc;                 // the state between its guard bands (xengFfaCheckGuards)
     FfaRecord* table = nullptr;         // [nser][noct][np][nwidth], inside alloc
     float* tbuf = nullptr;              // f32[nser][nt], behind it
     float* xbuf = nullptr;              // f32[nser][xw]
@@ -33,15 +32,13 @@ struct FfaContext : BeamStreamContext {
                ((size_t)nser * nt + (size_t)nser * xw + (size_t)nser * noct * 4 + 2 * (size_t)nser + FA_MAX_WIDTH * FA_RHO_STRIDE) * sizeof(float);
     }
 };
-constexpr size_t FA_GUARD = 64 << 10;   // guard bands around the state (xengFfaCheckGuards)
-constexpr int FA_GUARD_BYTE = 0xA5;
 static std::mutex g_famu;
 static FfaContext g_fa;
 
 static int ffa_destroy_locked() {
     if (!g_fa.live) return XENG_STATUS_SUCCESS;
     beam_context_close(g_fa);
-    if (g_fa.alloc) (void)hipFree(g_fa.alloc);
+    g_fa.alloc.free();
     g_fa = FfaContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -129,15 +126,12 @@ int xengFfaInitialize(int gpu, int npair, int ndm, int nwin, int nprod, int nds,
     std::vector<float> rho((size_t)FA_MAX_WIDTH * FA_RHO_STRIDE, 0.f);
     for (int iw = 0; iw < FA_MAX_WIDTH; iw++)
         for (int lm = 0; lm < FA_RHO_STRIDE; lm++) rho[(size_t)iw * FA_RHO_STRIDE + lm] = (float)(1.0 / std::sqrt((double)(1 << iw) * (double)(1 << lm)));
-    if (hipMalloc(&x.alloc, x.state_bytes() + 2 * FA_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc, FA_GUARD_BYTE, x.state_bytes() + 2 * FA_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc + FA_GUARD, 0, x.state_bytes()) != hipSuccess) {
+    if (x.alloc.open(x.state_bytes()) != hipSuccess) {
         (void)hipGetLastError();
-        if (x.alloc) (void)hipFree(x.alloc);
         x = FfaContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Ffa: cannot allocate %.3g MB of state", need * 1e-6);
     }
-    x.table = (FfaRecord*)(x.alloc + FA_GUARD);
+    x.table = (FfaRecord*)x.alloc.data();
     x.tbuf = (float*)(x.table + (size_t)x.nser * noct * x.np * nwidth);
     x.xbuf = x.tbuf + (size_t)x.nser * nt;
     x.stats = x.xbuf + (size_t)x.nser * x.xw;
@@ -145,7 +139,7 @@ int xengFfaInitialize(int gpu, int npair, int ndm, int nwin, int nprod, int nds,
     x.rho = x.part + 2 * (size_t)x.nser;
     if (hipMemcpy(x.rho, rho.data(), rho.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(x.alloc);
+        x.alloc.free();
         x = FfaContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Ffa: cannot upload the score table");
     }
@@ -218,22 +212,7 @@ int xengFfaGetStats(float* stats_host) {
     return XENG_STATUS_SUCCESS;
 }
 
-int xengFfaCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "FfaCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_famu);
-    FfaContext& x = g_fa;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Ffa: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * FA_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.alloc, FA_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + FA_GUARD, x.alloc + FA_GUARD + x.state_bytes(), FA_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != FA_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengFfaCheckGuards(int* intact) { return beam_context_check_guards(g_famu, g_fa, g_fa.alloc, "Ffa", intact); }
 int xengFfaMark(unsigned long long* ticket) { return beam_context_mark(g_famu, g_fa, "Ffa", ticket); }
 int xengFfaWait(unsigned long long ticket) { return beam_context_wait(g_famu, g_fa, "Ffa", ticket); }
 int xengFfaTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_famu, g_fa, "Ffa", ticket, done); }

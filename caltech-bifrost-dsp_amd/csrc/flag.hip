@@ -1,6 +1,5 @@
-// Host side of the flagging stage (UpchanFlag; flag_kernels.h): a process-global context of its own, beside the Beamform, Upchan*,
-// Dedisp, Pulse, Fold, Period, Cdedisp, Image, Gaincal, Calapply, Peel and Clean contexts, whose kernels run on the beamformer's
-// stream (STREAM_BEAM) and tick its clock, so that rings declared 'beam' and their span stamps cover it unchanged.
+// Host side of the flagging stage (UpchanFlag; flag_kernels.h): a process-global context of its own on the beamformer's stream
+// (BeamStreamContext, xeng_common.h).
 #include <algorithm>
 #include <cmath>
 #include <mutex>
@@ -16,7 +15,7 @@ static_assert(XENG_FLAG_MAX_NSTAND == FL_MAX_NSTAND && XENG_FLAG_MAX_NFINE == FL
 
 struct FlagContext : BeamStreamContext {
     int nstand = 0, nfine = 0;
-    uint8_t* alloc = nullptr;           // FL_GUARD bytes of FL_GUARD_BYTE, the state, FL_GUARD bytes of FL_GUARD_BYTE
+    GuardedState alloc;                 // the state between its guard bands (xengFlagCheckGuards)
     float* part = nullptr;              // f32[nfine][2][nstand][ntile], inside alloc
     float* autos = nullptr;             // f32[nfine][2][nstand], behind it
     float* w = nullptr;                 // f32[nstand]
@@ -34,15 +33,13 @@ struct FlagContext : BeamStreamContext {
         return (n + 15) & ~(size_t)15;
     }
 };
-constexpr size_t FL_GUARD = 64 << 10;   // guard bands around the state (xengFlagCheckGuards)
-constexpr int FL_GUARD_BYTE = 0xA5;
 static std::mutex g_flmu;
 static FlagContext g_fl;
 
 static int flag_destroy_locked() {
     if (!g_fl.live) return XENG_STATUS_SUCCESS;
     beam_context_close(g_fl);
-    if (g_fl.alloc) (void)hipFree(g_fl.alloc);
+    g_fl.alloc.free();
     g_fl = FlagContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -69,17 +66,16 @@ int xengFlagInitialize(int gpu, int nstand, int nfine) {
     x.nstand = nstand; x.nfine = nfine;
     const std::vector<float> ones((size_t)nstand, 1.f);
     bool ok = false;
-    if (hipMalloc(&x.alloc, x.state_bytes() + 2 * FL_GUARD) == hipSuccess && hip_memset_now(x.alloc, FL_GUARD_BYTE, x.state_bytes() + 2 * FL_GUARD) == hipSuccess &&
-        hip_memset_now(x.alloc + FL_GUARD, 0, x.state_bytes()) == hipSuccess) {
-        x.part = (float*)(x.alloc + FL_GUARD);
+    if (x.alloc.open(x.state_bytes()) == hipSuccess) {
+        x.part = (float*)x.alloc.data();
         x.autos = x.part + (size_t)nfine * 2 * nstand * x.ntile();
         x.w = x.autos + (size_t)nfine * 2 * nstand;
-        x.zero = (float2*)(x.alloc + FL_GUARD + x.zero_offset());
+        x.zero = (float2*)(x.alloc.data() + x.zero_offset());
         ok = hipMemcpy(x.w, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
     }
     if (!ok) {
         (void)hipGetLastError();
-        if (x.alloc) (void)hipFree(x.alloc);
+        x.alloc.free();
         x = FlagContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Flag: cannot allocate %.3g MB of state", (double)nfine * nstand * 8e-6 * ((nstand + FL_T - 1) / FL_T + 1));
     }
@@ -163,22 +159,7 @@ int xengFlagRun(const void* vis_dev, void* mask_dev, void* stats_dev, void* chan
     return XENG_STATUS_SUCCESS;
 }
 
-int xengFlagCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "FlagCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_flmu);
-    FlagContext& x = g_fl;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Flag: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * FL_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.alloc, FL_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + FL_GUARD, x.alloc + FL_GUARD + x.state_bytes(), FL_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != FL_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengFlagCheckGuards(int* intact) { return beam_context_check_guards(g_flmu, g_fl, g_fl.alloc, "Flag", intact); }
 int xengFlagMark(unsigned long long* ticket) { return beam_context_mark(g_flmu, g_fl, "Flag", ticket); }
 int xengFlagWait(unsigned long long ticket) { return beam_context_wait(g_flmu, g_fl, "Flag", ticket); }
 int xengFlagTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_flmu, g_fl, "Flag", ticket, done); }

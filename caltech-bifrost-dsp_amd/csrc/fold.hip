@@ -1,7 +1,6 @@
-// Host side of the phase folder (BeamFold; fold_kernels.h): a process-global context of its own, beside the Beamform, Upchan*,
-// Dedisp and Pulse contexts, whose kernels run on the beamformer's stream (STREAM_BEAM) and tick its clock, so that rings
-// declared 'beam' and their span stamps cover them unchanged.  The oscillators, the window counts and the hits live here, on
-// the host: the device holds the profile, a copy of the oscillators, the rotations, the weights and (for a dump) the hits.
+// Host side of the phase folder (BeamFold; fold_kernels.h): a process-global context of its own on the beamformer's stream
+// (BeamStreamContext, xeng_common.h).  The oscillators, the window counts and the hits live here, on the host: the device
+// holds the profile, a copy of the oscillators, the rotations, the weights and (for a dump) the hits.
 #include <algorithm>
 #include <cmath>
 #include <mutex>
@@ -14,7 +13,7 @@ namespace xeng {
 
 struct FoldContext : BeamStreamContext {
     int npair = 0, nfine = 0, nwin = 0, nbin = 0, nprod = 0;
-    uint8_t* prof_alloc = nullptr;      // FOLD_GUARD bytes of FOLD_GUARD_BYTE, the profile, FOLD_GUARD bytes of FOLD_GUARD_BYTE
+    GuardedState prof_alloc;            // the profile between its guard bands (xengFoldCheckGuards)
     float* prof = nullptr;              // f32[npair][nbin][nfine][nprod], inside prof_alloc
     FoldOsc* osc_dev = nullptr;         // [npair]
     int* rot = nullptr;                 // i32[npair][nfine]
@@ -30,13 +29,11 @@ struct FoldContext : BeamStreamContext {
     size_t prof_words() const { return (size_t)npair * nbin * nfine * nprod; }
     size_t prof_bytes() const { return prof_words() * sizeof(float); }
 };
-constexpr size_t FOLD_GUARD = 64 << 10; // guard bands around the profile (xengFoldCheckGuards)
-constexpr int FOLD_GUARD_BYTE = 0xA5;
 static std::mutex g_fomu;
 static FoldContext g_fo;
 
 static void fold_free(FoldContext& x) {
-    if (x.prof_alloc) (void)hipFree(x.prof_alloc);
+    x.prof_alloc.free();
     if (x.osc_dev) (void)hipFree(x.osc_dev);
     if (x.rot) (void)hipFree(x.rot);
     if (x.w) (void)hipFree(x.w);
@@ -79,11 +76,9 @@ int xengFoldInitialize(int gpu, int npair, int nfine, int nwin, int nbin, int np
     if (rc) return rc;
     x.npair = npair; x.nfine = nfine; x.nwin = nwin; x.nbin = nbin; x.nprod = nprod;
     const std::vector<float> ones((size_t)nfine, 1.f);
-    if (hipMalloc(&x.prof_alloc, x.prof_bytes() + 2 * FOLD_GUARD) != hipSuccess || hipMalloc(&x.osc_dev, (size_t)npair * sizeof(FoldOsc)) != hipSuccess ||
+    if (x.prof_alloc.open(x.prof_bytes()) != hipSuccess || hipMalloc(&x.osc_dev, (size_t)npair * sizeof(FoldOsc)) != hipSuccess ||
         hipMalloc(&x.rot, (size_t)npair * nfine * sizeof(int)) != hipSuccess || hipMalloc(&x.w, (size_t)nfine * sizeof(float)) != hipSuccess ||
-        hipMalloc(&x.hits_dev, (size_t)npair * nbin * sizeof(uint32_t)) != hipSuccess ||
-        hip_memset_now(x.prof_alloc, FOLD_GUARD_BYTE, x.prof_bytes() + 2 * FOLD_GUARD) != hipSuccess ||
-        hip_memset_now(x.prof_alloc + FOLD_GUARD, 0, x.prof_bytes()) != hipSuccess || hip_memset_now(x.osc_dev, 0, (size_t)npair * sizeof(FoldOsc)) != hipSuccess ||
+        hipMalloc(&x.hits_dev, (size_t)npair * nbin * sizeof(uint32_t)) != hipSuccess || hip_memset_now(x.osc_dev, 0, (size_t)npair * sizeof(FoldOsc)) != hipSuccess ||
         hip_memset_now(x.rot, 0, (size_t)npair * nfine * sizeof(int)) != hipSuccess || hip_memset_now(x.hits_dev, 0, (size_t)npair * nbin * sizeof(uint32_t)) != hipSuccess ||
         hipMemcpy(x.w, ones.data(), (size_t)nfine * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
@@ -91,7 +86,7 @@ int xengFoldInitialize(int gpu, int npair, int nfine, int nwin, int nbin, int np
         x = FoldContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Fold: cannot allocate %.3g MB of profile", bytes * 1e-6);
     }
-    x.prof = (float*)(x.prof_alloc + FOLD_GUARD);
+    x.prof = (float*)x.prof_alloc.data();
     x.osc.assign((size_t)npair, FoldOsc{0, 0, 0, 0, 0});
     x.hits.assign((size_t)npair * nbin, 0u);
     x.live = true;
@@ -242,22 +237,7 @@ int xengFoldGetInfo(long long* nwindows_since_reset, long long* nwindows_folded)
     return XENG_STATUS_SUCCESS;
 }
 
-int xengFoldCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "FoldCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_fomu);
-    FoldContext& x = g_fo;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Fold: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * FOLD_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.prof_alloc, FOLD_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + FOLD_GUARD, x.prof_alloc + FOLD_GUARD + x.prof_bytes(), FOLD_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != FOLD_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengFoldCheckGuards(int* intact) { return beam_context_check_guards(g_fomu, g_fo, g_fo.prof_alloc, "Fold", intact); }
 int xengFoldMark(unsigned long long* ticket) { return beam_context_mark(g_fomu, g_fo, "Fold", ticket); }
 int xengFoldWait(unsigned long long ticket) { return beam_context_wait(g_fomu, g_fo, "Fold", ticket); }
 int xengFoldTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_fomu, g_fo, "Fold", ticket, done); }

@@ -1,6 +1,5 @@
-// Host side of the gain solver (UpchanGainCal; gaincal_kernels.h): a process-global context of its own, beside the Beamform, Upchan*,
-// Dedisp, Pulse, Fold, Period, Cdedisp and Image contexts, whose kernel runs on the beamformer's stream (STREAM_BEAM) and ticks its
-// clock, so that rings declared 'beam' and their span stamps cover it unchanged.
+// Host side of the gain solver (UpchanGainCal; gaincal_kernels.h): a process-global context of its own on the beamformer's
+// stream (BeamStreamContext, xeng_common.h).
 #include <cmath>
 #include <mutex>
 #include <vector>
@@ -14,7 +13,7 @@ static_assert(XENG_GAINCAL_MAX_NSRC == GC_K && XENG_GAINCAL_MAX_NSTAND == GC_MAX
 
 struct GaincalContext : BeamStreamContext {
     int nstand = 0, nfine = 0, nsrc = 0;
-    uint8_t* alloc = nullptr;           // GC_GUARD bytes of GC_GUARD_BYTE, the state, GC_GUARD bytes of GC_GUARD_BYTE
+    GuardedState alloc;                 // the state between its guard bands (xengGaincalCheckGuards)
     double* freq = nullptr;             // f64[nfine], inside alloc
     double* tau = nullptr;              // f64[nsrc][nstand], behind it
     float2* keep_g = nullptr;           // cf32[nfine][2][nstand]: the last unreferenced solution
@@ -31,15 +30,13 @@ struct GaincalContext : BeamStreamContext {
         return (n + 15) & ~(size_t)15;
     }
 };
-constexpr size_t GC_GUARD = 64 << 10;   // guard bands around the state (xengGaincalCheckGuards)
-constexpr int GC_GUARD_BYTE = 0xA5;
 static std::mutex g_gcmu;
 static GaincalContext g_gc;
 
 static int gaincal_destroy_locked() {
     if (!g_gc.live) return XENG_STATUS_SUCCESS;
     beam_context_close(g_gc);
-    if (g_gc.alloc) (void)hipFree(g_gc.alloc);
+    g_gc.alloc.free();
     g_gc = GaincalContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -72,15 +69,12 @@ int xengGaincalInitialize(int gpu, int nstand, int nfine, int nsrc) {
         x = GaincalContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Gaincal: %d stands need %zu bytes of LDS, which the device refuses", nstand, lds);
     }
-    if (hipMalloc(&x.alloc, x.state_bytes() + 2 * GC_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc, GC_GUARD_BYTE, x.state_bytes() + 2 * GC_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc + GC_GUARD, 0, x.state_bytes()) != hipSuccess) {
+    if (x.alloc.open(x.state_bytes()) != hipSuccess) {
         (void)hipGetLastError();
-        if (x.alloc) (void)hipFree(x.alloc);
         x = GaincalContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Gaincal: cannot allocate %.3g MB of state", (double)nfine * nstand * 16e-6);
     }
-    x.freq = (double*)(x.alloc + GC_GUARD);
+    x.freq = (double*)x.alloc.data();
     x.tau = x.freq + nfine;
     x.keep_g = (float2*)(x.tau + (size_t)nsrc * nstand);
     x.flux = (float*)(x.keep_g + (size_t)nfine * 2 * nstand);
@@ -170,22 +164,7 @@ int xengGaincalRun(const void* vis_dev, void* gains_dev, void* stats_dev, int wa
     return XENG_STATUS_SUCCESS;
 }
 
-int xengGaincalCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "GaincalCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_gcmu);
-    GaincalContext& x = g_gc;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Gaincal: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * GC_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.alloc, GC_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + GC_GUARD, x.alloc + GC_GUARD + x.state_bytes(), GC_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != GC_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengGaincalCheckGuards(int* intact) { return beam_context_check_guards(g_gcmu, g_gc, g_gc.alloc, "Gaincal", intact); }
 int xengGaincalMark(unsigned long long* ticket) { return beam_context_mark(g_gcmu, g_gc, "Gaincal", ticket); }
 int xengGaincalWait(unsigned long long ticket) { return beam_context_wait(g_gcmu, g_gc, "Gaincal", ticket); }
 int xengGaincalTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_gcmu, g_gc, "Gaincal", ticket, done); }

@@ -1,6 +1,5 @@
-// Host side of the imager (UpchanImage; image_kernels.h): a process-global context of its own, beside the Beamform, Upchan*, Dedisp,
-// Pulse, Fold, Period and Cdedisp contexts, whose kernel runs on the beamformer's stream (STREAM_BEAM) and ticks its clock, so that
-// rings declared 'beam' and their span stamps cover it unchanged.
+// Host side of the imager (UpchanImage; image_kernels.h): a process-global context of its own on the beamformer's stream
+// (BeamStreamContext, xeng_common.h).
 #include <cmath>
 #include <mutex>
 #include <vector>
@@ -12,7 +11,7 @@ namespace xeng {
 
 struct ImageContext : BeamStreamContext {
     int nstand = 0, nfine = 0, nfavg = 0, npix = 0;
-    uint8_t* alloc = nullptr;           // IMG_GUARD bytes of IMG_GUARD_BYTE, the state, IMG_GUARD bytes of IMG_GUARD_BYTE
+    GuardedState alloc;                 // the state between its guard bands (xengImageCheckGuards)
     double* freq = nullptr;             // f64[nfine], inside alloc
     double* tau = nullptr;              // f64[npix][nstand], behind it
     float* w = nullptr;                 // f32[nstand], behind that
@@ -22,15 +21,13 @@ struct ImageContext : BeamStreamContext {
 
     size_t state_bytes() const { return ((size_t)nfine + (size_t)npix * nstand) * sizeof(double) + (((size_t)nstand * sizeof(float) + 15) & ~(size_t)15); }
 };
-constexpr size_t IMG_GUARD = 64 << 10;  // guard bands around the state (xengImageCheckGuards)
-constexpr int IMG_GUARD_BYTE = 0xA5;
 static std::mutex g_immu;
 static ImageContext g_im;
 
 static int image_destroy_locked() {
     if (!g_im.live) return XENG_STATUS_SUCCESS;
     beam_context_close(g_im);
-    if (g_im.alloc) (void)hipFree(g_im.alloc);
+    g_im.alloc.free();
     g_im = ImageContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -73,20 +70,17 @@ int xengImageInitialize(int gpu, int nstand, int nfine, int nfavg, int npix) {
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Image: %d stands need %zu bytes of LDS, which the device refuses", nstand, lds);
     }
     std::vector<float> ones((size_t)nstand, 1.0f);
-    if (hipMalloc(&x.alloc, x.state_bytes() + 2 * IMG_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc, IMG_GUARD_BYTE, x.state_bytes() + 2 * IMG_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc + IMG_GUARD, 0, x.state_bytes()) != hipSuccess) {
+    if (x.alloc.open(x.state_bytes()) != hipSuccess) {
         (void)hipGetLastError();
-        if (x.alloc) (void)hipFree(x.alloc);
         x = ImageContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Image: cannot allocate %.3g MB of state", (double)npix * nstand * 8e-6);
     }
-    x.freq = (double*)(x.alloc + IMG_GUARD);
+    x.freq = (double*)x.alloc.data();
     x.tau = x.freq + nfine;
     x.w = (float*)(x.tau + (size_t)npix * nstand);
     if (hipMemcpy(x.w, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(x.alloc);
+        x.alloc.free();
         x = ImageContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Image: cannot upload the weights");
     }
@@ -161,22 +155,7 @@ int xengImageRun(const void* vis_dev, void* out_dev) {
     return XENG_STATUS_SUCCESS;
 }
 
-int xengImageCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "ImageCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_immu);
-    ImageContext& x = g_im;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Image: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * IMG_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.alloc, IMG_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + IMG_GUARD, x.alloc + IMG_GUARD + x.state_bytes(), IMG_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != IMG_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengImageCheckGuards(int* intact) { return beam_context_check_guards(g_immu, g_im, g_im.alloc, "Image", intact); }
 int xengImageMark(unsigned long long* ticket) { return beam_context_mark(g_immu, g_im, "Image", ticket); }
 int xengImageWait(unsigned long long ticket) { return beam_context_wait(g_immu, g_im, "Image", ticket); }
 int xengImageTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_immu, g_im, "Image", ticket, done); }

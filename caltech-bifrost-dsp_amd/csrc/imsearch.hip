@@ -1,6 +1,5 @@
 // Host side of the dedispersed transient search of the images (UpchanImageSearch; imsearch_kernels.h): a process-global context of
-// its own, beside the Image, Clean and Pulse contexts, whose kernels run on the beamformer's stream (STREAM_BEAM) and tick its
-// clock, so that rings declared 'beam' and their span stamps cover them unchanged.
+// its own on the beamformer's stream (BeamStreamContext, xeng_common.h).
 #include <climits>
 #include <cmath>
 #include <mutex>
@@ -17,7 +16,7 @@ struct ImsearchContext : BeamStreamContext {
     int T = 0;                          // integrations a boxcar reaches back: 2^(nwidth-1) - 1
     int S = -1;                         // largest delay of the table in use, -1 before SetDelays
     int nused = 0;                      // groups of weight != 0
-    uint8_t* alloc = nullptr;           // IS_GUARD bytes of IS_GUARD_BYTE, state, U, Z, IS_GUARD bytes of IS_GUARD_BYTE
+    GuardedState alloc;                 // state, U, Z between their guard bands (xengImsearchCheckGuards)
     float *state = nullptr, *U = nullptr, *Z = nullptr;
     int *bk = nullptr, *gk = nullptr;   // i32[ndm][nusedp], i32[nusedp]: nused rounded up to IS_CHUNK
     float* wk = nullptr;                // f32[nusedp]
@@ -31,13 +30,11 @@ struct ImsearchContext : BeamStreamContext {
     size_t z_words() const { return (size_t)(T + 1) * ndm * npitch; }
     size_t bytes() const { return (state_words() + u_words() + z_words()) * sizeof(float); }
 };
-constexpr size_t IS_GUARD = 64 << 10;   // guard bands around the state (xengImsearchCheckGuards)
-constexpr int IS_GUARD_BYTE = 0xA5;
 static std::mutex g_ismu;
 static ImsearchContext g_is;
 
 static void imsearch_free(ImsearchContext& x) {
-    if (x.alloc) (void)hipFree(x.alloc);
+    x.alloc.free();
     if (x.bk) (void)hipFree(x.bk);
     if (x.gk) (void)hipFree(x.gk);
     if (x.wk) (void)hipFree(x.wk);
@@ -114,15 +111,14 @@ int xengImsearchInitialize(int gpu, int npix, int ngroup, int ndm, int max_delay
     x.r_nstat = 1.0f / (float)nstat;
     x.weights.assign((size_t)ngroup, 1.f);
     const size_t ngroupp = (size_t)(ngroup + IS_CHUNK - 1) / IS_CHUNK * IS_CHUNK;
-    if (hipMalloc(&x.alloc, x.bytes() + 2 * IS_GUARD) != hipSuccess || hipMalloc(&x.bk, (size_t)ndm * ngroupp * sizeof(int)) != hipSuccess ||
-        hipMalloc(&x.gk, ngroupp * sizeof(int)) != hipSuccess || hipMalloc(&x.wk, ngroupp * sizeof(float)) != hipSuccess ||
-        hip_memset_now(x.alloc, IS_GUARD_BYTE, x.bytes() + 2 * IS_GUARD) != hipSuccess || hip_memset_now(x.alloc + IS_GUARD, 0, x.bytes()) != hipSuccess) {
+    if (x.alloc.open(x.bytes()) != hipSuccess || hipMalloc(&x.bk, (size_t)ndm * ngroupp * sizeof(int)) != hipSuccess ||
+        hipMalloc(&x.gk, ngroupp * sizeof(int)) != hipSuccess || hipMalloc(&x.wk, ngroupp * sizeof(float)) != hipSuccess) {
         (void)hipGetLastError();
         imsearch_free(x);
         x = ImsearchContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Imsearch: cannot allocate %.3g MB of state", bytes * 1e-6);
     }
-    x.state = (float*)(x.alloc + IS_GUARD);
+    x.state = (float*)x.alloc.data();
     x.U = x.state + x.state_words();
     x.Z = x.U + x.u_words();
     x.live = true;
@@ -239,22 +235,7 @@ int xengImsearchGetBaseline(float* c, float* m, float* var) {
     return XENG_STATUS_SUCCESS;
 }
 
-int xengImsearchCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "ImsearchCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_ismu);
-    ImsearchContext& x = g_is;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Imsearch: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * IS_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.alloc, IS_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + IS_GUARD, x.alloc + IS_GUARD + x.bytes(), IS_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != IS_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengImsearchCheckGuards(int* intact) { return beam_context_check_guards(g_ismu, g_is, g_is.alloc, "Imsearch", intact); }
 int xengImsearchMark(unsigned long long* ticket) { return beam_context_mark(g_ismu, g_is, "Imsearch", ticket); }
 int xengImsearchWait(unsigned long long ticket) { return beam_context_wait(g_ismu, g_is, "Imsearch", ticket); }
 int xengImsearchTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_ismu, g_is, "Imsearch", ticket, done); }

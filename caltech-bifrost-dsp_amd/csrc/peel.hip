@@ -1,6 +1,5 @@
-// Host side of the peeling stage (UpchanPeel; peel_kernels.h): a process-global context of its own, beside the Beamform, Upchan*,
-// Dedisp, Pulse, Fold, Period, Cdedisp, Image, Gaincal, Calapply and Clean contexts, whose kernels run on the beamformer's stream
-// (STREAM_BEAM) and tick its clock, so that rings declared 'beam' and their span stamps cover it unchanged.
+// Host side of the peeling stage (UpchanPeel; peel_kernels.h): a process-global context of its own on the beamformer's stream
+// (BeamStreamContext, xeng_common.h).
 #include <cmath>
 #include <mutex>
 #include <vector>
@@ -14,7 +13,7 @@ static_assert(XENG_PEEL_MAX_NDIR == PL_D && XENG_PEEL_MAX_NSTAND == PL_MAX_NSTAN
 
 struct PeelContext : BeamStreamContext {
     int nstand = 0, nfine = 0, ndir = 0;
-    uint8_t* alloc = nullptr;           // PL_GUARD bytes of PL_GUARD_BYTE, the state, PL_GUARD bytes of PL_GUARD_BYTE
+    GuardedState alloc;                 // the state between its guard bands (xengPeelCheckGuards)
     double* freq = nullptr;             // f64[nfine], inside alloc
     double* tau = nullptr;              // f64[ndir][nstand], behind it
     float2* a = nullptr;                // cf32[nfine][ndir][nstand]: the steering factors (peel_steer_kernel)
@@ -33,15 +32,13 @@ struct PeelContext : BeamStreamContext {
     }
     int ntile() const { return (nstand + PS_T - 1) / PS_T; }
 };
-constexpr size_t PL_GUARD = 64 << 10;   // guard bands around the state (xengPeelCheckGuards)
-constexpr int PL_GUARD_BYTE = 0xA5;
 static std::mutex g_plmu;
 static PeelContext g_pl;
 
 static int peel_destroy_locked() {
     if (!g_pl.live) return XENG_STATUS_SUCCESS;
     beam_context_close(g_pl);
-    if (g_pl.alloc) (void)hipFree(g_pl.alloc);
+    g_pl.alloc.free();
     g_pl = PeelContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -73,15 +70,12 @@ int xengPeelInitialize(int gpu, int nstand, int nfine, int ndir) {
         x = PeelContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Peel: %d stands need %zu bytes of LDS, which the device refuses", nstand, lds);
     }
-    if (hipMalloc(&x.alloc, x.state_bytes() + 2 * PL_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc, PL_GUARD_BYTE, x.state_bytes() + 2 * PL_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc + PL_GUARD, 0, x.state_bytes()) != hipSuccess) {
+    if (x.alloc.open(x.state_bytes()) != hipSuccess) {
         (void)hipGetLastError();
-        if (x.alloc) (void)hipFree(x.alloc);
         x = PeelContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Peel: cannot allocate %.3g MB of state", (double)nfine * ndir * nstand * 24e-6);
     }
-    x.freq = (double*)(x.alloc + PL_GUARD);
+    x.freq = (double*)x.alloc.data();
     x.tau = x.freq + nfine;
     x.a = (float2*)(x.tau + (size_t)ndir * nstand);
     x.keep_g = x.a + (size_t)nfine * ndir * nstand;
@@ -186,22 +180,7 @@ int xengPeelRun(const void* vis_dev, void* out_dev, void* gains_dev, void* stats
     return XENG_STATUS_SUCCESS;
 }
 
-int xengPeelCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "PeelCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_plmu);
-    PeelContext& x = g_pl;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Peel: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * PL_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.alloc, PL_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + PL_GUARD, x.alloc + PL_GUARD + x.state_bytes(), PL_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != PL_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengPeelCheckGuards(int* intact) { return beam_context_check_guards(g_plmu, g_pl, g_pl.alloc, "Peel", intact); }
 int xengPeelMark(unsigned long long* ticket) { return beam_context_mark(g_plmu, g_pl, "Peel", ticket); }
 int xengPeelWait(unsigned long long ticket) { return beam_context_wait(g_plmu, g_pl, "Peel", ticket); }
 int xengPeelTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_plmu, g_pl, "Peel", ticket, done); }

@@ -1,6 +1,5 @@
-// Host side of the FFT periodicity search (BeamPeriodSearch; period_kernels.h): a process-global context of its own, beside the
-// Beamform, Upchan*, Dedisp, Pulse and Fold contexts, whose kernels run on the beamformer's stream (STREAM_BEAM) and tick its
-// clock, so that rings declared 'beam' and their span stamps cover them unchanged.
+// Host side of the FFT periodicity search (BeamPeriodSearch; period_kernels.h): a process-global context of its own on the
+// beamformer's stream (BeamStreamContext, xeng_common.h).
 #include <cmath>
 #include <mutex>
 #include <vector>
@@ -14,7 +13,7 @@ struct PeriodContext : BeamStreamContext {
     int npair = 0, ndm = 0, nwin = 0, nprod = 0, nt = 0, nstack = 0, nlevel = 0, nwhite = 0, kmin = 0;
     int nser = 0;                       // npair * ndm
     int L = 0, lb = 0;                  // log2 (nt / 2), log2 nwhite
-    uint8_t* alloc = nullptr;           // PR_GUARD bytes of PR_GUARD_BYTE, the state, PR_GUARD bytes of PR_GUARD_BYTE
+    GuardedState alloc;                 // the state between its guard bands (xengPeriodCheckGuards)
     float* tbuf = nullptr;              // f32[nser][nt], inside alloc
     float* A = nullptr;                 // f32[nser][nt/2], behind it
     float2* tw = nullptr;               // float2[nt/2]
@@ -31,15 +30,13 @@ struct PeriodContext : BeamStreamContext {
         return ((size_t)nser * nt + (size_t)nser * n) * sizeof(float) + n * sizeof(float2) + n / 2 * sizeof(float2) + n / nwhite * sizeof(float) + n;
     }
 };
-constexpr size_t PR_GUARD = 64 << 10;   // guard bands around the state (xengPeriodCheckGuards)
-constexpr int PR_GUARD_BYTE = 0xA5;
 static std::mutex g_prmu;
 static PeriodContext g_pr;
 
 static int period_destroy_locked() {
     if (!g_pr.live) return XENG_STATUS_SUCCESS;
     beam_context_close(g_pr);
-    if (g_pr.alloc) (void)hipFree(g_pr.alloc);
+    g_pr.alloc.free();
     g_pr = PeriodContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -117,15 +114,12 @@ int xengPeriodInitialize(int gpu, int npair, int ndm, int nwin, int nprod, int n
         for (int b = 0; b < x.L; b++) k |= ((2 * t >> b) & 1) << (x.L - 1 - b);
         tw[(size_t)n + t] = tw[k];
     }
-    if (hipMalloc(&x.alloc, x.state_bytes() + 2 * PR_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc, PR_GUARD_BYTE, x.state_bytes() + 2 * PR_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc + PR_GUARD, 0, x.state_bytes()) != hipSuccess) {
+    if (x.alloc.open(x.state_bytes()) != hipSuccess) {
         (void)hipGetLastError();
-        if (x.alloc) (void)hipFree(x.alloc);
         x = PeriodContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Period: cannot allocate %.3g MB of state", (double)npair * ndm * nt * 6e-6);
     }
-    x.tbuf = (float*)(x.alloc + PR_GUARD);
+    x.tbuf = (float*)x.alloc.data();
     x.A = x.tbuf + (size_t)x.nser * nt;
     x.tw = (float2*)(x.A + (size_t)x.nser * n);
     x.twu = x.tw + n;
@@ -133,7 +127,7 @@ int xengPeriodInitialize(int gpu, int npair, int ndm, int nwin, int nprod, int n
     x.keep = (uint8_t*)(x.cnt + n / nwhite);
     if (hipMemcpy(x.tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess || period_upload_mask(x, nullptr) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(x.alloc);
+        x.alloc.free();
         x = PeriodContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Period: cannot upload the twiddles and the mask");
     }
@@ -227,22 +221,7 @@ int xengPeriodGetSpectrum(float* A_host, int* nseg) {
     return XENG_STATUS_SUCCESS;
 }
 
-int xengPeriodCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "PeriodCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_prmu);
-    PeriodContext& x = g_pr;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Period: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * PR_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.alloc, PR_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + PR_GUARD, x.alloc + PR_GUARD + x.state_bytes(), PR_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != PR_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengPeriodCheckGuards(int* intact) { return beam_context_check_guards(g_prmu, g_pr, g_pr.alloc, "Period", intact); }
 int xengPeriodMark(unsigned long long* ticket) { return beam_context_mark(g_prmu, g_pr, "Period", ticket); }
 int xengPeriodWait(unsigned long long ticket) { return beam_context_wait(g_prmu, g_pr, "Period", ticket); }
 int xengPeriodTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_prmu, g_pr, "Period", ticket, done); }

@@ -1,6 +1,5 @@
-// Host side of the component subtraction (UpchanPredict; predict_kernels.h): a process-global context of its own, beside the Beamform,
-// Upchan*, Dedisp, Pulse, Fold, Period, Cdedisp, Image, Gaincal, Calapply, Peel, Clean and Flag contexts, whose kernels run on the
-// beamformer's stream (STREAM_BEAM) and tick its clock, so that rings declared 'beam' and their span stamps cover it unchanged.
+// Host side of the component subtraction (UpchanPredict; predict_kernels.h): a process-global context of its own on the
+// beamformer's stream (BeamStreamContext, xeng_common.h).
 #include <cmath>
 #include <mutex>
 #include <vector>
@@ -15,7 +14,7 @@ static_assert(XENG_PREDICT_MAX_NCOMP == PR_MAX_NCOMP && XENG_PREDICT_MAX_NSTAND 
 struct PredictContext : BeamStreamContext {
     int nstand = 0, nfine = 0, nfavg = 0, ndir = 0, ncomp_max = 0, cross = 0, mode = XENG_PREDICT_SUBTRACT;
     long long nfilled = 0;              // filled records of the list in force
-    uint8_t* alloc = nullptr;           // PR_GUARD bytes of PR_GUARD_BYTE, the state, PR_GUARD bytes of PR_GUARD_BYTE
+    GuardedState alloc;                 // the state between its guard bands (xengPredictCheckGuards)
     pr_record* rec = nullptr;           // [ngroup][ncomp_max], inside alloc (first: 32-byte records on a 256-byte boundary)
     double* freq = nullptr;             // f64[nfine], behind it
     double* tau = nullptr;              // f64[ndir][nstand]
@@ -30,15 +29,13 @@ struct PredictContext : BeamStreamContext {
     }
     int ntile() const { return (nstand + PR_T - 1) / PR_T; }
 };
-constexpr size_t PR_GUARD = 64 << 10;   // guard bands around the state (xengPredictCheckGuards)
-constexpr int PR_GUARD_BYTE = 0xA5;
 static std::mutex g_prmu;
 static PredictContext g_pr;
 
 static int predict_destroy_locked() {
     if (!g_pr.live) return XENG_STATUS_SUCCESS;
     beam_context_close(g_pr);
-    if (g_pr.alloc) (void)hipFree(g_pr.alloc);
+    g_pr.alloc.free();
     g_pr = PredictContext();
     return XENG_STATUS_SUCCESS;
 }
@@ -65,16 +62,14 @@ int xengPredictInitialize(int gpu, int nstand, int nfine, int nfavg, int ndir, i
     int rc = beam_context_open(x, gpu);
     if (rc) return rc;
     x.nstand = nstand; x.nfine = nfine; x.nfavg = nfavg; x.ndir = ndir; x.ncomp_max = ncomp_max; x.cross = cross;
-    // every byte 0xFF: pixel -1 in every record; then the tables and nrec 0
-    if (hipMalloc(&x.alloc, x.state_bytes() + 2 * PR_GUARD) != hipSuccess || hip_memset_now(x.alloc, PR_GUARD_BYTE, x.state_bytes() + 2 * PR_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc + PR_GUARD, 0xFF, x.nrecords() * sizeof(pr_record)) != hipSuccess ||
-        hip_memset_now(x.alloc + PR_GUARD + x.nrecords() * sizeof(pr_record), 0, x.state_bytes() - x.nrecords() * sizeof(pr_record)) != hipSuccess) {
+    // every byte 0xFF: pixel -1 in every record; the tables and nrec behind them stay 0
+    if (x.alloc.open(x.state_bytes()) != hipSuccess || hip_memset_now(x.alloc.data(), 0xFF, x.nrecords() * sizeof(pr_record)) != hipSuccess) {
         (void)hipGetLastError();
-        if (x.alloc) (void)hipFree(x.alloc);
+        x.alloc.free();
         x = PredictContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Predict: cannot allocate %.3g MB of state", ((double)ndir * nstand * 8 + (double)(nfine / nfavg) * ncomp_max * 32) * 1e-6);
     }
-    x.rec = (pr_record*)(x.alloc + PR_GUARD);
+    x.rec = (pr_record*)x.alloc.data();
     x.freq = (double*)(x.rec + x.nrecords());
     x.tau = x.freq + nfine;
     x.nrec = (int*)(x.tau + (size_t)ndir * nstand);
@@ -178,22 +173,7 @@ int xengPredictRun(const void* vis_dev, void* out_dev) {
     return XENG_STATUS_SUCCESS;
 }
 
-int xengPredictCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "PredictCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_prmu);
-    PredictContext& x = g_pr;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Predict: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * PR_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.alloc, PR_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + PR_GUARD, x.alloc + PR_GUARD + x.state_bytes(), PR_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != PR_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengPredictCheckGuards(int* intact) { return beam_context_check_guards(g_prmu, g_pr, g_pr.alloc, "Predict", intact); }
 int xengPredictMark(unsigned long long* ticket) { return beam_context_mark(g_prmu, g_pr, "Predict", ticket); }
 int xengPredictWait(unsigned long long ticket) { return beam_context_wait(g_prmu, g_pr, "Predict", ticket); }
 int xengPredictTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_prmu, g_pr, "Predict", ticket, done); }

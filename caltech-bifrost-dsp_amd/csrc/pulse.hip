@@ -1,6 +1,5 @@
-// Host side of the boxcar single-pulse search (BeamPulseSearch; pulse_kernels.h): a process-global context of its own, beside
-// the Beamform, Upchan* and Dedisp contexts, whose kernel runs on the beamformer's stream (STREAM_BEAM) and ticks its clock, so
-// that rings declared 'beam' and their span stamps cover it unchanged.
+// Host side of the boxcar single-pulse search (BeamPulseSearch; pulse_kernels.h): a process-global context of its own on the
+// beamformer's stream (BeamStreamContext, xeng_common.h).
 #include <cmath>
 #include <mutex>
 #include <vector>
@@ -14,7 +13,7 @@ struct PulseContext : BeamStreamContext {
     int npair = 0, ndm = 0, nwin = 0, nprod = 0, nwidth = 0, nstat = 0;
     int nser = 0;                       // npair * ndm
     int T = 0, L = 0;                   // windows a boxcar reaches back before a call: 2^(nwidth-1) - 1; slots of the y ring: T + nwin
-    uint8_t* alloc = nullptr;           // PS_GUARD bytes of PS_GUARD_BYTE, the state, the y ring, PS_GUARD bytes of PS_GUARD_BYTE
+    GuardedState alloc;                 // the state and the y ring between their guard bands (xengPulseCheckGuards)
     float* state = nullptr;             // f32[PS_NSTATE][nser], inside alloc
     float* tail = nullptr;              // f32[L][nser], behind the state
     float* rho = nullptr;               // f32[nwidth]
@@ -23,8 +22,6 @@ struct PulseContext : BeamStreamContext {
 
     size_t state_bytes() const { return (size_t)(PS_NSTATE + L) * nser * sizeof(float); }
 };
-constexpr size_t PS_GUARD = 64 << 10;   // guard bands around the state (xengPulseCheckGuards)
-constexpr int PS_GUARD_BYTE = 0xA5;
 constexpr int PS_LDS_ROWS = 256;        // rows of 64 floats in the 64 KiB a work-group may take
 static std::mutex g_psmu;
 static PulseContext g_ps;
@@ -32,7 +29,7 @@ static PulseContext g_ps;
 static int pulse_destroy_locked() {
     if (!g_ps.live) return XENG_STATUS_SUCCESS;
     beam_context_close(g_ps);
-    if (g_ps.alloc) (void)hipFree(g_ps.alloc);
+    g_ps.alloc.free();
     if (g_ps.rho) (void)hipFree(g_ps.rho);
     g_ps = PulseContext();
     return XENG_STATUS_SUCCESS;
@@ -76,17 +73,15 @@ int xengPulseInitialize(int gpu, int npair, int ndm, int nwin, int nprod, int nw
     x.r_nstat = 1.0f / (float)nstat;
     float rho[8];
     for (int iw = 0; iw < nwidth; iw++) rho[iw] = (float)std::ldexp(iw & 1 ? 0.70710678118654752440 : 1.0, -(iw >> 1));    // 2^(-iw/2)
-    if (hipMalloc(&x.alloc, x.state_bytes() + 2 * PS_GUARD) != hipSuccess || hipMalloc(&x.rho, sizeof(rho)) != hipSuccess ||
-        hip_memset_now(x.alloc, PS_GUARD_BYTE, x.state_bytes() + 2 * PS_GUARD) != hipSuccess ||
-        hip_memset_now(x.alloc + PS_GUARD, 0, x.state_bytes()) != hipSuccess ||
+    if (x.alloc.open(x.state_bytes()) != hipSuccess || hipMalloc(&x.rho, sizeof(rho)) != hipSuccess ||
         hipMemcpy(x.rho, rho, sizeof(rho), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
-        if (x.alloc) (void)hipFree(x.alloc);
+        x.alloc.free();
         if (x.rho) (void)hipFree(x.rho);
         x = PulseContext();
         XENG_FAIL(XENG_STATUS_DEVICE_ERROR, "Pulse: cannot allocate %.3g MB of state", (double)(PS_NSTATE + T + nwin) * npair * ndm * 4e-6);
     }
-    x.state = (float*)(x.alloc + PS_GUARD);
+    x.state = (float*)x.alloc.data();
     x.tail = x.state + (size_t)PS_NSTATE * x.nser;
     x.live = true;
     return XENG_STATUS_SUCCESS;
@@ -144,22 +139,7 @@ int xengPulseGetBaseline(float* c, float* m, float* var) {
     return XENG_STATUS_SUCCESS;
 }
 
-int xengPulseCheckGuards(int* intact) {
-    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "PulseCheckGuards: null result");
-    std::lock_guard<std::mutex> lk(g_psmu);
-    PulseContext& x = g_ps;
-    if (!x.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "Pulse: not initialized");
-    XENG_HIP(hipSetDevice(x.gpu));
-    XENG_HIP(hipStreamSynchronize(x.stream));
-    std::vector<uint8_t> g(2 * PS_GUARD);
-    XENG_HIP(hipMemcpy(g.data(), x.alloc, PS_GUARD, hipMemcpyDeviceToHost));
-    XENG_HIP(hipMemcpy(g.data() + PS_GUARD, x.alloc + PS_GUARD + x.state_bytes(), PS_GUARD, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (uint8_t b : g)
-        if (b != PS_GUARD_BYTE) *intact = 0;
-    return XENG_STATUS_SUCCESS;
-}
-
+int xengPulseCheckGuards(int* intact) { return beam_context_check_guards(g_psmu, g_ps, g_ps.alloc, "Pulse", intact); }
 int xengPulseMark(unsigned long long* ticket) { return beam_context_mark(g_psmu, g_ps, "Pulse", ticket); }
 int xengPulseWait(unsigned long long ticket) { return beam_context_wait(g_psmu, g_ps, "Pulse", ticket); }
 int xengPulseTicketDone(unsigned long long ticket, int* done) { return beam_context_ticket_done(g_psmu, g_ps, "Pulse", ticket, done); }

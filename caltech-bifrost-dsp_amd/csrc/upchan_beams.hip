@@ -1,6 +1,5 @@
 // Host side of the fine-channel power beams from live beams (UpchanSumBeams; upchan_beams_kernels.h): a process-global context
-// of its own, beside the Beamform, Upchan and UpchanCorr contexts, whose kernels run on the beamformer's stream (STREAM_BEAM)
-// and tick its clock, so that rings declared 'beam' and their span stamps cover them unchanged.
+// of its own on the beamformer's stream (BeamStreamContext, xeng_common.h).
 #include <mutex>
 
 #include "upchan_beams_kernels.h"

@@ -1,6 +1,5 @@
-// Host side of the upchannelised correlator (UpchanCorr; upchan_corr_kernels.h): a process-global context of its own, beside
-// the Upchan and Beamform contexts, whose kernels run on the beamformer's stream (STREAM_BEAM) and tick its clock, so that
-// rings declared 'beam' and their span stamps cover them unchanged.
+// Host side of the upchannelised correlator (UpchanCorr; upchan_corr_kernels.h): a process-global context of its own on the
+// beamformer's stream (BeamStreamContext, xeng_common.h).
 #include <mutex>
 
 #include "upchan_corr_kernels.h"

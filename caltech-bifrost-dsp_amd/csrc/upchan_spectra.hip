@@ -1,6 +1,5 @@
 // Host side of the per-input fine-channel spectra (UpchanSpectra; upchan_spectra_kernels.h): a process-global context of its
-// own, beside the Beamform, Upchan, UpchanCorr and UpchanSumBeams contexts, whose kernel runs on the beamformer's stream
-// (STREAM_BEAM) and ticks its clock, so that rings declared 'beam' and their span stamps cover it unchanged.
+// own on the beamformer's stream (BeamStreamContext, xeng_common.h).
 #include <mutex>
 
 #include "upchan_pfb.h"

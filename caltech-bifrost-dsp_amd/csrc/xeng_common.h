@@ -89,9 +89,10 @@ struct TicketRing {
     void destroy();                                                 // after the stream has been synchronised and its clock forgotten
 };
 // What every engine beside the beamformer on its stream has (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp,
-// Pulse, Fold): each
-// derives its process-global context from this and keeps a mutex of its own.  Its kernels run on STREAM_BEAM and tick that
-// clock, so that rings declared 'beam' and their span stamps cover them unchanged.
+// Pulse, Fold, Period, Ffa, Cdedisp, Cdlong, Image, Gaincal, Calapply, Peel, Clean, Flag, Predict, Imsearch; the table
+// ENGINES of ffi.py lists the same nineteen): each derives its process-global context from this and keeps a mutex of its
+// own.  Its kernels run on STREAM_BEAM and tick that clock, so that rings declared 'beam' and their span stamps cover
+// them unchanged.
 struct BeamStreamContext {
     bool live = false;
     int gpu = 0;
@@ -110,6 +111,24 @@ int beam_context_mark(std::mutex& mu, BeamStreamContext& c, const char* who, uns
 int beam_context_wait(std::mutex& mu, const BeamStreamContext& c, const char* who, unsigned long long ticket);
 int beam_context_ticket_done(std::mutex& mu, const BeamStreamContext& c, const char* who, unsigned long long ticket, int* done);
 int beam_context_sync(std::mutex& mu, const BeamStreamContext& c, const char* who);
+// The state an engine keeps on the device between calls, in one allocation with a guard band on either side: GUARD bytes
+// of PATTERN, the state, GUARD bytes of PATTERN.  A kernel that writes outside the state damages a band, and
+// xeng<who>CheckGuards tells.  Plain data, as the contexts that hold it: reset by assignment, never freed by a destructor.
+struct GuardedState {
+    static constexpr size_t GUARD = 64 << 10;
+    static constexpr int PATTERN = 0xA5;
+    // Both bands filled and the state zeroed, complete on return (hip_memset_now); on failure nothing is left allocated.
+    hipError_t open(size_t bytes);
+    uint8_t* data() const { return base ? base + GUARD : nullptr; }     // the hipMalloc base + 64 KiB
+    size_t bytes() const { return n; }                                  // as opened: what the check measures by
+    void free();                                                        // idempotent
+private:
+    uint8_t* base = nullptr;
+    size_t n = 0;
+};
+// xeng<who>CheckGuards: as the four above (a null pointer refused first, then the lock, then the missing context); the stream
+// is synchronised before both bands are read back and compared byte by byte.
+int beam_context_check_guards(std::mutex& mu, const BeamStreamContext& c, const GuardedState& s, const char* who, int* intact);
 // X-engine side of a stamp (xcorr.hip)
 void xgpu_pending_launch(unsigned long long* seq, unsigned long long* epoch, unsigned long long* nlaunch, unsigned long long* ctx);
 int xgpu_pending_poll(unsigned long long seq, unsigned long long epoch, bool* done, bool* launched, hipEvent_t* ev, int* gpu);

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <mutex>
 #include <utility>
+#include <vector>
 
 #include "xeng_common.h"
 
@@ -416,6 +417,39 @@ int beam_context_sync(std::mutex& mu, const BeamStreamContext& c, const char* wh
     if (!c.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "%s: not initialized", who);
     XENG_HIP(hipSetDevice(c.gpu));
     XENG_HIP(hipStreamSynchronize(c.stream));
+    return XENG_STATUS_SUCCESS;
+}
+
+hipError_t GuardedState::open(size_t bytes) {
+    hipError_t e = hipMalloc(&base, bytes + 2 * GUARD);
+    if (e != hipSuccess) {
+        base = nullptr;
+        return e;
+    }
+    n = bytes;
+    if ((e = hip_memset_now(base, PATTERN, n + 2 * GUARD)) != hipSuccess || (e = hip_memset_now(data(), 0, n)) != hipSuccess) free();
+    return e;
+}
+
+void GuardedState::free() {
+    if (base) (void)hipFree(base);
+    base = nullptr;
+    n = 0;
+}
+
+int beam_context_check_guards(std::mutex& mu, const BeamStreamContext& c, const GuardedState& s, const char* who, int* intact) {
+    if (!intact) XENG_FAIL(XENG_STATUS_INVALID_ARGUMENT, "%sCheckGuards: null result", who);
+    std::lock_guard<std::mutex> lk(mu);
+    if (!c.live) XENG_FAIL(XENG_STATUS_INVALID_STATE, "%s: not initialized", who);
+    XENG_HIP(hipSetDevice(c.gpu));
+    XENG_HIP(hipStreamSynchronize(c.stream));
+    constexpr size_t G = GuardedState::GUARD;
+    std::vector<uint8_t> g(2 * G);
+    XENG_HIP(hipMemcpy(g.data(), s.data() - G, G, hipMemcpyDeviceToHost));
+    XENG_HIP(hipMemcpy(g.data() + G, s.data() + s.bytes(), G, hipMemcpyDeviceToHost));
+    *intact = 1;
+    for (uint8_t b : g)
+        if (b != GuardedState::PATTERN) *intact = 0;
     return XENG_STATUS_SUCCESS;
 }
 

@@ -90,92 +90,62 @@ SYMBOLS = {
     "xengBeamformSetProfiling": [_i], "xengBeamformGetTimes": [ctypes.POINTER(ctypes.c_double), _pi],
     "xengBeamformGetRouteInfo": [_pi, _pi, _pi],
     "xengUpchanInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengUpchanInitializeDualPol": [_i, _i, _i, _i, _i, _i, _i], "xengUpchanRun": [_vp, _vp, _vp, _ll], "xengUpchanRunParts": [_vp, _i, _vp, _vp, _vp, _ll],
-    "xengUpchanMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanWait": [ctypes.c_ulonglong], "xengUpchanTicketDone": [ctypes.c_ulonglong, _pi],
-    "xengUpchanSync": [], "xengUpchanDestroy": [], "xengUpchanSetPfb": [_i, ctypes.POINTER(ctypes.c_float)], "xengUpchanReset": [],
+    # (the engines on the beamformer's stream: their Mark / Wait / TicketDone / Sync / Destroy / CheckGuards come from ENGINES below)
+    "xengUpchanSetPfb": [_i, ctypes.POINTER(ctypes.c_float)], "xengUpchanReset": [],
     "xengUpchanCorrInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengUpchanCorrGetInfo": [_pi, _pi],
     "xengUpchanCorrAccumulate": [_vp], "xengUpchanCorrAccumulateParts": [_vp, _i, _vp], "xengUpchanCorrDump": [_vp], "xengUpchanCorrReset": [],
-    "xengUpchanCorrMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanCorrWait": [ctypes.c_ulonglong], "xengUpchanCorrTicketDone": [ctypes.c_ulonglong, _pi],
-    "xengUpchanCorrSync": [], "xengUpchanCorrDestroy": [], "xengUpchanCorrSetPfb": [_i, ctypes.POINTER(ctypes.c_float)],
+    "xengUpchanCorrSetPfb": [_i, ctypes.POINTER(ctypes.c_float)],
     "xengUpchanCorrPrime": [_vp], "xengUpchanCorrPrimeParts": [_vp, _i, _vp],
     "xengUpchanSumBeamsInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengUpchanSumBeamsGetInfo": [_pi, _pi, _pi],
     "xengUpchanSumBeamsRun": [_vp, _vp], "xengUpchanSumBeamsSetPfb": [_i, ctypes.POINTER(ctypes.c_float)], "xengUpchanSumBeamsPrime": [_vp],
-    "xengUpchanSumBeamsReset": [], "xengUpchanSumBeamsMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanSumBeamsWait": [ctypes.c_ulonglong],
-    "xengUpchanSumBeamsTicketDone": [ctypes.c_ulonglong, _pi], "xengUpchanSumBeamsSync": [], "xengUpchanSumBeamsDestroy": [],
+    "xengUpchanSumBeamsReset": [],
     "xengUpchanSpectraInitialize": [_i, _i, _i, _i, _i, _i], "xengUpchanSpectraGetInfo": [_pi, _pi, _pi],
     "xengUpchanSpectraRun": [_vp, _vp], "xengUpchanSpectraRunParts": [_vp, _i, _vp, _vp], "xengUpchanSpectraSetPfb": [_i, ctypes.POINTER(ctypes.c_float)],
     "xengUpchanSpectraPrime": [_vp], "xengUpchanSpectraPrimeParts": [_vp, _i, _vp], "xengUpchanSpectraReset": [],
-    "xengUpchanSpectraMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengUpchanSpectraWait": [ctypes.c_ulonglong],
-    "xengUpchanSpectraTicketDone": [ctypes.c_ulonglong, _pi], "xengUpchanSpectraSync": [], "xengUpchanSpectraDestroy": [],
     "xengDedispInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengDedispSetDelays": [_pi], "xengDedispSetWeights": [ctypes.POINTER(ctypes.c_float)],
     "xengDedispRun": [_vp, _i, _vp], "xengDedispReset": [], "xengDedispGetInfo": [_pi, ctypes.POINTER(ctypes.c_longlong)],
-    "xengDedispMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengDedispWait": [ctypes.c_ulonglong], "xengDedispTicketDone": [ctypes.c_ulonglong, _pi],
-    "xengDedispSync": [], "xengDedispDestroy": [], "xengDedispCheckGuards": [_pi],
     "xengPulseInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengPulseRun": [_vp, _i, _vp], "xengPulseReset": [],
     "xengPulseGetInfo": [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)],
     "xengPulseGetBaseline": [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)],
-    "xengPulseCheckGuards": [_pi], "xengPulseMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengPulseWait": [ctypes.c_ulonglong],
-    "xengPulseTicketDone": [ctypes.c_ulonglong, _pi], "xengPulseSync": [], "xengPulseDestroy": [],
     "xengFoldInitialize": [_i, _i, _i, _i, _i, _i],
     "xengFoldSetPhase": [ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong), _pll, ctypes.POINTER(ctypes.c_ubyte), _ll],
     "xengFoldSetRotations": [_pi], "xengFoldSetWeights": [ctypes.POINTER(ctypes.c_float)], "xengFoldRun": [_vp, _i],
     "xengFoldDump": [_vp, ctypes.POINTER(ctypes.c_uint), _i, _i, _i], "xengFoldReset": [], "xengFoldGetInfo": [_pll, _pll],
-    "xengFoldCheckGuards": [_pi], "xengFoldMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengFoldWait": [ctypes.c_ulonglong],
-    "xengFoldTicketDone": [ctypes.c_ulonglong, _pi], "xengFoldSync": [], "xengFoldDestroy": [],
     "xengPeriodInitialize": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i], "xengPeriodSetMask": [ctypes.POINTER(ctypes.c_ubyte)],
     "xengPeriodRun": [_vp, _i, _vp, _pi], "xengPeriodReset": [], "xengPeriodGetInfo": [_pll, _pi, _pll],
-    "xengPeriodGetSpectrum": [ctypes.POINTER(ctypes.c_float), _pi], "xengPeriodCheckGuards": [_pi],
-    "xengPeriodMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengPeriodWait": [ctypes.c_ulonglong],
-    "xengPeriodTicketDone": [ctypes.c_ulonglong, _pi], "xengPeriodSync": [], "xengPeriodDestroy": [],
+    "xengPeriodGetSpectrum": [ctypes.POINTER(ctypes.c_float), _pi],
     "xengFfaInitialize": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i], "xengFfaRun": [_vp, _i, _vp, _pi], "xengFfaReset": [],
-    "xengFfaGetInfo": [_pll, _pll], "xengFfaGetStats": [ctypes.POINTER(ctypes.c_float)], "xengFfaCheckGuards": [_pi],
-    "xengFfaMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengFfaWait": [ctypes.c_ulonglong],
-    "xengFfaTicketDone": [ctypes.c_ulonglong, _pi], "xengFfaSync": [], "xengFfaDestroy": [],
+    "xengFfaGetInfo": [_pll, _pll], "xengFfaGetStats": [ctypes.POINTER(ctypes.c_float)],
     "xengCdedispInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdedispSetChirp": [ctypes.POINTER(ctypes.c_float)],
-    "xengCdedispRun": [_vp, _vp, _pi], "xengCdedispReset": [], "xengCdedispGetInfo": [_pi, _pi, _pll, _pll], "xengCdedispCheckGuards": [_pi],
-    "xengCdedispMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCdedispWait": [ctypes.c_ulonglong],
-    "xengCdedispTicketDone": [ctypes.c_ulonglong, _pi], "xengCdedispSync": [], "xengCdedispDestroy": [],
+    "xengCdedispRun": [_vp, _vp, _pi], "xengCdedispReset": [], "xengCdedispGetInfo": [_pi, _pi, _pll, _pll],
     "xengCdlongInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdlongSetChirp": [_i, ctypes.POINTER(ctypes.c_float)],
-    "xengCdlongRun": [_vp, _vp, _pi], "xengCdlongReset": [], "xengCdlongGetInfo": [_pi, _pi, _pll, _pll], "xengCdlongCheckGuards": [_pi],
-    "xengCdlongMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCdlongWait": [ctypes.c_ulonglong],
-    "xengCdlongTicketDone": [ctypes.c_ulonglong, _pi], "xengCdlongSync": [], "xengCdlongDestroy": [],
+    "xengCdlongRun": [_vp, _vp, _pi], "xengCdlongReset": [], "xengCdlongGetInfo": [_pi, _pi, _pll, _pll],
     "xengImageInitialize": [_i, _i, _i, _i, _i], "xengImageGetInfo": [_pi, _pi, _pi, ctypes.POINTER(ctypes.c_double)],
     "xengImageSetGeometry": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], "xengImageSetWeights": [ctypes.POINTER(ctypes.c_float), _i],
-    "xengImageRun": [_vp, _vp], "xengImageCheckGuards": [_pi], "xengImageMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengImageWait": [ctypes.c_ulonglong],
-    "xengImageTicketDone": [ctypes.c_ulonglong, _pi], "xengImageSync": [], "xengImageDestroy": [],
+    "xengImageRun": [_vp, _vp],
     "xengGaincalInitialize": [_i, _i, _i, _i], "xengGaincalGetInfo": [_pi, _pi, ctypes.POINTER(ctypes.c_double), _pi],
     "xengGaincalSetModel": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float)],
     "xengGaincalSetWeights": [ctypes.POINTER(ctypes.c_float), _i], "xengGaincalSetSolver": [_i, ctypes.c_double], "xengGaincalRun": [_vp, _vp, _vp, _i],
-    "xengGaincalCheckGuards": [_pi], "xengGaincalMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengGaincalWait": [ctypes.c_ulonglong],
-    "xengGaincalTicketDone": [ctypes.c_ulonglong, _pi], "xengGaincalSync": [], "xengGaincalDestroy": [],
     "xengCalapplyInitialize": [_i, _i, _i, _i], "xengCalapplyGetInfo": [_pi, _pi, _pi, _pll],
     "xengCalapplySetModel": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float)],
-    "xengCalapplySetFactors": [_vp], "xengCalapplyRun": [_vp, _vp], "xengCalapplyCheckGuards": [_pi],
-    "xengCalapplyMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCalapplyWait": [ctypes.c_ulonglong],
-    "xengCalapplyTicketDone": [ctypes.c_ulonglong, _pi], "xengCalapplySync": [], "xengCalapplyDestroy": [],
+    "xengCalapplySetFactors": [_vp], "xengCalapplyRun": [_vp, _vp],
     "xengPeelInitialize": [_i, _i, _i, _i], "xengPeelGetInfo": [_pi, _pi, ctypes.POINTER(ctypes.c_double), _pi, _pll],
     "xengPeelSetModel": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float)],
     "xengPeelSetWeights": [ctypes.POINTER(ctypes.c_float), _i], "xengPeelSetSolver": [_i, ctypes.c_double], "xengPeelRun": [_vp, _vp, _vp, _vp, _i],
-    "xengPeelCheckGuards": [_pi], "xengPeelMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengPeelWait": [ctypes.c_ulonglong],
-    "xengPeelTicketDone": [ctypes.c_ulonglong, _pi], "xengPeelSync": [], "xengPeelDestroy": [],
     "xengCleanInitialize": [_i, _i, _i, _i, _i, _i], "xengCleanGetInfo": [_pi, _pi, _pll, _pll, _pll, ctypes.POINTER(ctypes.c_double)],
     "xengCleanSetGeometry": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], "xengCleanSetWeights": [ctypes.POINTER(ctypes.c_float), _i],
     "xengCleanSetWindow": [ctypes.POINTER(ctypes.c_ubyte)], "xengCleanSetControl": [_i, ctypes.c_float, ctypes.c_float, ctypes.c_float],
-    "xengCleanRun": [_vp, _vp], "xengCleanCheckGuards": [_pi], "xengCleanMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengCleanWait": [ctypes.c_ulonglong],
-    "xengCleanTicketDone": [ctypes.c_ulonglong, _pi], "xengCleanSync": [], "xengCleanDestroy": [],
+    "xengCleanRun": [_vp, _vp],
     "xengFlagInitialize": [_i, _i, _i], "xengFlagGetInfo": [_pll, _pll, _pll, _pi], "xengFlagSetWeights": [ctypes.POINTER(ctypes.c_float)],
     "xengFlagSetControl": [ctypes.c_double, ctypes.c_double, ctypes.c_double, _i],
     "xengFlagGetControl": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _pi],
-    "xengFlagRun": [_vp, _vp, _vp, _vp], "xengFlagCheckGuards": [_pi], "xengFlagMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengFlagWait": [ctypes.c_ulonglong],
-    "xengFlagTicketDone": [ctypes.c_ulonglong, _pi], "xengFlagSync": [], "xengFlagDestroy": [],
+    "xengFlagRun": [_vp, _vp, _vp, _vp],
     "xengPredictInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengPredictGetInfo": [_pi, _pi, _pi, _pll, _pll, _pll, _pi],
     "xengPredictSetGeometry": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], "xengPredictSetComponents": [_vp], "xengPredictSetMode": [_i],
-    "xengPredictRun": [_vp, _vp], "xengPredictCheckGuards": [_pi], "xengPredictMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengPredictWait": [ctypes.c_ulonglong],
-    "xengPredictTicketDone": [ctypes.c_ulonglong, _pi], "xengPredictSync": [], "xengPredictDestroy": [],
+    "xengPredictRun": [_vp, _vp],
     "xengImsearchInitialize": [_i, _i, _i, _i, _i, _i, _i], "xengImsearchSetDelays": [_pi], "xengImsearchSetWeights": [ctypes.POINTER(ctypes.c_float)],
     "xengImsearchRun": [_vp, _vp], "xengImsearchReset": [], "xengImsearchGetInfo": [_pll, _pi],
     "xengImsearchGetBaseline": [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)],
-    "xengImsearchCheckGuards": [_pi], "xengImsearchMark": [ctypes.POINTER(ctypes.c_ulonglong)], "xengImsearchWait": [ctypes.c_ulonglong],
-    "xengImsearchTicketDone": [ctypes.c_ulonglong, _pi], "xengImsearchSync": [], "xengImsearchDestroy": [],
     "bfXgpuInitialize": [_pa, _pa, _i], "bfXgpuKernel": [_pa, _pa, _i], "bfXgpuCorrelate": [_pa, _pa, _i],
     "bfXgpuGetOrder": [_pa, _pa, _pa], "bfXgpuSubSelect": [_pa, _pa, _pa, _pa, _i, _i],
     "bfXgpuReorder": [_pa, _pa, _pa, _pa], "bfBeamformInitialize": [_i, _i, _i, _i, _i, _i],
@@ -183,6 +153,21 @@ SYMBOLS = {
     "bfBeamformIntegrateSingleBeam": [_pa, _pa, _i, _i],
 }
 STRING_SYMBOLS = ["xengGetLastError", "xengVersion"]
+
+# The engines on the beamformer's stream (csrc/xeng_common.h BeamStreamContext): (C name, HipBackend prefix, has CheckGuards).
+# Every one has xeng<C name>Mark / Wait / TicketDone / Sync / Destroy with the same prototypes, and HipBackend gets
+# <prefix>_mark / _wait / _ticket_done / _sync (and _guards_intact) from its row (backend.py).  The beamformer itself has a
+# native binding and is not listed.
+ENGINES = [("Upchan", "upchan", False), ("UpchanCorr", "upchan_corr", False), ("UpchanSumBeams", "upchan_sum_beams", False),
+           ("UpchanSpectra", "upchan_spectra", False), ("Dedisp", "dedisp", True), ("Pulse", "pulse", True), ("Fold", "fold", True),
+           ("Period", "period", True), ("Ffa", "ffa", True), ("Cdedisp", "cdedisp", True), ("Cdlong", "cdlong", True),
+           ("Image", "image", True), ("Gaincal", "gaincal", True), ("Calapply", "calapply", True), ("Peel", "peel", True),
+           ("Clean", "clean", True), ("Flag", "flag", True), ("Predict", "predict", True), ("Imsearch", "imsearch", True)]
+for _c, _prefix, _guards in ENGINES:
+    SYMBOLS.update({"xeng%sMark" % _c: [ctypes.POINTER(ctypes.c_ulonglong)], "xeng%sWait" % _c: [ctypes.c_ulonglong],
+                    "xeng%sTicketDone" % _c: [ctypes.c_ulonglong, _pi], "xeng%sSync" % _c: [], "xeng%sDestroy" % _c: []})
+    if _guards:
+        SYMBOLS["xeng%sCheckGuards" % _c] = [_pi]
 
 
 def lib():
@@ -217,33 +202,23 @@ def lib():
 # synchronous call, which polls: it is made on the releasing handle.)
 ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xengBeamformTryRunVersioned", "xengBeamformTryRunParts", "xengBeamformTryRunSlabs",
                 "xengBeamformIntegrate", "xengBeamformIntegrateSingleBeam", "xengBeamformPacketizeVoltages", "xengBeamformMark",
-                "xengUpchanRun", "xengUpchanRunParts", "xengUpchanMark", "xengUpchanTicketDone", "xengUpchanCorrAccumulate",
-                "xengUpchanCorrAccumulateParts", "xengUpchanCorrDump", "xengUpchanCorrReset", "xengUpchanCorrMark", "xengUpchanCorrTicketDone", "xengMapAssignI32",
+                "xengUpchanRun", "xengUpchanRunParts", "xengUpchanCorrAccumulate",
+                "xengUpchanCorrAccumulateParts", "xengUpchanCorrDump", "xengUpchanCorrReset", "xengMapAssignI32",
                 "xengUpchanReset", "xengUpchanCorrPrime", "xengUpchanCorrPrimeParts",
-                "xengUpchanSumBeamsRun", "xengUpchanSumBeamsPrime", "xengUpchanSumBeamsReset", "xengUpchanSumBeamsMark", "xengUpchanSumBeamsTicketDone",
+                "xengUpchanSumBeamsRun", "xengUpchanSumBeamsPrime", "xengUpchanSumBeamsReset",
                 "xengUpchanSpectraRun", "xengUpchanSpectraRunParts", "xengUpchanSpectraPrime", "xengUpchanSpectraPrimeParts", "xengUpchanSpectraReset",
-                "xengUpchanSpectraMark", "xengUpchanSpectraTicketDone",
-                "xengDedispRun", "xengDedispReset", "xengDedispMark", "xengDedispTicketDone",
-                "xengPulseRun", "xengPulseReset", "xengPulseMark", "xengPulseTicketDone",
-                "xengFoldRun", "xengFoldReset", "xengFoldMark", "xengFoldTicketDone",
-                "xengPeriodRun", "xengPeriodReset", "xengPeriodMark", "xengPeriodTicketDone",
-                "xengFfaRun", "xengFfaReset", "xengFfaMark", "xengFfaTicketDone",
-                "xengCdedispRun", "xengCdedispReset", "xengCdedispMark", "xengCdedispTicketDone",
-                "xengCdlongRun", "xengCdlongReset", "xengCdlongMark", "xengCdlongTicketDone",
-                "xengImageRun", "xengImageMark", "xengImageTicketDone",
-                "xengGaincalRun", "xengGaincalMark", "xengGaincalTicketDone",
-                "xengCalapplyRun", "xengCalapplyMark", "xengCalapplyTicketDone",
-                "xengPeelRun", "xengPeelMark", "xengPeelTicketDone",
-                "xengCleanRun", "xengCleanMark", "xengCleanTicketDone",
-                "xengFlagRun", "xengFlagMark", "xengFlagTicketDone",
-                "xengPredictRun", "xengPredictMark", "xengPredictTicketDone",
-                "xengImsearchRun", "xengImsearchReset", "xengImsearchMark", "xengImsearchTicketDone",
+                "xengDedispRun", "xengDedispReset", "xengPulseRun", "xengPulseReset", "xengFoldRun", "xengFoldReset", "xengPeriodRun", "xengPeriodReset",
+                "xengFfaRun", "xengFfaReset", "xengCdedispRun", "xengCdedispReset", "xengCdlongRun", "xengCdlongReset",
+                "xengImageRun", "xengGaincalRun", "xengCalapplyRun", "xengPeelRun", "xengCleanRun", "xengFlagRun", "xengPredictRun",
+                "xengImsearchRun", "xengImsearchReset",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
                 # the span rings: bookkeeping calls, and the calls that can wait asked with may_block = 0 first
                 "xengRingBeginSequence", "xengRingEndSequence", "xengRingEndWriting", "xengRingReserve", "xengRingCommit",
                 "xengRingCommitExternal", "xengRingNextSequence", "xengRingAcquire", "xengRingAcquireParts", "xengRingSpanRelease", "xengRingGetInfo",
                 "xengRingOpenReader", "xengRingCloseReader", "xengRingResize",
                 "xengStampNow", "xengStampNowFor", "xengStampDone", "xengGetDevice", "xengSetDevice"]
+for _c, _prefix, _guards in ENGINES:            # an event record and an event query: neither can wait
+    ENQUEUE_ONLY += ["xeng%sMark" % _c, "xeng%sTicketDone" % _c]
 _enq = None
 
 
