@@ -486,6 +486,44 @@ class HipBackend:
         ffi.call("xengPeriodGetSpectrum", A.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(nseg))
         return A, nseg.value
 
+    # ---- FFT periodicity search with long segments (BeamPeriodSearchLong; include/xeng.h "FFT periodicity search with long
+    # segments"): a context of its own, its kernels on the beamformer's stream
+    def plong_initialize(self, gpu, npair, ndm, nwin, nprod, nt, nstack, nlevel, nwhite, kedge):
+        """kedge: the nband + 1 band edges, strictly ascending integers."""
+        e = np.ascontiguousarray(kedge, np.int32)
+        return self._lib.xengPlongInitialize(int(gpu), int(npair), int(ndm), int(nwin), int(nprod), int(nt), int(nstack), int(nlevel), int(nwhite),
+                                             int(e.size - 1), e.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+
+    def plong_set_mask(self, keep):
+        """keep: host uint8 [nt/2], 0 = zapped, or None (all kept).  Waits for the context's work in flight; holds from the next
+        segment to complete."""
+        return self._lib.xengPlongSetMask(None if keep is None else keep.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
+
+    def plong_run(self, in_arr, nwin_call, out_arr):
+        """Enqueue only: f32 [nwin_call][npair][ndm][nprod] in; (status, completed).  out_arr, [npair][ndm][nlevel][nband] records
+        {f32 H, i32 k}, is written only when the call completes a stack (completed = 1) and may be None on every other call;
+        plong_mark / wait cover it."""
+        done = ctypes.c_int(0)
+        rv = self._enq.xengPlongRun(in_arr.ptr, int(nwin_call), None if out_arr is None else out_arr.ptr, ctypes.byref(done))
+        return rv, done.value
+
+    def plong_reset(self):
+        """The next input counts as window 0 of a new stack (host state only)."""
+        ffi.check("xengPlongReset", self._enq.xengPlongReset())
+
+    def plong_info(self):
+        """(windows taken since the last reset, complete segments of the stack in progress, stacks completed since the reset)"""
+        n, s, k = ctypes.c_longlong(), ctypes.c_int(), ctypes.c_longlong()
+        ffi.call("xengPlongGetInfo", ctypes.byref(n), ctypes.byref(s), ctypes.byref(k))
+        return n.value, s.value, k.value
+
+    def plong_spectrum(self, series0, nser, nt):
+        """Waits for the context's work; (A, nseg): series [series0, series0 + nser) of the stack as it stands, float32
+        [nser][nt/2] in natural k order, and the segments in it."""
+        A, nseg = np.empty((nser, nt // 2), np.float32), ctypes.c_int()
+        ffi.call("xengPlongGetSpectrum", int(series0), int(nser), A.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(nseg))
+        return A, nseg.value
+
     # ---- fast-folding search of the dedispersed beams (BeamFfaSearch; include/xeng.h "Fast-folding search of the dedispersed
     # beams"): a context of its own, its kernels on the beamformer's stream
     def ffa_initialize(self, gpu, npair, ndm, nwin, nprod, nds, nt, noct, pmin, pmax, nwidth):
@@ -844,7 +882,7 @@ class HipBackend:
         ffi.call("xengImsearchGetBaseline", *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for a in out])
         return tuple(out)
 
-    # ---- completion tickets and guard bands of the engines of ffi.ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
+    # ---- completion tickets and guard bands of the engines of ffi.ENGINES and ffi.MORE_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
     # _guards_intact are made from these below the class
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
@@ -900,7 +938,7 @@ def _engine_methods(cname, prefix, guards):
     return {"%s_%s" % (prefix, k): f for k, f in fs.items()}
 
 
-for _row in ffi.ENGINES:
+for _row in ffi.ENGINES + ffi.MORE_ENGINES:
     for _name, _f in _engine_methods(*_row).items():
         _f.__name__ = _name
         _f.__qualname__ = "HipBackend." + _name

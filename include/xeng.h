@@ -875,6 +875,97 @@ int xengPeriodTicketDone(unsigned long long ticket, int *done);
 int xengPeriodSync(void);
 int xengPeriodDestroy(void);
 
+/* ---------------------------------------------------------------- FFT periodicity search with long segments
+ * BeamPeriodSearchLong (no reference counterpart): xengPeriod* for segments of 2^15 to 2^20 windows, which no work-group's LDS
+ * holds -- the transform goes through a scratch buffer in HBM as a four-step FFT -- and with one peak record per series, harmonic
+ * level and BAND of fundamental frequency, since one peak among half a million bins is too few.  A context of its own,
+ * independent of all others (xengPeriod* included), whose kernels run on the beamformer's stream -- rings declared 'beam' cover
+ * them, and xengBeamformSync waits for them too.  An ingest kernel per call; per completed segment a mean kernel and, per batch
+ * of series, two FFT passes, an untangle and a whitening kernel; per completed stack and batch a sums and a reduce kernel
+ * (csrc/plong_kernels.h).
+ *   in       f32[nwin_call][npair][ndm][nprod], the output span of xengDedispRun unchanged; 16-byte aligned; never written.
+ *            1 <= nwin_call <= nwin <= NT, so that a call completes at most one segment.  A series is one (p, d), nser =
+ *            npair*ndm.  nprod = 1: z[n] = in[n][p][d][0]; nprod = 4: z[n] = fl(in[n][p][d][0] + in[n][p][d][1]), I = XX + YY.
+ *            n counts windows since the last reset (xengPlongReset, Initialize).
+ *   sizes    NT = nt, the segment length: a power of two, 2^15 <= NT <= 2^20 (2^14 and below are xengPeriod*'s).  nstack >= 1
+ *            segments per stack.  nlevel = 1..5 harmonic levels, h = 1, 2, 4, 8, 16.  nwhite = B, the whitening block: a power
+ *            of two, 8 <= B <= 2^13, so that a block never spans two work-groups' runs of bins.
+ *   segment  Segment s of a stack is the NT windows [(s0 + s)*NT, (s0 + s + 1)*NT).  The call that brings its last window
+ *            transforms it, per series:
+ *              1. x = z - mean(z).  The mean is formed when the segment completes, in a fixed tree over the whole segment: it is
+ *                 a function of the segment and not of how the calls cut it.  The summation order is the library's: everything
+ *                 up to A is held to a tolerance.
+ *              2. the NT-point real DFT  X[k] = sum_n x[n] * exp(-2 pi i n k / NT).
+ *              3. P[k] = |X[k]|^2 for 1 <= k < NT/2.  DC and Nyquist are dropped.
+ *              4. whitening.  Block b is the bins [b*B, (b+1)*B).  mu_b is the mean of P over the block's bins with k >= 1 and
+ *                 keep[k] != 0.  If the block has no such bin, or mu_b is not finite and positive, S[k] = 1.0f for the whole
+ *                 block (a dead series, all zeros, comes out as pure expectation); otherwise S[k] = P[k] / mu_b.
+ *              5. the mask: a zapped bin (keep[k] = 0) gets S[k] = 1.0f; S[0] = +0.
+ *              6. a segment whose mean(z) is not finite -- it held a NaN or an Inf sample -- has no spectrum: S[k] = NaN for
+ *                 every k >= 1, zapped bins included, so that the series stays NaN in A to the end of its stack.
+ *   stack    A[k] = ((S_1 + S_2) + S_3) + ... in segment order, fp32, one owner per word and no atomics.  The first segment of
+ *            a stack STORES, so nothing is ever cleared.  A is f32[npair][ndm][NT/2] on the device, natural k order.
+ *   bands    kedge[nband + 1], 1 <= nband <= 32: integers with 1 <= kedge[0] < kedge[1] < ... < kedge[nband] <= NT/2 and
+ *            kedge[0] < NT/32.  Band b of level h = 2^l is the set of top-harmonic bins h*kedge[b] <= k < min(h*kedge[b+1],
+ *            NT/2): it holds the fundamentals from kedge[b] to kedge[b+1].  At a high level an upper band may be empty.
+ *   sums     When segment nstack of a stack completes: for h = 2^l, l < nlevel,
+ *              H_h[k] = sum_{j=1..h} A[(j*k + h/2) div h]
+ *            j ascending, plain fp32 adds starting from A of j = 1, no contraction.  k indexes the TOP harmonic: the
+ *            fundamental is k/h bins, k / (h * NT * tsamp) Hz.  The index arithmetic is integer: which words are summed is
+ *            exact, and any float32 restatement that adds in this order reproduces H bit for bit from the same A.  With
+ *            nband = 1 and kedge = {kmin, NT/2} this is xengPeriod*'s rule.
+ *   out      [npair][ndm][nlevel][nband] records of two 32-bit words {f32 H, i32 k}, each one 8-byte store, out_dev 16-byte
+ *            aligned; nothing past npair*ndm*nlevel*nband*8 bytes is written.  A record is the largest H_h[k] of its band, among
+ *            equal sums the smallest k.  A NaN is never a maximum; an empty or all-NaN band reads {+0.0f, -1}.  A series that
+ *            held a non-finite sample anywhere in the stack therefore reads {+0.0f, -1} everywhere, and disturbs no neighbour.
+ *   state    between two guard bands of 64 KiB: the time buffer f32[nser][NT] (time the fastest axis, window n at slot
+ *            n mod NT); A; per series the mean and validity word of the last segment; one scratch for a batch of SB <= nser
+ *            series -- cf32[SB][NT/2] between the FFT passes, the power spectrum f32[SB][NT/2] and the partial records of the
+ *            sums -- with SB chosen at Initialize so that this scratch stays at or below 2 GiB, the per-segment launches looping
+ *            over the batches; the mask with the counts of its blocks, the edges, and the twiddle tables (float64 on the host,
+ *            rounded once).  4096 series at 2^20 are 24 GiB plus the scratch; 16384 series fit up to 2^18.  xengPlongReset moves
+ *            only the host's counts: the partial segment and the partial stack are dropped by index, and nothing is cleared.
+ * A and the records are a fixed function of the series, the mask and the edges: bit-identical however a run is split over calls,
+ * whatever nwin_call, after a Reset as in a fresh context, whatever else runs on the GPU, and whatever SB is.  The records are
+ * exact given A, and the sums exact on integer-valued A below 2^24.
+ * Rejected at Initialize, before any device is touched: a non-positive size, nprod outside {1, 4}, nt not a power of two in
+ * 2^15..2^20, nstack < 1, nlevel outside 1..5, nwhite not a power of two in 8..2^13, nband outside 1..32, NULL edges, edges not
+ * strictly ascending or outside 1..nt/2, kedge[0] >= nt/32, nwin > nt, npair*ndm > 2^24, a state above
+ * XENG_PLONG_MAX_STATE_BYTES; once the device is known, an LDS need above what a work-group may take (64 KiB at most).  Rejected
+ * by Run without a launch: a NULL input or result, a misaligned pointer, nwin_call outside 1..nwin, a NULL output on the call
+ * that completes a stack.  Every call without a context, and GetSpectrum before a segment has completed:
+ * XENG_STATUS_INVALID_STATE. */
+#define XENG_PLONG_MAX_STATE_BYTES (1LL << 36)
+int xengPlongInitialize(int gpu, int npair, int ndm, int nwin, int nprod, int nt, int nstack, int nlevel, int nwhite, int nband, const int *kedge);
+/* keep: u8[nt/2] on the host, 0 = zapped; NULL: all kept (as after Initialize).  Waits for the context's work in flight; holds
+ * from the next segment to complete. */
+int xengPlongSetMask(const unsigned char *keep);
+/* enqueue only.  out_dev is written only by a call that completes a stack (*completed = 1); the host's window count decides that
+ * before anything is enqueued.  Such a call with out_dev NULL is INVALID_ARGUMENT and enqueues nothing; on every other call
+ * out_dev may be NULL and is not touched. */
+int xengPlongRun(const void *in_dev, int nwin_call, void *out_dev, int *completed);
+/* host state only, nothing is launched and nothing cleared: the next input counts as window 0 of segment 0 of a new stack */
+int xengPlongReset(void);
+/* windows taken since the last reset, complete segments of the stack in progress, stacks completed since the last reset */
+int xengPlongGetInfo(long long *nwindows_since_reset, int *nseg_in_stack, long long *nstacks_complete);
+/* waits for the context's work in flight; series [series0, series0 + nser) of the stack as it stands into host f32[nser][nt/2],
+ * natural k order, and the segments it holds (nstack after the call that completed a stack).  A range outside [0, npair*ndm) is
+ * INVALID_ARGUMENT. */
+int xengPlongGetSpectrum(int series0, int nser, float *A_host, int *nseg);
+/* The series per batch: SB as Initialize chose it (nser_batch_max, what the scratch holds) and as the launches take it.
+ * SetBatch lowers it to 1 <= nser_batch <= nser_batch_max from the next call on (0: back to nser_batch_max); host state only.
+ * Results do not depend on it: it is there for the test of exactly that. */
+int xengPlongSetBatch(int nser_batch);
+int xengPlongGetBatch(int *nser_batch, int *nser_batch_max);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengPlongCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengPlongMark(unsigned long long *ticket);
+int xengPlongWait(unsigned long long ticket);
+int xengPlongTicketDone(unsigned long long ticket, int *done);
+int xengPlongSync(void);
+int xengPlongDestroy(void);
+
 /* ---------------------------------------------------------------- Fast-folding search of the dedispersed beams
  * BeamFfaSearch (no reference counterpart: the reference has no detection stage): the fast folding algorithm (Staelin 1969) for
  * the long periods and small duty cycles the FFT search above is blind to.  Per series a segment of NT downsampled samples is
