@@ -524,6 +524,54 @@ class HipBackend:
         ffi.call("xengPlongGetSpectrum", int(series0), int(nser), A.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(nseg))
         return A, nseg.value
 
+    # ---- acceleration search of the long-segment spectra (BeamAccelSearch; include/xeng.h "Acceleration search of the long-segment
+    # spectra"): a context of its own, its kernels on the beamformer's stream
+    def accel_initialize(self, gpu, npair, ndm, nwin, nprod, nt, nlevel, nwhite, kedge, alphas):
+        """kedge: the nband + 1 band edges, strictly ascending integers; alphas: the ntrial index-map coefficients (float64)."""
+        e, a = np.ascontiguousarray(kedge, np.int32), np.ascontiguousarray(alphas, np.float64).reshape(-1)
+        return self._lib.xengAccelInitialize(int(gpu), int(npair), int(ndm), int(nwin), int(nprod), int(nt), int(nlevel), int(nwhite), int(e.size - 1),
+                                             e.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), int(a.size), a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+
+    def accel_set_mask(self, keep):
+        """keep: host uint8 [nt/2], 0 = zapped, or None (all kept).  Waits for the context's work in flight; holds from the next
+        segment to complete."""
+        return self._lib.xengAccelSetMask(None if keep is None else keep.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
+
+    def accel_run(self, in_arr, nwin_call, out_arr):
+        """Enqueue only: f32 [nwin_call][npair][ndm][nprod] in; (status, completed).  out_arr, [npair][ndm][nlevel][nband] records
+        {f32 H, i32 k, i32 ia, f32 H0}, is written only when the call completes a segment (completed = 1) and may be None on every
+        other call; accel_mark / wait cover it."""
+        done = ctypes.c_int(0)
+        rv = self._enq.xengAccelRun(in_arr.ptr, int(nwin_call), None if out_arr is None else out_arr.ptr, ctypes.byref(done))
+        return rv, done.value
+
+    def accel_reset(self):
+        """The next input counts as window 0 of a new segment (host state only)."""
+        ffi.check("xengAccelReset", self._enq.xengAccelReset())
+
+    def accel_info(self):
+        """(windows taken since the last reset, segments completed since the reset)"""
+        n, k = ctypes.c_longlong(), ctypes.c_longlong()
+        ffi.call("xengAccelGetInfo", ctypes.byref(n), ctypes.byref(k))
+        return n.value, k.value
+
+    def accel_trial_records(self, series0, nser, ntrial, nlevel, nband):
+        """Waits for the context's work; the trial records of series [series0, series0 + nser) of the segment that completed last:
+        a {f32 H, i32 k} array [ntrial][nser][nlevel][nband]."""
+        rec = np.empty((ntrial, nser, nlevel, nband), np.dtype([('H', '<f4'), ('k', '<i4')]))
+        ffi.call("xengAccelGetTrialRecords", int(series0), int(nser), rec.ctypes.data)
+        return rec
+
+    def accel_set_batch(self, nser_batch):
+        """The series per batch from the next call on (0: as many as the scratch holds).  Results do not depend on it."""
+        ffi.call("xengAccelSetBatch", int(nser_batch))
+
+    def accel_get_batch(self):
+        """(series per batch as the launches take it, as the scratch holds it)"""
+        a, b = ctypes.c_int(), ctypes.c_int()
+        ffi.call("xengAccelGetBatch", ctypes.byref(a), ctypes.byref(b))
+        return a.value, b.value
+
     # ---- fast-folding search of the dedispersed beams (BeamFfaSearch; include/xeng.h "Fast-folding search of the dedispersed
     # beams"): a context of its own, its kernels on the beamformer's stream
     def ffa_initialize(self, gpu, npair, ndm, nwin, nprod, nds, nt, noct, pmin, pmax, nwidth):
@@ -882,7 +930,7 @@ class HipBackend:
         ffi.call("xengImsearchGetBaseline", *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for a in out])
         return tuple(out)
 
-    # ---- completion tickets and guard bands of the engines of ffi.ENGINES and ffi.MORE_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
+    # ---- completion tickets and guard bands of the engines of ffi.ENGINES, ffi.MORE_ENGINES and ffi.NEWER_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
     # _guards_intact are made from these below the class
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
@@ -938,7 +986,7 @@ def _engine_methods(cname, prefix, guards):
     return {"%s_%s" % (prefix, k): f for k, f in fs.items()}
 
 
-for _row in ffi.ENGINES + ffi.MORE_ENGINES:
+for _row in ffi.ENGINES + ffi.MORE_ENGINES + ffi.NEWER_ENGINES:
     for _name, _f in _engine_methods(*_row).items():
         _f.__name__ = _name
         _f.__qualname__ = "HipBackend." + _name

@@ -117,6 +117,9 @@ SYMBOLS = {
     "xengPlongInitialize": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _pi], "xengPlongSetMask": [ctypes.POINTER(ctypes.c_ubyte)],
     "xengPlongRun": [_vp, _i, _vp, _pi], "xengPlongReset": [], "xengPlongGetInfo": [_pll, _pi, _pll],
     "xengPlongGetSpectrum": [_i, _i, ctypes.POINTER(ctypes.c_float), _pi], "xengPlongSetBatch": [_i], "xengPlongGetBatch": [_pi, _pi],
+    "xengAccelInitialize": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _pi, _i, ctypes.POINTER(ctypes.c_double)], "xengAccelSetMask": [ctypes.POINTER(ctypes.c_ubyte)],
+    "xengAccelRun": [_vp, _i, _vp, _pi], "xengAccelReset": [], "xengAccelGetInfo": [_pll, _pll],
+    "xengAccelGetTrialRecords": [_i, _i, _vp], "xengAccelSetBatch": [_i], "xengAccelGetBatch": [_pi, _pi],
     "xengFfaInitialize": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i], "xengFfaRun": [_vp, _i, _vp, _pi], "xengFfaReset": [],
     "xengFfaGetInfo": [_pll, _pll], "xengFfaGetStats": [ctypes.POINTER(ctypes.c_float)],
     "xengCdedispInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdedispSetChirp": [ctypes.POINTER(ctypes.c_float)],
@@ -168,7 +171,9 @@ ENGINES = [("Upchan", "upchan", False), ("UpchanCorr", "upchan_corr", False), ("
            ("Clean", "clean", True), ("Flag", "flag", True), ("Predict", "predict", True), ("Imsearch", "imsearch", True)]
 # Engines added since tests/test_engine_table_cpu.py pinned the length of ENGINES: rows of the same kind, treated the same everywhere.
 MORE_ENGINES = [("Plong", "plong", True)]
-for _c, _prefix, _guards in ENGINES + MORE_ENGINES:
+# ... and since tests/test_plong_cpu.py pinned MORE_ENGINES
+NEWER_ENGINES = [("Accel", "accel", True)]
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES:
     SYMBOLS.update({"xeng%sMark" % _c: [ctypes.POINTER(ctypes.c_ulonglong)], "xeng%sWait" % _c: [ctypes.c_ulonglong],
                     "xeng%sTicketDone" % _c: [ctypes.c_ulonglong, _pi], "xeng%sSync" % _c: [], "xeng%sDestroy" % _c: []})
     if _guards:
@@ -213,7 +218,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengUpchanSumBeamsRun", "xengUpchanSumBeamsPrime", "xengUpchanSumBeamsReset",
                 "xengUpchanSpectraRun", "xengUpchanSpectraRunParts", "xengUpchanSpectraPrime", "xengUpchanSpectraPrimeParts", "xengUpchanSpectraReset",
                 "xengDedispRun", "xengDedispReset", "xengPulseRun", "xengPulseReset", "xengFoldRun", "xengFoldReset", "xengPeriodRun", "xengPeriodReset",
-                "xengPlongRun", "xengPlongReset",
+                "xengPlongRun", "xengPlongReset", "xengAccelRun", "xengAccelReset",
                 "xengFfaRun", "xengFfaReset", "xengCdedispRun", "xengCdedispReset", "xengCdlongRun", "xengCdlongReset",
                 "xengImageRun", "xengGaincalRun", "xengCalapplyRun", "xengPeelRun", "xengCleanRun", "xengFlagRun", "xengPredictRun",
                 "xengImsearchRun", "xengImsearchReset",
@@ -223,7 +228,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengRingCommitExternal", "xengRingNextSequence", "xengRingAcquire", "xengRingAcquireParts", "xengRingSpanRelease", "xengRingGetInfo",
                 "xengRingOpenReader", "xengRingCloseReader", "xengRingResize",
                 "xengStampNow", "xengStampNowFor", "xengStampDone", "xengGetDevice", "xengSetDevice"]
-for _c, _prefix, _guards in ENGINES + MORE_ENGINES:     # an event record and an event query: neither can wait
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES:     # an event record and an event query: neither can wait
     ENQUEUE_ONLY += ["xeng%sMark" % _c, "xeng%sTicketDone" % _c]
 _enq = None
 

@@ -966,6 +966,72 @@ int xengPlongTicketDone(unsigned long long ticket, int *done);
 int xengPlongSync(void);
 int xengPlongDestroy(void);
 
+/* ---------------------------------------------------------------- Acceleration search of the long-segment spectra
+ * BeamAccelSearch (no reference counterpart): the search of xengPlong* repeated per trial acceleration.  Over a segment of minutes
+ * a pulsar in a binary drifts across z = a T^2 f / c Fourier bins and its harmonics smear; trial a reads the segment through a
+ * quadratic index map that undoes a constant acceleration (time-domain resampling, nearest sample) and searches the result as
+ * xengPlong* searches a segment.  A context of its own, independent of all others (xengPlong* included), whose kernels run on the
+ * beamformer's stream.  An ingest kernel per call; per completed segment, per batch of series and per trial a gathered mean and
+ * columns pass and xengPlong*'s rows pass, untangle, whitening, sums and reduce; then one kernel that takes the best over the
+ * trials (csrc/accel_kernels.h).
+ *   in       exactly xengPlong*'s: f32[nwin_call][npair][ndm][nprod], 16-byte aligned, never written; nprod 1 or 4;
+ *            1 <= nwin_call <= nwin <= NT; NT = nt a power of two, 2^15 <= NT <= 2^20; the time buffer f32[nser][NT].  There is
+ *            no stack: every completed segment yields one plane.
+ *   trials   1 <= ntrial <= 256, alpha f64[ntrial] given at Initialize.  Trial a searches the series
+ *              z_a[n] = z[n + s_a(n)],   s_a(n) = (long long) rint(alpha[a] * (double)(n * (n - NT))),   n = 0 .. NT-1
+ *            the integer product formed exactly (it is below 2^40 in size, exact as a float64), ONE float64 multiply, rounding to
+ *            nearest even.  Every term is an IEEE operation: any float64 restatement gives the same indices.  s_a(0) = 0 and
+ *            s_a(NT-1) = 0 (|alpha| (NT-1) < 0.5): the segment's ends stay where they are and its middle moves by alpha NT^2 / 4
+ *            windows.  Initialize refuses a non-finite alpha and |alpha| * NT > 0.5; under that limit the map is non-decreasing
+ *            and stays inside [0, NT-1], so there is no clamp.  (alpha = a tsamp / 2c for an acceleration a along the line of
+ *            sight: the limit is |a| <= c / T, far beyond any binary.)  izero is the first trial with alpha == 0.0, -1 without.
+ *   trial a  computes everything xengPlong* computes for one segment with nstack = 1, applied to z_a: the segment mean in that
+ *            engine's tree -- over z_a, not over z -- the transform, P, the block-mean whitening under the mask, and the banded
+ *            harmonic sums (nlevel <= 5, nband <= 32, kedge as there).  The records of trial a are BIT FOR BIT the records
+ *            xengPlongRun writes when fed z_a as its input, whatever the batch size and however the calls cut the segment.
+ *   records  {f32 H, i32 k}[ntrial][npair*ndm][nlevel][nband] of the segment that completed last are kept in the state:
+ *            xengAccelGetTrialRecords.
+ *   out      written only by the call that completes a segment (*completed = 1): [npair][ndm][nlevel][nband] records of four
+ *            32-bit words {f32 H, i32 k, i32 ia, f32 H0}, each one 16-byte store; nothing past npair*ndm*nlevel*nband*16 bytes
+ *            is written.  (H, k, ia) is the best over the trials taken in ascending order: the larger H, then the smaller ia,
+ *            then (within a trial already) the smaller k.  A NaN never enters.  A record that is empty in every trial reads
+ *            {+0, -1, -1, H0}.  H0 is the H of trial izero for that record: what the unaccelerated search finds; +0 when
+ *            izero < 0 or that record is empty.
+ *   state    between two guard bands of 64 KiB: the time buffer, the trial records, one scratch for a batch of SB <= nser series
+ *            (cf32[SB][NT/2] between the passes, the power spectrum and the whitened spectrum f32[SB][NT/2] each, the partial
+ *            records of the sums, mean and validity of SB series), SB chosen at Initialize so that the scratch stays at or below
+ *            2 GiB and SB <= 32768; the mask with its block counts, the edges and the twiddle tables.  Nothing of size
+ *            [ntrial][NT] exists: the resampled series is never stored.  xengAccelReset moves only the host's counts.
+ * Rejected at Initialize, before any device is touched: what xengPlongInitialize rejects (it has no nstack), ntrial outside
+ * 1..256, a NULL or non-finite alpha, |alpha| * nt > 0.5, a state above XENG_ACCEL_MAX_STATE_BYTES; once the device is known, an
+ * LDS need above what a work-group may take.  Rejected by Run without a launch: a NULL input or result, a misaligned pointer,
+ * nwin_call outside 1..nwin, a NULL output on the call that completes a segment.  Every call without a context, and
+ * GetTrialRecords before a segment has completed: XENG_STATUS_INVALID_STATE. */
+#define XENG_ACCEL_MAX_STATE_BYTES (1LL << 36)
+int xengAccelInitialize(int gpu, int npair, int ndm, int nwin, int nprod, int nt, int nlevel, int nwhite, int nband, const int *kedge, int ntrial,
+                        const double *alpha);
+/* keep: u8[nt/2] on the host, 0 = zapped; NULL: all kept.  Waits for the context's work in flight; holds from the next segment. */
+int xengAccelSetMask(const unsigned char *keep);
+/* enqueue only.  out_dev is written only by a call that completes a segment (*completed = 1); such a call with out_dev NULL is
+ * INVALID_ARGUMENT and enqueues nothing; on every other call out_dev may be NULL and is not touched. */
+int xengAccelRun(const void *in_dev, int nwin_call, void *out_dev, int *completed);
+/* host state only: the next input counts as window 0 of a new segment */
+int xengAccelReset(void);
+/* windows taken and segments completed since the last reset */
+int xengAccelGetInfo(long long *nwindows_since_reset, long long *nsegments_complete);
+/* waits for the context's work in flight; the trial records of series [series0, series0 + nser) of the segment that completed
+ * last into host {f32 H, i32 k}[ntrial][nser][nlevel][nband].  A range outside [0, npair*ndm) is INVALID_ARGUMENT. */
+int xengAccelGetTrialRecords(int series0, int nser, void *records_host);
+/* the series per batch, as xengPlongSetBatch / GetBatch: results do not depend on it */
+int xengAccelSetBatch(int nser_batch);
+int xengAccelGetBatch(int *nser_batch, int *nser_batch_max);
+int xengAccelCheckGuards(int *intact);
+int xengAccelMark(unsigned long long *ticket);
+int xengAccelWait(unsigned long long ticket);
+int xengAccelTicketDone(unsigned long long ticket, int *done);
+int xengAccelSync(void);
+int xengAccelDestroy(void);
+
 /* ---------------------------------------------------------------- Fast-folding search of the dedispersed beams
  * BeamFfaSearch (no reference counterpart: the reference has no detection stage): the fast folding algorithm (Staelin 1969) for
  * the long periods and small duty cycles the FFT search above is blind to.  Per series a segment of NT downsampled samples is
