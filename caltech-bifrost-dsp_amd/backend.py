@@ -602,6 +602,55 @@ class HipBackend:
         ffi.call("xengFfaGetStats", st.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
         return st
 
+    # ---- folding of search candidates (BeamCandFold; include/xeng.h "Folding of search candidates"): a context of its own, its kernels
+    # on the beamformer's stream
+    def candfold_initialize(self, gpu, npair, ndm, nwin, nprod, ncand_max, nbin, nsub, nsubwin, nwidth, d1, d2, gains):
+        """d1, d2: the trial table in sixteenths of a bin (blocks/cand_fold.py candfold_trials); gains: float32 [nwidth]."""
+        d1, d2 = np.ascontiguousarray(d1, np.int32), np.ascontiguousarray(d2, np.int32)
+        gains = np.ascontiguousarray(gains, np.float32)
+        if d1.shape != d2.shape or d1.ndim != 1 or gains.shape != (int(nwidth),):
+            raise ValueError("candfold_initialize: d1 %r and d2 %r are not one table, or gains %r not [nwidth]" % (d1.shape, d2.shape, gains.shape))
+        return self._lib.xengCandfoldInitialize(int(gpu), int(npair), int(ndm), int(nwin), int(nprod), int(ncand_max), int(nbin), int(nsub), int(nsubwin),
+                                                int(nwidth), d1.size, d1.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                d2.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), gains.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+
+    def candfold_set_candidates(self, series, phi0, dphi, ddphi, active):
+        """Host arrays of one entry per candidate (blocks/cand_fold.py candfold_oscillators).  Waits for the context's work in
+        flight; in force from the next segment boundary, or at once when the window count stands on one."""
+        series = np.ascontiguousarray(series, np.int32)
+        phi0, dphi = np.ascontiguousarray(phi0, np.uint64), np.ascontiguousarray(dphi, np.uint64)
+        ddphi, active = np.ascontiguousarray(ddphi, np.int64), np.ascontiguousarray(active, np.uint8)
+        if not series.shape == phi0.shape == dphi.shape == ddphi.shape == active.shape or series.ndim != 1:
+            raise ValueError("candfold_set_candidates: the arrays are not one entry per candidate")
+        u64 = ctypes.POINTER(ctypes.c_ulonglong)
+        return self._lib.xengCandfoldSetCandidates(series.size, series.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), phi0.ctypes.data_as(u64),
+                                                   dphi.ctypes.data_as(u64), ddphi.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)),
+                                                   active.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
+
+    def candfold_run(self, in_arr, nwin_call, out_arr):
+        """Enqueue only: f32 [nwin_call][npair][ndm][nprod] in; (status, completed).  out_arr, ncand_max records {f32 S, f32 S0, i16 it,
+        i16 iw, i16 j, i16 pad} and then f32 [ncand_max][nbin] best profiles, is written only when the call completes a segment
+        (completed = 1) and may be None on every other call; candfold_mark / wait cover it."""
+        done = ctypes.c_int(0)
+        rv = self._enq.xengCandfoldRun(in_arr.ptr, int(nwin_call), None if out_arr is None else out_arr.ptr, ctypes.byref(done))
+        return rv, done.value
+
+    def candfold_reset(self):
+        """The next input counts as window 0 of a new segment with m = 0; the partial cube is cleared by one launch."""
+        ffi.check("xengCandfoldReset", self._enq.xengCandfoldReset())
+
+    def candfold_info(self):
+        """(windows taken since the last reset, segments completed since the reset)"""
+        n, k = ctypes.c_longlong(), ctypes.c_longlong()
+        ffi.call("xengCandfoldGetInfo", ctypes.byref(n), ctypes.byref(k))
+        return n.value, k.value
+
+    def candfold_cube(self, ncand_max, nsub, nbin):
+        """Waits for the context's work; (cube float32, hits uint32), each [ncand_max][nsub][nbin], of the last completed segment."""
+        cube, hits = np.empty((ncand_max, nsub, nbin), np.float32), np.empty((ncand_max, nsub, nbin), np.uint32)
+        ffi.call("xengCandfoldGetCube", cube.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), hits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)))
+        return cube, hits
+
     # ---- coherent dedispersion of the voltage beams (BeamCoherentDedisperse; include/xeng.h "Coherent dedispersion of the voltage
     # beams"): a context of its own, its kernels on the beamformer's stream
     def cdedisp_initialize(self, gpu, nchan, nbeam, ntime, pair0, npair, nfft, overlap):
@@ -930,7 +979,7 @@ class HipBackend:
         ffi.call("xengImsearchGetBaseline", *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for a in out])
         return tuple(out)
 
-    # ---- completion tickets and guard bands of the engines of ffi.ENGINES, ffi.MORE_ENGINES and ffi.NEWER_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
+    # ---- completion tickets and guard bands of the engines of ffi.ENGINES, ffi.MORE_ENGINES, ffi.NEWER_ENGINES and ffi.NEWEST_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
     # _guards_intact are made from these below the class
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
@@ -986,7 +1035,7 @@ def _engine_methods(cname, prefix, guards):
     return {"%s_%s" % (prefix, k): f for k, f in fs.items()}
 
 
-for _row in ffi.ENGINES + ffi.MORE_ENGINES + ffi.NEWER_ENGINES:
+for _row in ffi.ENGINES + ffi.MORE_ENGINES + ffi.NEWER_ENGINES + ffi.NEWEST_ENGINES:
     for _name, _f in _engine_methods(*_row).items():
         _f.__name__ = _name
         _f.__qualname__ = "HipBackend." + _name

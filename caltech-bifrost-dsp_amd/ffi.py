@@ -122,6 +122,10 @@ SYMBOLS = {
     "xengAccelGetTrialRecords": [_i, _i, _vp], "xengAccelSetBatch": [_i], "xengAccelGetBatch": [_pi, _pi],
     "xengFfaInitialize": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i], "xengFfaRun": [_vp, _i, _vp, _pi], "xengFfaReset": [],
     "xengFfaGetInfo": [_pll, _pll], "xengFfaGetStats": [ctypes.POINTER(ctypes.c_float)],
+    "xengCandfoldInitialize": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _pi, _pi, ctypes.POINTER(ctypes.c_float)],
+    "xengCandfoldSetCandidates": [_i, _pi, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong), _pll, ctypes.POINTER(ctypes.c_ubyte)],
+    "xengCandfoldRun": [_vp, _i, _vp, _pi], "xengCandfoldReset": [], "xengCandfoldGetInfo": [_pll, _pll],
+    "xengCandfoldGetCube": [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint)],
     "xengCdedispInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdedispSetChirp": [ctypes.POINTER(ctypes.c_float)],
     "xengCdedispRun": [_vp, _vp, _pi], "xengCdedispReset": [], "xengCdedispGetInfo": [_pi, _pi, _pll, _pll],
     "xengCdlongInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdlongSetChirp": [_i, ctypes.POINTER(ctypes.c_float)],
@@ -173,7 +177,9 @@ ENGINES = [("Upchan", "upchan", False), ("UpchanCorr", "upchan_corr", False), ("
 MORE_ENGINES = [("Plong", "plong", True)]
 # ... and since tests/test_plong_cpu.py pinned MORE_ENGINES
 NEWER_ENGINES = [("Accel", "accel", True)]
-for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES:
+# ... and since tests/test_accel_cpu.py pinned NEWER_ENGINES
+NEWEST_ENGINES = [("Candfold", "candfold", True)]
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES:
     SYMBOLS.update({"xeng%sMark" % _c: [ctypes.POINTER(ctypes.c_ulonglong)], "xeng%sWait" % _c: [ctypes.c_ulonglong],
                     "xeng%sTicketDone" % _c: [ctypes.c_ulonglong, _pi], "xeng%sSync" % _c: [], "xeng%sDestroy" % _c: []})
     if _guards:
@@ -219,7 +225,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengUpchanSpectraRun", "xengUpchanSpectraRunParts", "xengUpchanSpectraPrime", "xengUpchanSpectraPrimeParts", "xengUpchanSpectraReset",
                 "xengDedispRun", "xengDedispReset", "xengPulseRun", "xengPulseReset", "xengFoldRun", "xengFoldReset", "xengPeriodRun", "xengPeriodReset",
                 "xengPlongRun", "xengPlongReset", "xengAccelRun", "xengAccelReset",
-                "xengFfaRun", "xengFfaReset", "xengCdedispRun", "xengCdedispReset", "xengCdlongRun", "xengCdlongReset",
+                "xengFfaRun", "xengFfaReset", "xengCandfoldRun", "xengCandfoldReset", "xengCdedispRun", "xengCdedispReset", "xengCdlongRun", "xengCdlongReset",
                 "xengImageRun", "xengGaincalRun", "xengCalapplyRun", "xengPeelRun", "xengCleanRun", "xengFlagRun", "xengPredictRun",
                 "xengImsearchRun", "xengImsearchReset",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
@@ -228,7 +234,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengRingCommitExternal", "xengRingNextSequence", "xengRingAcquire", "xengRingAcquireParts", "xengRingSpanRelease", "xengRingGetInfo",
                 "xengRingOpenReader", "xengRingCloseReader", "xengRingResize",
                 "xengStampNow", "xengStampNowFor", "xengStampDone", "xengGetDevice", "xengSetDevice"]
-for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES:     # an event record and an event query: neither can wait
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES:     # an event record and an event query: neither can wait
     ENQUEUE_ONLY += ["xeng%sMark" % _c, "xeng%sTicketDone" % _c]
 _enq = None
 

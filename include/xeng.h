@@ -1104,6 +1104,92 @@ int xengFfaTicketDone(unsigned long long ticket, int *done);
 int xengFfaSync(void);
 int xengFfaDestroy(void);
 
+/* ---------------------------------------------------------------- Folding of search candidates
+ * BeamCandFold (no reference counterpart: the reference has no detection stage): what prepfold / pdmp do after a search.  Up to
+ * ncand_max candidates are folded at once, each from its own (pair, trial) series of the dedispersed beams, into nsub
+ * sub-integrations x nbin phase bins; at the end of each segment a table of period / period-derivative offsets is searched per
+ * candidate on the folded cube, and one record and one best profile per candidate come out.  A context of its own, independent of
+ * all others, whose kernels run on the beamformer's stream -- rings declared 'beam' cover them, and xengBeamformSync waits for
+ * them too.  A fold kernel per call; per completed segment a refine kernel and a clearing launch (csrc/candfold_kernels.h).  The
+ * library knows integers only: nothing of pulsars, time or c.
+ * Everything below is fp32 and fl() is one rounding to fp32; no product is contracted into a sum anywhere.
+ *   in       f32[nwin_call][npair][ndm][nprod], the output span of xengDedispRun unchanged; 16-byte aligned; never written.
+ *            1 <= nwin_call <= nwin.  A series is one (p, d), series = p*ndm + d.  z[n] as xengPeriodRun / xengFfaRun take it:
+ *            nprod = 1 the word, nprod = 4 fl(XX + YY).  n counts windows since the last reset (xengCandfoldReset, Initialize).
+ *   sizes    nbin a power of two, 16 .. 256; 2 <= nsub <= 64 (odd values too), nsub*nbin <= 8192; nsubwin >= 1 windows a
+ *            sub-integration; a segment is NT = nsub*nsubwin windows, NT < 2^31, nwin <= NT (a call completes at most one segment);
+ *            1 <= ncand_max <= XENG_CANDFOLD_MAX_CAND; 1 <= nwidth, 2^(nwidth-1) <= nbin/2; 1 <= ntrial <= XENG_CANDFOLD_MAX_TRIAL
+ *            trials (d1[t], d2[t]), int32, |d| <= 2^20, in sixteenths of a bin; g = f32[nwidth], finite and positive, from the host
+ *            ((float)(1/sqrt(w(1 - w/nbin))), w = 2^iw).
+ *   candidates  xengCandfoldSetCandidates: per candidate {series, u64 phi0, u64 dphi, i64 ddphi, active}.  The oscillator is
+ *            xengFoldSetPhase's word for word: with m = n - n_ref, in wrapping 64-bit arithmetic
+ *            Phi(m) = phi0 + dphi*m + ddphi*(m(m-1)/2) and bin = ((Phi >> 32) * nbin) >> 32.  A set takes effect at the next
+ *            segment boundary, or at once when the count stands on one (after Initialize or Reset, or exactly between two
+ *            segments); n_ref is the window at which it took effect, and m keeps running across segments.  Run refuses a call
+ *            whose last m would reach 2^31.  Two candidates may name the same series.  Slots from ncand on are unset.
+ *   fold     every call, s = (n mod NT) div nsubwin, b = bin_c(n): cube[c][s][b] = fl(cube[c][s][b] + z_c[n]) in ascending n, one
+ *            strictly sequential chain of fp32 adds per word from +0; hits[c][s][b] += 1 (u32).  No atomics and no partial sums:
+ *            the cube does not depend on nwin_call, on how calls cut sub-integrations, or on what else runs.  A NaN stays in its
+ *            cell.  A call may straddle the end of a segment: it completes that segment (refine, outputs, one clearing launch) and
+ *            its remaining windows fold into the next.
+ *   refine   on the call that completes a segment, per active candidate.  u_s = 2s + 1 - nsub;
+ *            r_t(s) = floor((2N + D) / (2D)), N = d1[t]*u_s*nsub + 2*d2[t]*u_s^2, D = 32*nsub^2, in 64-bit integers with floor
+ *            division: d1*(t/T) + d2*(2t/T)^2 sixteenths of a bin about mid-segment, rounded half up to bins.  Per trial t
+ *              P_t[b] = sum over s ascending of cube[c][s][(b - r_t(s)) mod nbin], plain adds from +0; H_t[b] the same over hits;
+ *              p_t[b] = P_t[b] / (float)H_t[b], a correctly rounded division, +0 where H_t[b] = 0;
+ *              circular boxcars B_1 = p_t, B_2w[j] = fl(B_w[j] + B_w[(j + w) mod nbin]);
+ *              total_c = ((p_z[0] + p_z[1]) + ...) over the bins of the all-zero-shift profile p_z, whatever the table holds;
+ *              base_w = fl(total_c * w/nbin) (w/nbin exact); the score C = fl(fl(B_w[j] - base_w) * g[iw]).
+ *            The record is the largest C over (t, iw, j); among equals (+0 and -0 are equal) the smallest t, then iw, then j.  A
+ *            NaN is never a maximum.
+ *   out      written only by the completing call (*completed = 1): ncand_max records {f32 S, f32 S0, i16 it, i16 iw, i16 j,
+ *            i16 pad = 0}, one 16-byte store each, then the best profiles f32[ncand_max][nbin], p_t at the winning trial;
+ *            nothing past ncand_max*(16 + 4*nbin) bytes is written.  S0 is the best score, by the same rule, of the first trial
+ *            with d1 = d2 = 0 (+0 without one, or when it has no score that is not NaN).  An inactive or unset slot reads
+ *            {+0, +0, -1, -1, -1, 0}, a candidate without a score {+0, S0, -1, -1, -1, 0}; their profiles read +0.
+ *   state    between two guard bands of 64 KiB: two cubes with their hits (the one that folds; the last completed one, kept for
+ *            xengCandfoldGetCube until the next segment completes), two candidate tables, the shifts r_t(s) mod nbin, the gains.
+ *            xengCandfoldReset moves the host's counts and enqueues one clearing launch: the partial segment is dropped, the
+ *            candidates stay (a set that waited takes effect), the next window is n = 0 with m = 0.
+ * Cube, hits, records and profiles are a fixed function of the windows and the candidates: bit-identical however a run is split
+ * over calls, after a Reset as in a fresh context, and whatever else runs on the GPU.
+ * Rejected at Initialize, before any device is touched: every size outside the ranges above, nprod outside {1, 4},
+ * npair*ndm > 2^24, a null or misaligned table, a trial outside +-2^20, a gain that is not finite and positive, a state above
+ * XENG_CANDFOLD_MAX_STATE_BYTES.  Rejected by SetCandidates: a null or misaligned array, ncand outside 1..ncand_max, a series
+ * outside 0..npair*ndm-1.  Rejected by Run without a launch: a NULL input or result, a misaligned pointer, nwin_call outside
+ * 1..nwin, a last m of 2^31 or more, a NULL output on the call that completes a segment.  Every call without a context, Run
+ * before the first SetCandidates and GetCube before a segment has completed: XENG_STATUS_INVALID_STATE.
+ * Not built: DM refinement (it needs the channelised data, which xengFold* has), interpolated (sub-bin) shifts, a chi^2 statistic,
+ * plots or archive output, a second derivative of the period (jerk). */
+#define XENG_CANDFOLD_MAX_STATE_BYTES (1LL << 28)
+#define XENG_CANDFOLD_MAX_CAND 4096
+#define XENG_CANDFOLD_MAX_TRIAL 4096
+int xengCandfoldInitialize(int gpu, int npair, int ndm, int nwin, int nprod, int ncand_max, int nbin, int nsub, int nsubwin, int nwidth, int ntrial,
+                           const int *d1, const int *d2, const float *g);
+/* host arrays of ncand entries.  Waits for the context's work in flight (as xengFoldSetPhase); the set is in force from the next
+ * segment boundary, or at once when the window count stands on one */
+int xengCandfoldSetCandidates(int ncand, const int *series, const unsigned long long *phi0, const unsigned long long *dphi, const long long *ddphi,
+                              const unsigned char *active);
+/* enqueue only.  out_dev is written only by a call that completes a segment (*completed = 1); the host's window count decides
+ * that before anything is enqueued.  Such a call with out_dev NULL is INVALID_ARGUMENT and enqueues nothing; on every other call
+ * out_dev may be NULL and is not touched. */
+int xengCandfoldRun(const void *in_dev, int nwin_call, void *out_dev, int *completed);
+/* enqueue only: the host's counts, and one clearing launch on the stream */
+int xengCandfoldReset(void);
+/* windows taken and segments completed since the last reset */
+int xengCandfoldGetInfo(long long *nwindows_since_reset, long long *nsegments_complete);
+/* waits for the context's work in flight; cube f32 and hits u32 [ncand_max][nsub][nbin] of the last completed segment: what the
+ * exact tests read */
+int xengCandfoldGetCube(float *cube_host, unsigned int *hits_host);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengCandfoldCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengCandfoldMark(unsigned long long *ticket);
+int xengCandfoldWait(unsigned long long ticket);
+int xengCandfoldTicketDone(unsigned long long ticket, int *done);
+int xengCandfoldSync(void);
+int xengCandfoldDestroy(void);
+
 /* ---------------------------------------------------------------- Coherent dedispersion of the voltage beams
  * BeamCoherentDedisperse (no reference counterpart): every (coarse channel, selected beam) row of the voltage beams is filtered by
  * overlap-save with a table given in the frequency domain, and comes out in the format it came in.  The library knows nothing of
