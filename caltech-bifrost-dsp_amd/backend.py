@@ -651,6 +651,50 @@ class HipBackend:
         ffi.call("xengCandfoldGetCube", cube.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), hits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)))
         return cube, hits
 
+    # ---- cleaning of the fine-channel power beams (BeamRfiClean; include/xeng.h "Cleaning of the fine-channel power beams"): a context
+    # of its own, its kernels on the beamformer's stream
+    def rfi_initialize(self, gpu, npair, nfine, nwin, nstat):
+        return self._lib.xengRfiInitialize(int(gpu), int(npair), int(nfine), int(nwin), int(nstat))
+
+    def rfi_set_control(self, k_chan, t_clip, t_broad, min_count, zerodm):
+        """The thresholds as the library takes them (blocks/rfi_clean.py rfi_controls); they hold from the next block to be decided."""
+        return self._lib.xengRfiSetControl(float(k_chan), float(t_clip), float(t_broad), int(min_count), int(bool(zerodm)))
+
+    def rfi_set_mask(self, mask):
+        """mask: host uint8 [nfine], non-zero = left out, or None (none left out).  Waits for the context's work in flight; holds
+        from the next block to be decided."""
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        return self._lib.xengRfiSetMask(None if mask is None else mask.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
+
+    def rfi_run(self, in_arr, nwin_call, out_arr, stats_arr):
+        """Enqueue only: f32 [nwin_call][npair][nfine][4] in and out, i32 [nwin_call][npair][4] stats; (status, completed): the call
+        decided a block.  The output is the cleaned input nstat windows earlier; rfi_mark / wait cover it."""
+        done = ctypes.c_int(0)
+        rv = self._enq.xengRfiRun(in_arr.ptr, int(nwin_call), out_arr.ptr, stats_arr.ptr, ctypes.byref(done))
+        return rv, done.value
+
+    def rfi_reset(self):
+        """The next input counts as window 0 (host state only)."""
+        ffi.check("xengRfiReset", self._enq.xengRfiReset())
+
+    def rfi_info(self):
+        """(windows taken since the last reset, blocks decided since the reset)"""
+        n, k = ctypes.c_longlong(), ctypes.c_longlong()
+        ffi.call("xengRfiGetInfo", ctypes.byref(n), ctypes.byref(k))
+        return n.value, k.value
+
+    def rfi_block(self, npair, nfine):
+        """Waits for the context's work; the newest decided block's tables: (flags uint8, mu, var, r float32, each [npair][nfine],
+        gains float32 [npair][nfine][4])."""
+        flags = np.empty((npair, nfine), np.uint8)
+        mu, var, r = (np.empty((npair, nfine), np.float32) for _ in range(3))
+        gains = np.empty((npair, nfine, 4), np.float32)
+        pf = ctypes.POINTER(ctypes.c_float)
+        ffi.call("xengRfiGetBlock", flags.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)), mu.ctypes.data_as(pf), var.ctypes.data_as(pf), r.ctypes.data_as(pf),
+                 gains.ctypes.data_as(pf))
+        return flags, mu, var, r, gains
+
     # ---- coherent dedispersion of the voltage beams (BeamCoherentDedisperse; include/xeng.h "Coherent dedispersion of the voltage
     # beams"): a context of its own, its kernels on the beamformer's stream
     def cdedisp_initialize(self, gpu, nchan, nbeam, ntime, pair0, npair, nfft, overlap):
@@ -979,7 +1023,7 @@ class HipBackend:
         ffi.call("xengImsearchGetBaseline", *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for a in out])
         return tuple(out)
 
-    # ---- completion tickets and guard bands of the engines of ffi.ENGINES, ffi.MORE_ENGINES, ffi.NEWER_ENGINES and ffi.NEWEST_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
+    # ---- completion tickets and guard bands of the engines of ffi.ENGINES, ffi.MORE_ENGINES, ffi.NEWER_ENGINES, ffi.NEWEST_ENGINES and ffi.LATEST_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
     # _guards_intact are made from these below the class
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
@@ -1035,7 +1079,7 @@ def _engine_methods(cname, prefix, guards):
     return {"%s_%s" % (prefix, k): f for k, f in fs.items()}
 
 
-for _row in ffi.ENGINES + ffi.MORE_ENGINES + ffi.NEWER_ENGINES + ffi.NEWEST_ENGINES:
+for _row in ffi.ENGINES + ffi.MORE_ENGINES + ffi.NEWER_ENGINES + ffi.NEWEST_ENGINES + ffi.LATEST_ENGINES:
     for _name, _f in _engine_methods(*_row).items():
         _f.__name__ = _name
         _f.__qualname__ = "HipBackend." + _name

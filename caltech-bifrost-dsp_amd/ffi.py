@@ -126,6 +126,10 @@ SYMBOLS = {
     "xengCandfoldSetCandidates": [_i, _pi, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong), _pll, ctypes.POINTER(ctypes.c_ubyte)],
     "xengCandfoldRun": [_vp, _i, _vp, _pi], "xengCandfoldReset": [], "xengCandfoldGetInfo": [_pll, _pll],
     "xengCandfoldGetCube": [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint)],
+    "xengRfiInitialize": [_i, _i, _i, _i, _i], "xengRfiSetControl": [ctypes.c_float, ctypes.c_float, ctypes.c_float, _i, _i],
+    "xengRfiSetMask": [ctypes.POINTER(ctypes.c_ubyte)], "xengRfiRun": [_vp, _i, _vp, _vp, _pi], "xengRfiReset": [], "xengRfiGetInfo": [_pll, _pll],
+    "xengRfiGetBlock": [ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                        ctypes.POINTER(ctypes.c_float)],
     "xengCdedispInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdedispSetChirp": [ctypes.POINTER(ctypes.c_float)],
     "xengCdedispRun": [_vp, _vp, _pi], "xengCdedispReset": [], "xengCdedispGetInfo": [_pi, _pi, _pll, _pll],
     "xengCdlongInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdlongSetChirp": [_i, ctypes.POINTER(ctypes.c_float)],
@@ -179,7 +183,9 @@ MORE_ENGINES = [("Plong", "plong", True)]
 NEWER_ENGINES = [("Accel", "accel", True)]
 # ... and since tests/test_accel_cpu.py pinned NEWER_ENGINES
 NEWEST_ENGINES = [("Candfold", "candfold", True)]
-for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES:
+# ... and since tests/test_candfold_cpu.py pinned NEWEST_ENGINES
+LATEST_ENGINES = [("Rfi", "rfi", True)]
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES:
     SYMBOLS.update({"xeng%sMark" % _c: [ctypes.POINTER(ctypes.c_ulonglong)], "xeng%sWait" % _c: [ctypes.c_ulonglong],
                     "xeng%sTicketDone" % _c: [ctypes.c_ulonglong, _pi], "xeng%sSync" % _c: [], "xeng%sDestroy" % _c: []})
     if _guards:
@@ -225,7 +231,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengUpchanSpectraRun", "xengUpchanSpectraRunParts", "xengUpchanSpectraPrime", "xengUpchanSpectraPrimeParts", "xengUpchanSpectraReset",
                 "xengDedispRun", "xengDedispReset", "xengPulseRun", "xengPulseReset", "xengFoldRun", "xengFoldReset", "xengPeriodRun", "xengPeriodReset",
                 "xengPlongRun", "xengPlongReset", "xengAccelRun", "xengAccelReset",
-                "xengFfaRun", "xengFfaReset", "xengCandfoldRun", "xengCandfoldReset", "xengCdedispRun", "xengCdedispReset", "xengCdlongRun", "xengCdlongReset",
+                "xengFfaRun", "xengFfaReset", "xengCandfoldRun", "xengCandfoldReset", "xengRfiRun", "xengRfiReset", "xengCdedispRun", "xengCdedispReset", "xengCdlongRun", "xengCdlongReset",
                 "xengImageRun", "xengGaincalRun", "xengCalapplyRun", "xengPeelRun", "xengCleanRun", "xengFlagRun", "xengPredictRun",
                 "xengImsearchRun", "xengImsearchReset",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
@@ -234,7 +240,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengRingCommitExternal", "xengRingNextSequence", "xengRingAcquire", "xengRingAcquireParts", "xengRingSpanRelease", "xengRingGetInfo",
                 "xengRingOpenReader", "xengRingCloseReader", "xengRingResize",
                 "xengStampNow", "xengStampNowFor", "xengStampDone", "xengGetDevice", "xengSetDevice"]
-for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES:     # an event record and an event query: neither can wait
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES:     # an event record and an event query: neither can wait
     ENQUEUE_ONLY += ["xeng%sMark" % _c, "xeng%sTicketDone" % _c]
 _enq = None
 

@@ -1190,6 +1190,82 @@ int xengCandfoldTicketDone(unsigned long long ticket, int *done);
 int xengCandfoldSync(void);
 int xengCandfoldDestroy(void);
 
+/* ---------------------------------------------------------------- Cleaning of the fine-channel power beams
+ * BeamRfiClean (no reference counterpart): the power beams of UpchanSumBeams / UpchanBeamform(dual_pol) are normalised by a
+ * bandpass measured per block of nstat windows, channels whose statistics stand out are dropped for that block, single samples
+ * and whole windows that stand out are zeroed, and the mean over the channels (the zero-DM series) is taken off every window.  The
+ * output has the input's format and is nstat windows late, so xengDedispRun and xengFoldRun read it unchanged.
+ * Everything is fp32; fl() is one rounding, and nothing is contracted into an fma.
+ *   in       f32[nwin_call][npair][nfine][4] = [XX, YY, Re XY*, Im XY*], as xengDedispRun takes it; 16-byte aligned, never written
+ *   out      the same shape and format; stats i32[nwin_call][npair][4], 16-byte aligned
+ *   n        counts windows since the last reset.  out[i] of a call that starts at window n0 is the cleaned window n0 + i - nstat;
+ *            for n0 + i < nstat the four words of every channel are +0 and stats = {0, 0, 4, 0}.
+ *   sizes    1 <= npair <= 65535, 4 <= nfine <= 8192, 2 <= nstat <= 2^20, 1 <= nwin <= nstat, 1 <= nwin_call <= nwin, and the
+ *            history of nstat + nwin windows below XENG_RFI_MAX_HISTORY_BYTES.
+ *   control  k_chan (channel threshold, in units of the median absolute deviation; the host folds in 1.4826), t_clip (sample
+ *            threshold on z; the host folds in sqrt 2), t_broad (the host folds in sqrt 2), all finite and > 0; min_count in
+ *            0..nfine; zerodm 0 or 1.  mask u8[nfine]: non-zero leaves the channel out.  Controls and mask hold from the next
+ *            block to be decided: a block is decided by the call that takes its last window, with what stands at that call.
+ *   baseline of block k = windows [k nstat, (k+1) nstat), per (pair, channel, word w): at the block's first window c_w = x_w,
+ *            a_w = +0, and for w in {0, 1} s_w = +0.  For every window of the block in ascending n, the first included:
+ *              d = fl(x_w - c_w);  a_w = fl(a_w + d);  s_w = fl(s_w + fl(d d)) for w in {0, 1}.
+ *            At the block's end, with r = 1.0f / (float)nstat formed on the host: m_w = fl(a_w r),
+ *            v_w = fl(fl(s_w r) - fl(m_w m_w)) for w in {0, 1}.
+ *   decision per (pair, block): mu = fl(fl(c_0 + m_0) + fl(c_1 + m_1)), V = fl(v_0 + v_1), R = fl(V / fl(mu mu)): the variance
+ *            of the total power over its squared mean, flat across a clean band whatever the bandpass.  A channel is live iff
+ *            its mask byte is 0, the four m_w are finite, 0 < v_0, v_1 < +inf, mu > 0 and R is finite.  med is the median of R
+ *            over the live channels: ranked by a sortable key of fl(R + 0) (-0 as +0), ties by index; the value of rank n/2 for
+ *            odd n, 0.5f (lo + hi) of ranks (n-1)/2 and n/2 for even n, +0 for n = 0.  dev = |fl(R - med)|, mad the median of dev
+ *            by the same rule.  A live channel is an outlier iff dev > fl(k_chan mad).  Flag byte: bit 0 the mask, bit 1 one of
+ *            the other conditions of "live" fails (whether or not the channel is masked), bit 2 outlier.  A channel is kept iff
+ *            its byte is 0.  Gains of a kept channel: g_0 = fl(1 / fl(sqrt v_0)), g_1 from v_1, g_2 = g_3 = fl(sqrt fl(g_0 g_1))
+ *            -- power gains per hand and their geometric mean on the cross words, what a voltage gain per hand does; the gains of
+ *            every other channel read +0.  Division and square root are correctly rounded.
+ *   apply    per window n of a decided block and per pair, with the block's tables and the controls it was decided under:
+ *            on kept channels y_w = fl(fl(fl(x_w - c_w) - m_w) g_w), z = fl(y_0 + y_1); the sample is clipped iff some y_w is
+ *            not finite or !(|z| <= t_clip).  K = the kept, unclipped channels, count = |K|.  Sums over K per word in a fixed
+ *            order: chain t in [0, 256) starts from +0 and takes channels q = t (mod 256) ascending (a channel outside K enters
+ *            as +0); then P_t = fl(P_t + P_{t+h}) for t < h, h = 128, 64, .. 1; Z_w = P_0.  zm_w = fl(Z_w / (float)count), +0 at
+ *            count = 0.  The window has code 1 iff count < min_count; otherwise code 2 iff
+ *            |fl(Z_0 + Z_1)| > fl(t_broad fl(sqrt (float)count)); otherwise 0.  A window with a code writes +0 everywhere.
+ *            Otherwise a channel in K writes fl(y_w - zm_w) with zerodm, y_w without, and every other channel four +0.
+ *            stats = {count, clipped samples among kept channels, code, channels not kept in the block}.
+ *            A +0 is the mean of a normalised channel: excised data is zero, not NaN, and the dedisperser's sums need no weights.
+ *   state    between two guard bands of 64 KiB: a ring of nstat + nwin windows in the input's layout, the running {c, a, s},
+ *            and two halves of block tables {c, m, v, g, flag, mu, V, R} that change places block by block (a call applies at
+ *            most two blocks, and the newer one completes inside that call), the mask.
+ * xengRfiReset moves the host's counts; it launches and clears nothing: the kernels decide by index what lies before window 0.
+ * Everything is a fixed function of the window stream, the mask and the controls: bit-identical however a run is split over calls,
+ * after a Reset as in a fresh context, and whatever else runs on the GPU.
+ * Rejected at Initialize, before any device is touched: every size outside the ranges above, a history of
+ * XENG_RFI_MAX_HISTORY_BYTES or more.  Rejected by SetControl: a float that is not finite and > 0, zerodm outside {0, 1},
+ * min_count outside 0..nfine.  Rejected by Run without a launch: a NULL or misaligned pointer, nwin_call outside 1..nwin.  Every
+ * call without a context, Run before the first SetControl, GetBlock before a block is decided: XENG_STATUS_INVALID_STATE.
+ * Not built: statistics re-estimated after clipping (a burst inflates its own block's v; the test on R then drops the channel for
+ * that block), a test along time between blocks, a smooth-bandpass test on mu, a flush of the last nstat windows, a mask ring. */
+#define XENG_RFI_MAX_HISTORY_BYTES (1LL << 32)
+int xengRfiInitialize(int gpu, int npair, int nfine, int nwin, int nstat);
+int xengRfiSetControl(float k_chan, float t_clip, float t_broad, int min_count, int zerodm);
+/* host array u8[nfine], or NULL for no channel left out.  Waits for the context's work in flight */
+int xengRfiSetMask(const unsigned char *mask);
+/* enqueue only: the three launches (the decision only on a call that takes a block's last window: *completed = 1) */
+int xengRfiRun(const void *in_dev, int nwin_call, void *out_dev, void *stats_dev, int *completed);
+/* the host's counts only */
+int xengRfiReset(void);
+/* windows taken and blocks decided since the last reset */
+int xengRfiGetInfo(long long *nwindows_since_reset, long long *nblocks_decided);
+/* waits for the context's work in flight; the newest decided block's tables: flags u8[npair][nfine], mu, var (V) and r
+ * f32[npair][nfine], gains f32[npair][nfine][4] */
+int xengRfiGetBlock(unsigned char *flags, float *mu, float *var, float *r, float *gains);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengRfiCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengRfiMark(unsigned long long *ticket);
+int xengRfiWait(unsigned long long ticket);
+int xengRfiTicketDone(unsigned long long ticket, int *done);
+int xengRfiSync(void);
+int xengRfiDestroy(void);
+
 /* ---------------------------------------------------------------- Coherent dedispersion of the voltage beams
  * BeamCoherentDedisperse (no reference counterpart): every (coarse channel, selected beam) row of the voltage beams is filtered by
  * overlap-save with a table given in the frequency domain, and comes out in the format it came in.  The library knows nothing of
