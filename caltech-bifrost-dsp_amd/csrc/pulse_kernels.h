@@ -66,15 +66,19 @@ __global__ __launch_bounds__(256) void pulse_search_kernel(const float* __restri
     float* G = ps_lds + (size_t)R * PS_SERIES + lane;
     const int s = blockIdx.x * PS_SERIES + lane;
     const bool live = s < nser;
-    const int sc = live ? s : nser - 1;             // (idle lanes read what a live lane reads and store nothing)
+    const int sc = live ? s : nser - 1;             // (idle lanes read the input and the ring where a live lane does and store nothing)
     const float nan = __int_as_float(0x7fc00000);
 
     if (j == 0) {
         bool prev = n0 >= nstat;                    // the window's block has a block before it
         int pos = pos0;
-        float dc = state[(size_t)PS_DC * nser + sc], dm = state[(size_t)PS_DM * nser + sc], dv = state[(size_t)PS_DV * nser + sc],
-              dg = state[(size_t)PS_DG * nser + sc];
-        float rc = state[(size_t)PS_RC * nser + sc], ra = state[(size_t)PS_RA * nser + sc], rq = state[(size_t)PS_RQ * nser + sc];
+        // (an idle lane takes no state: a clamped read would take the words the last live lane writes below, with no barrier between)
+        float dc = 0.f, dm = 0.f, dv = 0.f, dg = 0.f, rc = 0.f, ra = 0.f, rq = 0.f;
+        if (live) {
+            dc = state[(size_t)PS_DC * nser + s]; dm = state[(size_t)PS_DM * nser + s]; dv = state[(size_t)PS_DV * nser + s];
+            dg = state[(size_t)PS_DG * nser + s];
+            rc = state[(size_t)PS_RC * nser + s]; ra = state[(size_t)PS_RA * nser + s]; rq = state[(size_t)PS_RQ * nser + s];
+        }
         bool ok = prev && dv > 0.f && dv < __int_as_float(0x7f800000);
 #pragma unroll 4
         for (int i = 0; i < nc; i++) {

@@ -4,11 +4,14 @@ the record of a call.
 
 pulse_search(z, nstat, nwidth, dtype, sizes) is vectorised over the series.  dtype = np.float64 is the tolerance reference (every
 step in float64, rho and g exact to float64).  dtype = np.float32 follows the contract's roundings one by one: every fl() is a
-float32 operation and fmaf(a, b, c) is float32(float64(a) * float64(b) + float64(c)) -- the product of two float32 is exact in
-float64, so this is the fused result whenever the float64 sum is exact too, which holds on the integer data the word-for-word
-tests use; g = float32(1) / sqrt(v) in float32, the library's documented choice.  pulse_search_naive is the same definition one
+float32 operation and fmaf(a, b, c) is the correctly rounded fused multiply-add of tests/fold_ref.py (fmaf32: the exact product, the
+sum rounded to odd in float64, one rounding to float32), so the float32 mode is the contract's value on any data, float data
+included, not only on the integer data of the word-for-word tests; g = float32(1) / sqrt(v) in float32, the library's documented
+choice.  pulse_search_naive is the same definition one
 term at a time, with a mask for "has a y" where the vectorised version has one too (no NaN sentinel in either)."""
 import numpy as np
+
+from tests.fold_ref import fmaf32
 
 NONE = (0.0, -1, -1, 0.0)           # the record of a series with nothing scored in the call
 
@@ -24,7 +27,7 @@ def series(x, dtype=np.float64):
 def _fma(a, b, c, dtype):
     if dtype == np.float64:
         return a * b + c
-    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+    return fmaf32(a, b, c)
 
 
 def rho(iw, dtype):
@@ -34,19 +37,27 @@ def rho(iw, dtype):
     return np.float32(r) if dtype == np.float32 else r
 
 
+def block_chain(zb, dtype):
+    """(c, a, q) of the contract after the first zb.shape[1] windows of a block, zb [nblocks][windows][nser]: the pivot and the
+    two running sums (the state of a block that is not complete yet)."""
+    with np.errstate(all='ignore'):
+        c = zb[:, 0].copy()
+        a = np.zeros_like(c)
+        q = np.zeros_like(c)
+        for i in range(zb.shape[1]):
+            d = (zb[:, i] - c).astype(dtype)
+            a = (a + d).astype(dtype)
+            q = _fma(d, d, q, dtype)
+    return c, a, q
+
+
 def baseline_blocks(z, nstat, dtype):
     """(c, m, v, valid, g) of every complete block, [nblocks][nser] each."""
     nb = z.shape[0] // nstat
     zb = z[:nb * nstat].reshape(nb, nstat, z.shape[1])
     r = dtype(np.float32(1.0) / np.float32(nstat)) if dtype == np.float32 else 1.0 / nstat
     with np.errstate(all='ignore'):
-        c = zb[:, 0].copy()
-        a = np.zeros_like(c)
-        q = np.zeros_like(c)
-        for i in range(nstat):
-            d = (zb[:, i] - c).astype(dtype)
-            a = (a + d).astype(dtype)
-            q = _fma(d, d, q, dtype)
+        c, a, q = block_chain(zb, dtype)
         m = (a * r).astype(dtype)
         v = _fma(-m, m, (q * r).astype(dtype), dtype)
         valid = (v > 0) & (v < np.inf)
@@ -56,7 +67,7 @@ def baseline_blocks(z, nstat, dtype):
 
 def pulse_search(z, nstat, nwidth, dtype=np.float64, sizes=None):
     """z: [nwindows][...] (the trailing axes are the series).  Returns a dict: 'snr', 'B' [nwindows][nwidth][...] (NaN where
-    not scored), 'scored' (bool, same shape), 'c', 'm', 'v', 'valid' [nblocks][...], and, with `sizes` (the windows of the
+    not scored), 'scored' (bool, same shape), 'c', 'm', 'v', 'valid', 'g' [nblocks][...], and, with `sizes` (the windows of the
     consecutive calls), 'records': per call a dict of 'snr', 'n', 'iw', 'B' [...]."""
     z = np.asarray(z).astype(dtype)
     shape = z.shape[1:]
@@ -95,7 +106,7 @@ def pulse_search(z, nstat, nwidth, dtype=np.float64, sizes=None):
             Bs[:, iw] = np.where(ok, B, np.nan)
     out = dict(snr=snr.reshape((nwindows, nwidth) + shape), B=Bs.reshape((nwindows, nwidth) + shape),
                scored=scored.reshape((nwindows, nwidth) + shape), c=c.reshape((-1,) + shape), m=m.reshape((-1,) + shape),
-               v=v.reshape((-1,) + shape), valid=valid.reshape((-1,) + shape))
+               v=v.reshape((-1,) + shape), valid=valid.reshape((-1,) + shape), g=g.reshape((-1,) + shape))
     if sizes is not None:
         assert sum(sizes) == nwindows
         recs, a = [], 0

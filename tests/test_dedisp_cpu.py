@@ -14,7 +14,8 @@ from caltech_bifrost_dsp_amd import ffi, ring
 from caltech_bifrost_dsp_amd.blocks import BeamDedisperse, dm_delays
 from caltech_bifrost_dsp_amd.blocks.dedisp import KDM
 from caltech_bifrost_dsp_amd.ring import Ring
-from tests.dedisp_ref import dedisperse, dedisperse_naive
+from tests import dedisp_cases
+from tests.dedisp_ref import dedisperse, dedisperse_naive, dedisperse_one_chain32, dedisperse_ordered32
 from tests.fake_backend import OracleBackend
 from tests.pipeline_util import LOG, Sink, Source, run_blocks, source_header
 from tests.test_upchan_pfb_cpu import _FakeRing, _FakeSeq
@@ -171,6 +172,36 @@ def test_restatement_recovers_an_injected_pulse():
     assert np.unravel_index(y.argmax(), y.shape) == (t0 + S, d0) and y[t0 + S, d0] == nfine * (amp + 2)
     y[t0 + S, d0] = 0
     assert y.max() < nfine * (amp + 2) // 2
+
+
+@pytest.mark.parametrize("nprod", [1, 4])
+@pytest.mark.parametrize("case", sorted(dedisp_cases.CASES))
+def test_ordered_float32_restatement_is_exact_on_integers_and_within_the_bound_on_floats(case, nprod):
+    """dedisperse_ordered32 (the contract's order in float32 steps): on integer data and weights below 2^24 it is the int64
+    restatement word for word; on the float case, NaN in the zero-weight channels, it is finite and within the a-priori bound
+    (nfine + 2) * 2^-24 * sum |w x| of the float64 restatement, which any order of an fp32 sum keeps."""
+    x, s, w = dedisp_cases.float_case(case, nprod)
+    rng = np.random.default_rng(5)
+    xi = rng.integers(-5 if nprod == 4 else 0, 10, x.shape).astype(np.float32)
+    wi = rng.integers(0, 4, w.size).astype(np.float32)
+    exact = dedisperse(xi, s, wi, nprod, np.int64)
+    got = dedisperse_ordered32(xi, s, wi, nprod)
+    assert got.dtype == np.float32 and np.abs(exact).max() < 2 ** 24 and np.array_equal(got.astype(np.int64), exact)
+    got = dedisperse_ordered32(x, s, w, nprod)
+    assert np.isfinite(got).all()
+    bound = (x.shape[2] + 2) * 2.0 ** -24 * dedisperse(x, s, w, nprod, absolute=True)
+    assert (np.abs(got.astype(np.float64) - dedisperse(x, s, w, nprod)) <= bound).all()
+
+
+@pytest.mark.parametrize("nprod", [1, 4])
+def test_float_data_tell_the_contracts_order_from_one_ascending_chain(nprod):
+    """On float case (a) one chain over all 70 channels gives other words than four segments added pairwise in more than half
+    of the outputs: a test that holds this case bit for bit pins the order."""
+    x, s, w = dedisp_cases.float_case("a", nprod)
+    a, b = dedisperse_ordered32(x, s, w, nprod), dedisperse_one_chain32(x, s, w, nprod)
+    assert np.mean(a.view(np.uint32) != b.view(np.uint32)) > 0.5
+    bound = (x.shape[2] + 2) * 2.0 ** -24 * dedisperse(x, s, w, nprod, absolute=True)
+    assert (np.abs(b.astype(np.float64) - dedisperse(x, s, w, nprod)) <= bound).all()         # (the a-priori bound passes either order)
 
 
 # ---------------------------------------------------------------- the block on CPU rings

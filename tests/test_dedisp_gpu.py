@@ -1,7 +1,8 @@
 """BeamDedisperse on the MI355X: xengDedisp* against the restatement (tests/dedisp_ref.py).  Word for word on integer data
 (both products, S = 0, S beyond a call, a ring wrapped several times, ragged sizes, more windows than a wave has lanes, the live
 shape with an injected dispersed pulse); bit identity across splits of a run over calls, after Reset against a fresh context
-and beside an X-engine contraction and xengBeamformRun; NaN / Inf in zero-weight channels; float data against the a-priori
+and beside an X-engine contraction and xengBeamformRun; float data word for word against the contract's summation order in
+float32 steps (dedisperse_ordered32); NaN / Inf in zero-weight channels; float data against the a-priori
 bound of an fp32 sum and the house bar of 1e-5 of the RMS; guard bands around every output and around the history; the checks
 that need a context; and Beamform -> UpchanSumBeams -> BeamDedisperse on device rings beside BeamformSumBeams.  No wall-clock
 assertions."""
@@ -16,7 +17,8 @@ import caltech_bifrost_dsp_amd  # noqa: E402,F401
 from caltech_bifrost_dsp_amd import ffi  # noqa: E402
 from caltech_bifrost_dsp_amd.blocks import Beamform, BeamDedisperse, BeamformSumBeams, UpchanSumBeams, dm_delays  # noqa: E402
 from caltech_bifrost_dsp_amd.ring import Ring  # noqa: E402
-from tests.dedisp_ref import dedisperse  # noqa: E402
+from tests import dedisp_cases  # noqa: E402
+from tests.dedisp_ref import dedisperse, dedisperse_ordered32  # noqa: E402
 from tests.gpu_util import Xgpu, synth_voltages  # noqa: E402
 from tests.pipeline_util import LOG, Sink, Source, run_blocks, source_header  # noqa: E402
 from tests.test_blocks_cpu import _beam_cmds  # noqa: E402
@@ -243,6 +245,25 @@ def test_bit_identical_across_splits_reset_and_concurrent_kernels(nprod):
     for o in outs:
         assert np.array_equal(a.view(np.uint32), o.view(np.uint32))
     assert np.isfinite(a).all()
+
+
+@pytest.mark.parametrize("nprod", [1, 4])
+@pytest.mark.parametrize("case", ["a", "b", "c"])
+def test_float_data_match_the_contracts_summation_order_bit_for_bit(case, nprod):
+    """The public summation order on the device: float data (weights in [0.5, 1.5] with an eighth 0, NaN in those channels) in
+    the calls of tests/dedisp_cases.py -- (a) nfine 70, Q = 18, ragged tiles, a ring of 16 slots wrapped three times; (b) fewer
+    channels than segments; (c) more windows than a wave has lanes -- equal the ordered float32 restatement (four segments, one
+    fmaf a channel from +0, ((P0 + P1) + P2) + P3) as uint32 words.  One ascending chain over all channels differs from it in
+    most words of case (a) (tests/test_dedisp_cpu.py), and so would a product that is not fused."""
+    c = dedisp_cases.CASES[case]
+    x, s, w = dedisp_cases.float_case(case, nprod)
+    dd = DD(c["npair"], c["nfine"], c["nwin"], c["ndm"], c["S"], nprod, s, w)
+    got = dd.stream(x, c["calls"])
+    dd.close()
+    exp = dedisperse_ordered32(x, s, w, nprod)
+    diff = got.view(np.uint32) != exp.view(np.uint32)
+    print("dedisp ordered case %s nprod=%d: %d of %d words differ" % (case, nprod, diff.sum(), diff.size))
+    assert np.isfinite(got).all() and not diff.any(), "%d of %d words differ, first at %s" % (diff.sum(), diff.size, np.argwhere(diff)[:1])
 
 
 @pytest.mark.parametrize("nprod", [1, 4])

@@ -2,9 +2,10 @@
 products, series that do not fill a work-group, no tail and a tail longer than any call, calls of 1, 7 and 30 windows that put
 block boundaries at their first, an inner and their last window); bit identity across splits of a run over calls, after Reset
 against a fresh context and beside an X-engine contraction and xengBeamformRun; float data against the float64 restatement at
-tol = 1e-4 * max(1, |snr|); series without a baseline; tickets and the checks that need a context; the live shape with a planted
-pulse; and Source -> BeamDedisperse -> BeamPulseSearch on device rings.  The output sits between two poisoned guard bands that
-are checked after every call, the state's guards at every close.  No wall-clock assertions."""
+tol = 1e-4 * max(1, |snr|), and the baseline's c, m, v and every record's B bit for bit against the float32 restatement; series
+without a baseline; tickets and the checks that need a context; the live shape with a planted pulse; and Source ->
+BeamDedisperse -> BeamPulseSearch on device rings.  The output sits between two poisoned guard bands that are checked after
+every call, the state's guards at every close.  No wall-clock assertions."""
 import ctypes
 
 import numpy as np
@@ -19,6 +20,7 @@ from caltech_bifrost_dsp_amd.blocks.pulse_search import RECORD, as_records  # no
 from caltech_bifrost_dsp_amd.ring import Ring  # noqa: E402
 from tests.gpu_util import Xgpu, synth_voltages  # noqa: E402
 from tests.pipeline_util import LOG, Sink, Source, run_blocks  # noqa: E402
+from tests.pulse_cases import FIXED_SIZES, INT_CASES, _sizes, float_case, integer_case  # noqa: E402,F401
 from tests.pulse_ref import merge_records, pulse_search, series  # noqa: E402
 
 POISON = 0xA5
@@ -109,47 +111,7 @@ def merged_bits(planes, sizes):
     return out.tobytes()
 
 
-def _sizes(rng, total, nwin, choices=None):
-    out = []
-    while total:
-        nc = int(rng.choice(choices)) if choices else int(rng.integers(1, nwin + 1))
-        out.append(min(total, nc))
-        total -= out[-1]
-    return out
-
-
 # ---------------------------------------------------------------- 1. word for word on integer data
-INT_CASES = {
-    # npair, ndm, nprod, nwidth, nstat, windows, seed (checked on the CPU: every winner leads, see integer_case)
-    "111 series, I, 4 widths": (3, 37, 1, 4, 16, 110, 0),
-    "128 series, XX+YY, 4 widths": (2, 64, 4, 4, 16, 110, 0),
-    "111 series, XX+YY, no tail": (3, 37, 4, 1, 16, 110, 0),
-    "128 series, I, a tail of 127 windows": (2, 64, 1, 8, 128, 512, 3),
-    "111 series, XX+YY, a tail of 127 windows": (3, 37, 4, 8, 128, 512, 10),
-}
-FIXED_SIZES = [7, 1, 1, 7, 1, 30, 1, 1, 7, 7, 1, 1, 30, 7, 1, 1, 1, 1, 1, 1, 1, 1]       # 110 windows
-
-
-def integer_case(name):
-    """(x, sizes, float32 restatement, float64 reference) of a case.  Values 0..49; per series two planted box pulses of
-    amplitude 40-200 per window.  With nstat = 16 the calls are FIXED_SIZES: windows 0, 16, 48, 64 are the first window of a call,
-    32 and 80 inner ones, 16, 63, 64 the last (window 15, a block's last, ends a call too); with nstat = 128 a random sequence
-    of 1, 7 and 30."""
-    npair, ndm, nprod, nwidth, nstat, total, seed = INT_CASES[name]
-    rng = np.random.default_rng([seed, sorted(INT_CASES).index(name)])
-    x = rng.integers(0, 50, (total, npair, ndm, nprod)).astype(np.float32)
-    for p in range(npair):
-        for d in range(ndm):
-            for _ in range(2):
-                w = 1 << int(rng.integers(0, nwidth))
-                n1 = int(rng.integers(nstat + w, total))
-                x[n1 - w + 1:n1 + 1, p, d, 0] += float(rng.integers(40, 201))
-    sizes = FIXED_SIZES if nstat == 16 else _sizes(rng, total, 30, (1, 7, 30))
-    assert sum(sizes) == total >= 3 * nstat + (1 << (nwidth - 1)) and {1, 7, 30} <= set(sizes)
-    z32, z64 = series(x, np.float32), series(x, np.float64)
-    return x, sizes, pulse_search(z32, nstat, nwidth, np.float32, sizes), pulse_search(z64, nstat, nwidth, np.float64, sizes)
-
-
 def winners_lead(ref, sizes):
     """On the float64 reference: in every call of every series, every scored candidate other than the winner either trails it
     by more than tol, or holds EXACTLY the winner's score.  Integer data make exact ties common -- equal sums at two windows, or
@@ -205,18 +167,6 @@ def test_integer_data_match_the_restatement_word_for_word(case):
 
 
 # ---------------------------------------------------------------- 2. bit identity
-def float_case(rng, nwindows, npair, ndm, nprod):
-    """chi^2 powers summed over 3072 channels (4 degrees of freedom each: mean / sigma = 78) times a gain in [0.5, 1.5] per
-    series; with nprod = 4, XX and YY take half each and the cross terms are noise."""
-    gain = rng.uniform(0.5, 1.5, (npair, ndm))
-    if nprod == 1:
-        return (rng.chisquare(4 * 3072, (nwindows, npair, ndm)) * gain).astype(np.float32)[..., None]
-    x = rng.standard_normal((nwindows, npair, ndm, 4)) * 100
-    x[..., 0] = rng.chisquare(2 * 3072, (nwindows, npair, ndm)) * gain
-    x[..., 1] = rng.chisquare(2 * 3072, (nwindows, npair, ndm)) * gain
-    return x.astype(np.float32)
-
-
 @pytest.mark.parametrize("nprod", [1, 4])
 def test_bit_identical_across_splits_reset_and_concurrent_kernels(nprod):
     """540 windows of float data, nstat = 128, 8 widths: one call per 30 windows, 10 windows, 1 window and a random split give
@@ -309,6 +259,48 @@ def test_float_data_within_tol_of_the_float64_restatement(nprod, nstat, nwidth):
     ps.close()
     worst = check_against_float64(planes, sizes, ref, "float nprod=%d nstat=%d" % (nprod, nstat))
     print("pulse float nprod=%d nstat=%d nwidth=%d: worst |snr - ref| / max(1, |ref|) = %.3g (tol 1e-4)" % (nprod, nstat, nwidth, worst))
+
+
+@pytest.mark.parametrize("nprod", [1, 4])
+@pytest.mark.parametrize("nstat,nwidth", [(24, 5), (128, 8)])
+def test_float_data_hold_the_baseline_and_the_boxcar_sums_bit_for_bit(nstat, nwidth, nprod):
+    """The contract's roundings on the device, on float data: 3 x 37 series of float_case, calls of 30 windows and a ragged last
+    one.  After every call that completes a block GetBaseline's c, m and v equal the float32 restatement (delta = fl(z - c),
+    a = fl(a + delta), q = fmaf(delta, delta, q), m = fl(a r), v = fmaf(-m, m, fl(q r)), the fused steps correctly rounded) as
+    uint32 words; and each record's B equals the restatement's B at the record's own (n, iw) -- y = fl(fl(z - c) - m), not
+    contracted, and plain fp32 adds.  snr keeps tol() and a near-tie may resolve either way, as check_against_float64 has it."""
+    npair, ndm, nwin = 3, 37, 30
+    total = 4 * nstat + 17
+    rng = np.random.default_rng(127 + nprod + nstat)
+    x = float_case(rng, total, npair, ndm, nprod)
+    sizes = [nwin] * (total // nwin) + ([total % nwin] if total % nwin else [])
+    assert sizes[-1] < nwin
+    r64 = pulse_search(series(x, np.float64), nstat, nwidth, np.float64)
+    r32 = pulse_search(series(x, np.float32), nstat, nwidth, np.float32)
+    B32 = r32['B'].reshape(total, nwidth, -1)
+    ps = PS(npair, ndm, nwin, nprod, nwidth, nstat)
+    planes, a, nblocks = [], 0, 0
+    for nc in sizes:
+        before = a // nstat
+        planes.append(ps.run(x[a:a + nc]))
+        if (a + nc) // nstat > before:
+            blk = (a + nc) // nstat - 1
+            for g, f in zip(ps.baseline(), ('c', 'm', 'v')):
+                diff = g.view(np.uint32) != r32[f][blk].view(np.uint32)
+                print("pulse float nprod=%d nstat=%d block %d: %d of %d words of %s differ" % (nprod, nstat, blk, diff.sum(), diff.size, f))
+                assert not diff.any(), (f, blk, int(diff.sum()))
+            nblocks += 1
+        p = planes[-1].reshape(-1)
+        has = p['n'] >= 0
+        col = np.arange(p.size)[has]
+        exp = B32[a + p['n'][has], p['iw'][has], col]
+        diff = p['B'][has].view(np.uint32) != exp.view(np.uint32)
+        print("pulse float nprod=%d nstat=%d call at %d: %d of %d B differ" % (nprod, nstat, a, diff.sum(), diff.size))
+        assert not diff.any(), (a, int(diff.sum()))
+        a += nc
+    ps.close()
+    assert nblocks == 4 and all((pl['n'] >= 0).all() for pl in planes[-2:])
+    check_against_float64(planes, sizes, r64, "float bit for bit nprod=%d nstat=%d" % (nprod, nstat))
 
 
 # ---------------------------------------------------------------- 4. series without a baseline
