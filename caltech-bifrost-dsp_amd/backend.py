@@ -695,6 +695,37 @@ class HipBackend:
                  gains.ctypes.data_as(pf))
         return flags, mu, var, r, gains
 
+    # ---- baseline removal of the dedispersed beams (BeamDetrend; include/xeng.h "Baseline removal of the dedispersed beams"): a context
+    # of its own, its kernels on the beamformer's stream
+    def detrend_initialize(self, gpu, npair, ndm, nwin, nprod, nblk, normalise, k_mad):
+        """k_mad as the library takes it (blocks/detrend.py detrend_k_mad folds in 1.4826)."""
+        return self._lib.xengDetrendInitialize(int(gpu), int(npair), int(ndm), int(nwin), int(nprod), int(nblk), int(bool(normalise)), float(k_mad))
+
+    def detrend_run(self, in_arr, nwin_call, out_arr):
+        """Enqueue only: f32 [nwin_call][npair][ndm][nprod] in, f32 [nwin_call][npair][ndm] out; (status, completed): the call decided
+        a block.  The output is the detrended input 3 nblk / 2 windows earlier; detrend_mark / wait cover it."""
+        done = ctypes.c_int(0)
+        rv = self._enq.xengDetrendRun(in_arr.ptr, int(nwin_call), out_arr.ptr, ctypes.byref(done))
+        return rv, done.value
+
+    def detrend_reset(self):
+        """The next input counts as window 0 (host state only)."""
+        ffi.check("xengDetrendReset", self._enq.xengDetrendReset())
+
+    def detrend_info(self):
+        """(windows taken since the last reset, blocks decided since the reset)"""
+        n, k = ctypes.c_longlong(), ctypes.c_longlong()
+        ffi.call("xengDetrendGetInfo", ctypes.byref(n), ctypes.byref(k))
+        return n.value, k.value
+
+    def detrend_knots(self, npair, ndm):
+        """Waits for the context's work; the newest decided block's knots: (M, A float32, valid uint8, each [npair][ndm])."""
+        M, A = (np.empty((npair, ndm), np.float32) for _ in range(2))
+        valid = np.empty((npair, ndm), np.uint8)
+        pf = ctypes.POINTER(ctypes.c_float)
+        ffi.call("xengDetrendGetKnots", M.ctypes.data_as(pf), A.ctypes.data_as(pf), valid.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
+        return M, A, valid
+
     # ---- coherent dedispersion of the voltage beams (BeamCoherentDedisperse; include/xeng.h "Coherent dedispersion of the voltage
     # beams"): a context of its own, its kernels on the beamformer's stream
     def cdedisp_initialize(self, gpu, nchan, nbeam, ntime, pair0, npair, nfft, overlap):
@@ -1023,7 +1054,7 @@ class HipBackend:
         ffi.call("xengImsearchGetBaseline", *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for a in out])
         return tuple(out)
 
-    # ---- completion tickets and guard bands of the engines of ffi.ENGINES, ffi.MORE_ENGINES, ffi.NEWER_ENGINES, ffi.NEWEST_ENGINES and ffi.LATEST_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
+    # ---- completion tickets and guard bands of the engines of ffi.ENGINES, ffi.MORE_ENGINES, ffi.NEWER_ENGINES, ffi.NEWEST_ENGINES, ffi.LATEST_ENGINES and ffi.FURTHER_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
     # _guards_intact are made from these below the class
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
@@ -1079,7 +1110,7 @@ def _engine_methods(cname, prefix, guards):
     return {"%s_%s" % (prefix, k): f for k, f in fs.items()}
 
 
-for _row in ffi.ENGINES + ffi.MORE_ENGINES + ffi.NEWER_ENGINES + ffi.NEWEST_ENGINES + ffi.LATEST_ENGINES:
+for _row in ffi.ENGINES + ffi.MORE_ENGINES + ffi.NEWER_ENGINES + ffi.NEWEST_ENGINES + ffi.LATEST_ENGINES + ffi.FURTHER_ENGINES:
     for _name, _f in _engine_methods(*_row).items():
         _f.__name__ = _name
         _f.__qualname__ = "HipBackend." + _name

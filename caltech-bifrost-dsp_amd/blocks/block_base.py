@@ -164,7 +164,8 @@ class SpanLoop(object):
     run() is one input sequence.  Per whole span (a short final one is ignored), with t its first sample:
       a gap (t is not where the span before ended): on_gap(), the log line, the output sequence ends;
       before(t) loads what is pending and may answer RESTART (the output sequence ends here) or SKIP (the span is dropped);
-      the output sequence is begun if there is none, at time tag t with header(t);
+      the output sequence is begun if there is none, at time tag t + tag_offset with header(t + tag_offset) (tag_offset, in
+      samples, is for a block whose first committed span is a later input span than the one that begins the sequence);
       body(t, held, loop) enqueues the kernels on the input `held`.  It writes where loop.target(meta) says -- which reserves
       the output span -- or nowhere, and returns the stats it changes; 'last_end_sample' is added.
     The call is then pushed with its ticket, or waited for and finished.  An output sequence ends only after retire(0)."""
@@ -190,7 +191,7 @@ class SpanLoop(object):
             oseq, self._oseq = self._oseq, None
             oseq.end()
 
-    def run(self, iseq, seq0, igulp_size, ntime_gulp, ogulp_size, header, body, before=None, on_gap=None):
+    def run(self, iseq, seq0, igulp_size, ntime_gulp, ogulp_size, header, body, before=None, on_gap=None, tag_offset=0):
         block, inflight = self.block, self.inflight
         self._ogulp_size, self._oseq = ogulp_size, None
         if not self.streaming and (self._dev is None or self._dev.nbytes != ogulp_size):
@@ -220,7 +221,7 @@ class SpanLoop(object):
                     self._end_sequence()
                 held = ispan.data
                 if self._oseq is None:
-                    self._oseq = self.oring.begin_sequence(time_tag=this_gulp_time, header=json.dumps(header(this_gulp_time)))
+                    self._oseq = self.oring.begin_sequence(time_tag=this_gulp_time + tag_offset, header=json.dumps(header(this_gulp_time + tag_offset)))
                 curr_time = time.time()
                 acquire_time = curr_time - prev_time
                 prev_time = curr_time

@@ -130,6 +130,8 @@ SYMBOLS = {
     "xengRfiSetMask": [ctypes.POINTER(ctypes.c_ubyte)], "xengRfiRun": [_vp, _i, _vp, _vp, _pi], "xengRfiReset": [], "xengRfiGetInfo": [_pll, _pll],
     "xengRfiGetBlock": [ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                         ctypes.POINTER(ctypes.c_float)],
+    "xengDetrendInitialize": [_i, _i, _i, _i, _i, _i, _i, ctypes.c_float], "xengDetrendRun": [_vp, _i, _vp, _pi], "xengDetrendReset": [],
+    "xengDetrendGetInfo": [_pll, _pll], "xengDetrendGetKnots": [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_ubyte)],
     "xengCdedispInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdedispSetChirp": [ctypes.POINTER(ctypes.c_float)],
     "xengCdedispRun": [_vp, _vp, _pi], "xengCdedispReset": [], "xengCdedispGetInfo": [_pi, _pi, _pll, _pll],
     "xengCdlongInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdlongSetChirp": [_i, ctypes.POINTER(ctypes.c_float)],
@@ -185,7 +187,9 @@ NEWER_ENGINES = [("Accel", "accel", True)]
 NEWEST_ENGINES = [("Candfold", "candfold", True)]
 # ... and since tests/test_candfold_cpu.py pinned NEWEST_ENGINES
 LATEST_ENGINES = [("Rfi", "rfi", True)]
-for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES:
+# ... and since tests/test_rfi_cpu.py pinned LATEST_ENGINES
+FURTHER_ENGINES = [("Detrend", "detrend", True)]
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES + FURTHER_ENGINES:
     SYMBOLS.update({"xeng%sMark" % _c: [ctypes.POINTER(ctypes.c_ulonglong)], "xeng%sWait" % _c: [ctypes.c_ulonglong],
                     "xeng%sTicketDone" % _c: [ctypes.c_ulonglong, _pi], "xeng%sSync" % _c: [], "xeng%sDestroy" % _c: []})
     if _guards:
@@ -231,7 +235,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengUpchanSpectraRun", "xengUpchanSpectraRunParts", "xengUpchanSpectraPrime", "xengUpchanSpectraPrimeParts", "xengUpchanSpectraReset",
                 "xengDedispRun", "xengDedispReset", "xengPulseRun", "xengPulseReset", "xengFoldRun", "xengFoldReset", "xengPeriodRun", "xengPeriodReset",
                 "xengPlongRun", "xengPlongReset", "xengAccelRun", "xengAccelReset",
-                "xengFfaRun", "xengFfaReset", "xengCandfoldRun", "xengCandfoldReset", "xengRfiRun", "xengRfiReset", "xengCdedispRun", "xengCdedispReset", "xengCdlongRun", "xengCdlongReset",
+                "xengFfaRun", "xengFfaReset", "xengCandfoldRun", "xengCandfoldReset", "xengRfiRun", "xengRfiReset", "xengDetrendRun", "xengDetrendReset", "xengCdedispRun", "xengCdedispReset", "xengCdlongRun", "xengCdlongReset",
                 "xengImageRun", "xengGaincalRun", "xengCalapplyRun", "xengPeelRun", "xengCleanRun", "xengFlagRun", "xengPredictRun",
                 "xengImsearchRun", "xengImsearchReset",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
@@ -240,7 +244,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengRingCommitExternal", "xengRingNextSequence", "xengRingAcquire", "xengRingAcquireParts", "xengRingSpanRelease", "xengRingGetInfo",
                 "xengRingOpenReader", "xengRingCloseReader", "xengRingResize",
                 "xengStampNow", "xengStampNowFor", "xengStampDone", "xengGetDevice", "xengSetDevice"]
-for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES:     # an event record and an event query: neither can wait
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES + FURTHER_ENGINES:     # an event record and an event query: neither can wait
     ENQUEUE_ONLY += ["xeng%sMark" % _c, "xeng%sTicketDone" % _c]
 _enq = None
 

@@ -1266,6 +1266,68 @@ int xengRfiTicketDone(unsigned long long ticket, int *done);
 int xengRfiSync(void);
 int xengRfiDestroy(void);
 
+/* ---------------------------------------------------------------- Baseline removal of the dedispersed beams
+ * BeamDetrend (no reference counterpart): under every (pair, DM trial) series of xengDedispRun's output lies a slowly varying
+ * baseline that the searches behind assume away.  Per block of nblk windows and per series a knot is measured, the median and the
+ * median absolute deviation; every window then loses the straight line between the two knots around it and, with `normalise`, is
+ * scaled by the line between the knots' reciprocal scales.  The output is one word per series and 3 nblk / 2 windows late, in the
+ * format xengPulseRun, xengPeriodRun, xengPlongRun, xengAccelRun, xengFfaRun and xengCandfoldRun take at nprod = 1.
+ * Everything is fp32; fl() is one rounding, and nothing is contracted into an fma.
+ *   in       f32[nwin_call][npair][ndm][nprod], xengDedispRun's output, 16-byte aligned, never written.  z = in[..][0] at
+ *            nprod = 1, z = fl(XX + YY) at nprod = 4.  A series is one (pair, trial); nser = npair ndm <= 2^24.
+ *   out      f32[nwin_call][npair][ndm], 16-byte aligned: always one word per series.
+ *   sizes    nblk even, 4 <= nblk <= 8192; h = nblk/2, D = 3h; 1 <= nwin <= nblk, 1 <= nwin_call <= nwin; nprod 1 or 4; the
+ *            history of D + nwin windows of nser floats below XENG_DETREND_MAX_HISTORY_BYTES.  Given to Initialize beside the
+ *            sizes: normalise in {0, 1}; k_mad, finite and > 0 (the host folds in 1.4826); the library forms
+ *            r = 1.0f / (float)(2 nblk) on the host.  There are no run-time controls.
+ *   n        counts windows since the last reset.
+ *   knots    block k is the windows [k nblk, (k+1) nblk); its knot is decided by the call that takes its last window.  Per
+ *            series: M_k is the median of the block's z, A_k the median of |fl(z - M_k)|.  Both by one rule: the values are
+ *            ranked by a sortable key of fl(v + 0) (-0 as +0), lo and hi are the values fl(v + 0) of ranks nblk/2 - 1 and
+ *            nblk/2 (equal keys are equal values: ties need no rule), and the median is fl(0.5f fl(lo + hi)).
+ *            The knot is valid iff all nblk values z are finite and, with normalise, s = fl(k_mad A_k) satisfies 0 < s < +inf;
+ *            then G_k = fl(1.0f / s), correctly rounded.  A block with a z that is not finite has M_k = A_k = +0; G_k = +0
+ *            wherever the knot is not valid or nothing is normalised.
+ *   apply    out[i] of a call that starts at window n0 is the detrended window m = n0 + i - D; for m < 0 it is +0.  For m < h,
+ *            k = -1 and t = m + h; otherwise k = (m - h) div nblk and t = m - (k nblk + h).  The two knots are a = max(k, 0)
+ *            and b = k + 1; both are complete by the time window m + D has been taken: the latency is a constant.  If exactly
+ *            one of them is not valid the other stands for both; if neither is, the output is +0.  With
+ *            u = fl((float)(2t + 1) r):
+ *              base = fl(M_a + fl(u fl(M_b - M_a)));  y = fl(z - base);
+ *              with normalise, g = fl(G_a + fl(u fl(G_b - G_a))) and y = fl(y g).
+ *            A y that is not finite is written as +0: excised data is zero, as in the cleaner.
+ *   state    between two guard bands of 64 KiB: a ring of D + nwin windows per series, time the fastest axis, and four slots of
+ *            knot tables {M, A, G, valid} that blocks take in turn (a call reads the knots of at most three blocks, the newest
+ *            decided inside that call).
+ * xengDetrendReset moves the host's counts; it launches and clears nothing: the kernels decide by index what lies before window 0.
+ * Everything is a fixed function of the window stream: bit-identical however a run is split over calls, after a Reset as in a
+ * fresh context, and whatever else runs on the GPU.
+ * Rejected at Initialize, before any device is touched: every size outside the ranges above, normalise outside {0, 1}, a k_mad
+ * that is not finite and > 0, a history of XENG_DETREND_MAX_HISTORY_BYTES or more.  Rejected by Run without a launch: a NULL or
+ * misaligned pointer, nwin_call outside 1..nwin.  Every call without a context, GetKnots before a block is decided:
+ * XENG_STATUS_INVALID_STATE.
+ * Not built: a running median per sample instead of per-block knots, knots re-estimated after detected pulses are masked (a
+ * pulse shorter than nblk/2 windows cannot move the median; a longer one is baseline), a flush of the last D windows, spectral
+ * median whitening inside xengPlongRun. */
+#define XENG_DETREND_MAX_HISTORY_BYTES (1LL << 32)
+int xengDetrendInitialize(int gpu, int npair, int ndm, int nwin, int nprod, int nblk, int normalise, float k_mad);
+/* enqueue only: the three launches (the decision only on a call that takes a block's last window: *completed = 1) */
+int xengDetrendRun(const void *in_dev, int nwin_call, void *out_dev, int *completed);
+/* the host's counts only */
+int xengDetrendReset(void);
+/* windows taken and blocks decided since the last reset */
+int xengDetrendGetInfo(long long *nwindows_since_reset, long long *nblocks_decided);
+/* waits for the context's work in flight; the newest decided block's knots: M and A f32[npair][ndm], valid u8[npair][ndm] */
+int xengDetrendGetKnots(float *M, float *A, unsigned char *valid);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengDetrendCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengDetrendMark(unsigned long long *ticket);
+int xengDetrendWait(unsigned long long ticket);
+int xengDetrendTicketDone(unsigned long long ticket, int *done);
+int xengDetrendSync(void);
+int xengDetrendDestroy(void);
+
 /* ---------------------------------------------------------------- Coherent dedispersion of the voltage beams
  * BeamCoherentDedisperse (no reference counterpart): every (coarse channel, selected beam) row of the voltage beams is filtered by
  * overlap-save with a table given in the frequency domain, and comes out in the format it came in.  The library knows nothing of
