@@ -726,6 +726,48 @@ class HipBackend:
         ffi.call("xengDetrendGetKnots", M.ctypes.data_as(pf), A.ctypes.data_as(pf), valid.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
         return M, A, valid
 
+    # ---- dedispersed cut-outs of single pulses (BeamPulseCutout; include/xeng.h "Dedispersed cut-outs and DM refinement of single
+    # pulses"): a context of its own, its kernels on the beamformer's stream
+    def cutout_initialize(self, gpu, npair, nfine, nwin, ndmf, nhist, nband, nt, tscr, ndmc, nwidth, nreq_max, k_mad):
+        """k_mad as the library takes it (blocks/pulse_cutout.py cutout_k_mad folds in 1.4826)."""
+        return self._lib.xengCutoutInitialize(int(gpu), int(npair), int(nfine), int(nwin), int(ndmf), int(nhist), int(nband), int(nt), int(tscr), int(ndmc),
+                                              int(nwidth), int(nreq_max), float(k_mad))
+
+    def cutout_set_delays(self, delays):
+        """delays: host int32 [ndmf][nfine], C-contiguous, in windows.  Waits for the context's work in flight; clears the count and
+        the pending requests."""
+        return self._lib.xengCutoutSetDelays(delays.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+
+    def cutout_set_weights(self, weights):
+        """weights: host float32 [nfine] or None (all ones).  Waits for the context's work in flight; acts on the history held."""
+        return self._lib.xengCutoutSetWeights(_host_floats(weights))
+
+    def cutout_request(self, reqs):
+        """reqs: a host array of CUTOUT_REQUEST {id, pair, n_c, ic, dstep} (blocks/pulse_cutout.py): all taken, or none."""
+        reqs = np.ascontiguousarray(reqs)
+        if reqs.dtype.itemsize != 24 or reqs.ndim != 1:
+            raise ValueError("cutout_request: %r of %r is not a list of 24-byte requests" % (reqs.shape, reqs.dtype))
+        return self._enq.xengCutoutRequest(reqs.size, reqs.ctypes.data)
+
+    def cutout_run(self, in_arr, nwin_call, out_arr, nreq_max):
+        """Enqueue only: f32 [nwin_call][npair][nfine][4] in; (status, served ids in slot order, expired ids).  out_arr (records, then
+        the waterfalls, then the planes: cutout_info's bytes) is written only when the call serves a request and may be None
+        otherwise -- the status tells when it was needed; cutout_mark / wait cover it."""
+        ns, ne = ctypes.c_int(0), ctypes.c_int(0)
+        served, expired = (ctypes.c_int * int(nreq_max))(), (ctypes.c_int * 1024)()
+        rv = self._enq.xengCutoutRun(in_arr.ptr, int(nwin_call), None if out_arr is None else out_arr.ptr, ctypes.byref(ns), served, ctypes.byref(ne), expired)
+        return rv, list(served[:ns.value]), list(expired[:ne.value])
+
+    def cutout_reset(self):
+        """The next input counts as window 0; the pending requests are dropped (host state only)."""
+        ffi.check("xengCutoutReset", self._enq.xengCutoutReset())
+
+    def cutout_info(self):
+        """(windows taken since the last reset, requests waiting, bytes of a serving call's output)"""
+        n, k, b = ctypes.c_longlong(), ctypes.c_int(), ctypes.c_longlong()
+        ffi.call("xengCutoutGetInfo", ctypes.byref(n), ctypes.byref(k), ctypes.byref(b))
+        return n.value, k.value, b.value
+
     # ---- coherent dedispersion of the voltage beams (BeamCoherentDedisperse; include/xeng.h "Coherent dedispersion of the voltage
     # beams"): a context of its own, its kernels on the beamformer's stream
     def cdedisp_initialize(self, gpu, nchan, nbeam, ntime, pair0, npair, nfft, overlap):
@@ -1054,7 +1096,7 @@ class HipBackend:
         ffi.call("xengImsearchGetBaseline", *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for a in out])
         return tuple(out)
 
-    # ---- completion tickets and guard bands of the engines of ffi.ENGINES, ffi.MORE_ENGINES, ffi.NEWER_ENGINES, ffi.NEWEST_ENGINES, ffi.LATEST_ENGINES and ffi.FURTHER_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
+    # ---- completion tickets and guard bands of the engines of ffi.ENGINES, ffi.MORE_ENGINES, ffi.NEWER_ENGINES, ffi.NEWEST_ENGINES, ffi.LATEST_ENGINES, ffi.FURTHER_ENGINES and ffi.CUTOUT_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
     # _guards_intact are made from these below the class
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
@@ -1110,7 +1152,7 @@ def _engine_methods(cname, prefix, guards):
     return {"%s_%s" % (prefix, k): f for k, f in fs.items()}
 
 
-for _row in ffi.ENGINES + ffi.MORE_ENGINES + ffi.NEWER_ENGINES + ffi.NEWEST_ENGINES + ffi.LATEST_ENGINES + ffi.FURTHER_ENGINES:
+for _row in ffi.ENGINES + ffi.MORE_ENGINES + ffi.NEWER_ENGINES + ffi.NEWEST_ENGINES + ffi.LATEST_ENGINES + ffi.FURTHER_ENGINES + ffi.CUTOUT_ENGINES:
     for _name, _f in _engine_methods(*_row).items():
         _f.__name__ = _name
         _f.__qualname__ = "HipBackend." + _name

@@ -132,6 +132,9 @@ SYMBOLS = {
                         ctypes.POINTER(ctypes.c_float)],
     "xengDetrendInitialize": [_i, _i, _i, _i, _i, _i, _i, ctypes.c_float], "xengDetrendRun": [_vp, _i, _vp, _pi], "xengDetrendReset": [],
     "xengDetrendGetInfo": [_pll, _pll], "xengDetrendGetKnots": [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_ubyte)],
+    "xengCutoutInitialize": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float], "xengCutoutSetDelays": [_pi],
+    "xengCutoutSetWeights": [ctypes.POINTER(ctypes.c_float)], "xengCutoutRequest": [_i, _vp], "xengCutoutRun": [_vp, _i, _vp, _pi, _pi, _pi, _pi],
+    "xengCutoutReset": [], "xengCutoutGetInfo": [_pll, _pi, _pll],
     "xengCdedispInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdedispSetChirp": [ctypes.POINTER(ctypes.c_float)],
     "xengCdedispRun": [_vp, _vp, _pi], "xengCdedispReset": [], "xengCdedispGetInfo": [_pi, _pi, _pll, _pll],
     "xengCdlongInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdlongSetChirp": [_i, ctypes.POINTER(ctypes.c_float)],
@@ -189,7 +192,9 @@ NEWEST_ENGINES = [("Candfold", "candfold", True)]
 LATEST_ENGINES = [("Rfi", "rfi", True)]
 # ... and since tests/test_rfi_cpu.py pinned LATEST_ENGINES
 FURTHER_ENGINES = [("Detrend", "detrend", True)]
-for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES + FURTHER_ENGINES:
+# ... and since tests/test_detrend_cpu.py pinned FURTHER_ENGINES
+CUTOUT_ENGINES = [("Cutout", "cutout", True)]
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES + FURTHER_ENGINES + CUTOUT_ENGINES:
     SYMBOLS.update({"xeng%sMark" % _c: [ctypes.POINTER(ctypes.c_ulonglong)], "xeng%sWait" % _c: [ctypes.c_ulonglong],
                     "xeng%sTicketDone" % _c: [ctypes.c_ulonglong, _pi], "xeng%sSync" % _c: [], "xeng%sDestroy" % _c: []})
     if _guards:
@@ -235,7 +240,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengUpchanSpectraRun", "xengUpchanSpectraRunParts", "xengUpchanSpectraPrime", "xengUpchanSpectraPrimeParts", "xengUpchanSpectraReset",
                 "xengDedispRun", "xengDedispReset", "xengPulseRun", "xengPulseReset", "xengFoldRun", "xengFoldReset", "xengPeriodRun", "xengPeriodReset",
                 "xengPlongRun", "xengPlongReset", "xengAccelRun", "xengAccelReset",
-                "xengFfaRun", "xengFfaReset", "xengCandfoldRun", "xengCandfoldReset", "xengRfiRun", "xengRfiReset", "xengDetrendRun", "xengDetrendReset", "xengCdedispRun", "xengCdedispReset", "xengCdlongRun", "xengCdlongReset",
+                "xengFfaRun", "xengFfaReset", "xengCandfoldRun", "xengCandfoldReset", "xengRfiRun", "xengRfiReset", "xengDetrendRun", "xengDetrendReset", "xengCutoutRun", "xengCutoutReset", "xengCutoutRequest", "xengCdedispRun", "xengCdedispReset", "xengCdlongRun", "xengCdlongReset",
                 "xengImageRun", "xengGaincalRun", "xengCalapplyRun", "xengPeelRun", "xengCleanRun", "xengFlagRun", "xengPredictRun",
                 "xengImsearchRun", "xengImsearchReset",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
@@ -244,7 +249,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengRingCommitExternal", "xengRingNextSequence", "xengRingAcquire", "xengRingAcquireParts", "xengRingSpanRelease", "xengRingGetInfo",
                 "xengRingOpenReader", "xengRingCloseReader", "xengRingResize",
                 "xengStampNow", "xengStampNowFor", "xengStampDone", "xengGetDevice", "xengSetDevice"]
-for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES + FURTHER_ENGINES:     # an event record and an event query: neither can wait
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES + FURTHER_ENGINES + CUTOUT_ENGINES:     # an event record and an event query: neither can wait
     ENQUEUE_ONLY += ["xeng%sMark" % _c, "xeng%sTicketDone" % _c]
 _enq = None
 

@@ -1328,6 +1328,98 @@ int xengDetrendTicketDone(unsigned long long ticket, int *done);
 int xengDetrendSync(void);
 int xengDetrendDestroy(void);
 
+/* ---------------------------------------------------------------- Dedispersed cut-outs and DM refinement of single pulses
+ * BeamPulseCutout (no reference counterpart): the follow-up stage of a single-pulse candidate, as xengCandfold* is that of a
+ * periodic one.  The engine keeps a history of the channelised power beams of its own and, on request, cuts out of it the
+ * dedispersed dynamic spectrum of one pulse (the waterfall), its DM-time plane over a fine DM grid (the "bow tie"), and the best
+ * boxcar score over that plane: a DM finer than the search grid, a width and a time.  The library knows integers only: nothing of
+ * the dispersion constant, of time or of DM (blocks/pulse_cutout.py).
+ * Everything is fp32; fl() is one rounding; no product is contracted into a sum except where fmaf is written.
+ *   in       f32[nwin_call][npair][nfine][4] = [XX, YY, Re XY*, Im XY*], what xengDedispRun and xengFoldRun take; 16-byte
+ *            aligned, never written.  x = fl(XX + YY).  n counts windows since the last reset.
+ *   history  f32[npair][nfine][L], L = nhist + nwin, time the fastest axis: window n at slot n mod L, stored unweighted.  After a
+ *            call that ends at count n the windows [max(0, n - nhist), n) are held.  xengCutoutReset moves the host's counts and
+ *            drops the pending requests; it launches and clears nothing: by index, nothing from before window 0 is read.
+ *   tables   SetDelays: i32[ndmf][nfine], the forward delays s[d][q] >= 0 of a fine DM grid (blocks/dedisp.py dm_delays' output
+ *            as it is); refused if a delay is negative or max s + ntu > nhist; it clears the count and the pending requests.
+ *            SetWeights: f32[nfine], finite (NULL: all 1); a weight of 0 leaves a channel out; it acts on the history held.
+ *   sizes    at Initialize: 1 <= npair <= 65535; nfine >= 1; 1 <= nwin; 1 <= ndmf, ndmf nfine <= 2^28; nband in 1..256 divides
+ *            nfine, band g = channels [g nfine/nband, (g+1) nfine/nband); tscr a power of two in 1..64; nt even in 16..1024,
+ *            ntu = nt tscr; ndmc in 1..256, centre row c = ndmc div 2; nwidth >= 1 with 2^(nwidth-1) <= nt/2; nreq_max in 1..64;
+ *            nhist >= ntu; k_mad finite and > 0 (the host folds in 1.4826); the history below XENG_CUTOUT_MAX_HISTORY_BYTES.
+ *   request  xengCutoutReq {i32 id, i32 pair, i64 n_c, i32 ic, i32 dstep}: n_c is the window at which the pulse stands in the
+ *            zero-delay channel.  Row i of the cut-out is fine trial d_i = ic + (i - c) dstep, dstep >= 1; a row with d_i outside
+ *            0..ndmf-1 is ABSENT.  Column m of 0..ntu-1 is window a(m) = n_c - ntu/2 + m at the zero-delay channel.  The request
+ *            needs the windows from first = a(0) to last = a(ntu-1) + max over present rows of max_q s[d_i][q].  Refused, and
+ *            then none of the call's requests is taken: a pair or an ic out of range, n_c < 0 or >= 2^62, dstep outside 1..2^20,
+ *            more than XENG_CUTOUT_MAX_PENDING waiting.
+ *   serving  The host's counts decide, before anything is enqueued.  After the ingest of a call that ends at count n the pending
+ *            requests are taken in the order given: first < n - nhist: EXPIRED, reported and never served; otherwise last < n:
+ *            SERVED, in slot 0, 1, .. of this call, at most nreq_max per call (one that is due beyond that waits); otherwise
+ *            it waits.  Run returns the ids served, in slot order, and the ids expired.  A request given before its last window
+ *            comes is served for certain if nhist >= ntu + S + nwin - 1 (S its largest delay: the call that brings the last
+ *            window may bring nwin - 1 more), and nwin more for every call it may have to wait for a free slot.
+ *   partials for a present row i, band g and column m: D_i[g][m] starts from +0 and takes the band's channels in ascending q, one
+ *            fmaf(w[q], v, sum) each, v = x[a(m) + s[d_i][q]][pair][q], and v = +0 where w[q] = 0 or the window lies before 0 (a
+ *            select, as in xengDedispRun: a NaN in a left-out channel never arrives).
+ *   waterfall W[g][j] = sum over u = 0..tscr-1 ascending of D_c[g][j tscr + u], plain adds from +0 (all +0 if row c is absent:
+ *            it cannot be, 0 <= ic < ndmf).
+ *   plane    B_i[m] = sum over g ascending of D_i[g][m], plain adds from +0; P[i][j] = sum over u ascending of B_i[j tscr + u],
+ *            plain adds from +0.  An absent row is +0.
+ *   refine   per present row: M_i and A_i are the median and the median absolute deviation of P[i][0..nt) by xengDetrend's knot
+ *            rule: ranked by a sortable key of fl(v + 0), lo and hi the values of ranks nt/2 - 1 and nt/2, the median
+ *            fl(0.5f fl(lo + hi)); A_i the same of |fl(fl(v + 0) - M_i)|.  The row is VALID iff all nt values are finite and
+ *            0 < fl(k_mad A_i) < +inf; then G_i = fl(1.0f / fl(k_mad A_i)), correctly rounded.  y[j] = fl(P[i][j] - M_i).
+ *            Boxcars as xengPulseRun's tree: B_1 = y, B_2w[j] = fl(B_w[j] + B_w[j - w]) for j >= 2w - 1.  The score
+ *            C = fl(fl(B_w[j] G_i) rho_iw), w = 2^iw, rho_iw = (float)2^(-iw/2) formed on the host.
+ *   record   the largest C over valid rows, iw < nwidth and j >= w - 1; among equals (+0 and -0 are equal) the smallest i, then
+ *            iw, then j.  A NaN is never a maximum.  S0 is the best score of the centre row by the same rule, +0 without one.
+ *   out      A call that serves nothing launches the ingest only and touches no output (out_dev may be NULL then).  A call that
+ *            serves r >= 1 writes: nreq_max records of 32 bytes {i32 id, i32 status, f32 S, f32 S0, i16 i, i16 iw, i16 j, i16 0,
+ *            f32 M, f32 A} (M and A of row i); slots from r on read {-1, 0, +0, +0, -1, -1, -1, 0, +0, +0}; a served request
+ *            without a score {id, 1, +0, S0 = +0, -1, -1, -1, 0, +0, +0}.  Then per slot W f32[nband][nt] (slot z at byte
+ *            32 nreq_max + 4 z nband nt), then per slot P f32[ndmc][nt] (slot z at 32 nreq_max + 4 nreq_max nband nt +
+ *            4 z ndmc nt).  Only the areas of slots < r are written, and nothing past nreq_max (32 + 4 nt (nband + ndmc)) bytes.
+ *   state    between two guard bands of 64 KiB: the history, the two tables, the row records of the last serving call.
+ * A served cut-out is a fixed function of the window stream, the tables and the request: bit-identical however the run is split
+ * over calls and whichever call serves it, after a Reset as in a fresh context, and whatever else runs on the GPU.  Exact on
+ * integer data while the sums stay below 2^24.
+ * Rejected at Initialize, before any device is touched: every size outside the ranges above.  Rejected by Run without a launch: a
+ * NULL or misaligned input, a NULL result, nwin_call outside 1..nwin, a NULL or misaligned output on a serving call (the pending
+ * requests stay as they were).  Every call without a context, and Run or Request before SetDelays: XENG_STATUS_INVALID_STATE.
+ * Not built: the four Stokes words (I only), sharing xengDedisp's ring instead of a second history, sub-window delays, a
+ * scattering fit, a file or trigger writer. */
+#define XENG_CUTOUT_MAX_HISTORY_BYTES (1LL << 32)
+#define XENG_CUTOUT_MAX_PENDING 1024
+typedef struct xengCutoutReq {
+    int id, pair;
+    long long n_c;
+    int ic, dstep;
+} xengCutoutReq;
+int xengCutoutInitialize(int gpu, int npair, int nfine, int nwin, int ndmf, int nhist, int nband, int nt, int tscr, int ndmc, int nwidth, int nreq_max,
+                         float k_mad);
+/* host array i32[ndmf][nfine].  Waits for the context's work in flight; clears the count and the pending requests */
+int xengCutoutSetDelays(const int *delays);
+/* host array f32[nfine], or NULL for all 1.  Waits for the context's work in flight */
+int xengCutoutSetWeights(const float *weights);
+/* host array of nreq requests, appended to the pending ones in the order given: all of them or, on a refusal, none */
+int xengCutoutRequest(int nreq, const xengCutoutReq *reqs);
+/* enqueue only.  served_ids i32[nreq_max] and expired_ids i32[XENG_CUTOUT_MAX_PENDING] are host arrays; out_dev is written only
+ * when *nserved >= 1 */
+int xengCutoutRun(const void *in_dev, int nwin_call, void *out_dev, int *nserved, int *served_ids, int *nexpired, int *expired_ids);
+/* the host's counts and the pending requests only */
+int xengCutoutReset(void);
+/* windows taken since the last reset, requests waiting, and the bytes of a serving call's output */
+int xengCutoutGetInfo(long long *nwindows_since_reset, int *npending, long long *out_bytes);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengCutoutCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengCutoutMark(unsigned long long *ticket);
+int xengCutoutWait(unsigned long long ticket);
+int xengCutoutTicketDone(unsigned long long ticket, int *done);
+int xengCutoutSync(void);
+int xengCutoutDestroy(void);
+
 /* ---------------------------------------------------------------- Coherent dedispersion of the voltage beams
  * BeamCoherentDedisperse (no reference counterpart): every (coarse channel, selected beam) row of the voltage beams is filtered by
  * overlap-save with a table given in the frequency domain, and comes out in the format it came in.  The library knows nothing of
