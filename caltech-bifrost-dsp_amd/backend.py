@@ -768,6 +768,49 @@ class HipBackend:
         ffi.call("xengCutoutGetInfo", ctypes.byref(n), ctypes.byref(k), ctypes.byref(b))
         return n.value, k.value, b.value
 
+    # ---- Faraday rotation-measure synthesis of folded profiles (BeamRmSynth; include/xeng.h "Faraday rotation-measure synthesis of
+    # folded profiles"): a context of its own, its kernels on the beamformer's stream
+    def rmsynth_initialize(self, gpu, npair, nchg, nbin, nphi, feeds):
+        """feeds: 0 linear, 1 circular."""
+        return self._lib.xengRmsynthInitialize(int(gpu), int(npair), int(nchg), int(nbin), int(nphi), int(feeds))
+
+    def rmsynth_set_table(self, T, w=None, use=None):
+        """T: host float32 [nchg][nphi][2] = (Tc, Ts), C-contiguous; w: host float32 [nchg] or None (all 1); use: host uint8 [nchg] or
+        None (all).  Waits for the context's work in flight."""
+        if T.dtype != np.float32 or not T.flags.c_contiguous or (use is not None and (use.dtype != np.uint8 or not use.flags.c_contiguous)):
+            raise ValueError("rmsynth_set_table: the table must be C-contiguous float32 and `use` C-contiguous uint8")
+        return self._lib.xengRmsynthSetTable(T.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), _host_floats(w),
+                                             None if use is None else use.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
+
+    def rmsynth_set_masks(self, off=None, on=None):
+        """off, on: host uint8 [npair][nbin], C-contiguous, or None (every bin).  Waits for the context's work in flight."""
+        for m in (off, on):
+            if m is not None and (m.dtype != np.uint8 or not m.flags.c_contiguous):
+                raise ValueError("rmsynth_set_masks: a mask must be C-contiguous uint8")
+        pb = ctypes.POINTER(ctypes.c_ubyte)
+        return self._lib.xengRmsynthSetMasks(None if off is None else off.ctypes.data_as(pb), None if on is None else on.ctypes.data_as(pb))
+
+    def rmsynth_set_active(self, active=None):
+        """active: host uint8 [npair] or None (all).  Waits for the context's work in flight."""
+        if active is not None and (active.dtype != np.uint8 or not active.flags.c_contiguous):
+            raise ValueError("rmsynth_set_active: the list must be C-contiguous uint8")
+        return self._lib.xengRmsynthSetActive(None if active is None else active.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
+
+    def rmsynth_run(self, in_arr, out_arr):
+        """Enqueue only: f32 [npair][4][nchg][nbin] in; records, spec and the profile out (rmsynth_info's offsets); rmsynth_mark /
+        wait cover it."""
+        return self._enq.xengRmsynthRun(in_arr.ptr, out_arr.ptr)
+
+    def rmsynth_reset(self):
+        """The call count starts again (host state only: a call carries nothing over to the next)."""
+        ffi.check("xengRmsynthReset", self._enq.xengRmsynthReset())
+
+    def rmsynth_info(self):
+        """(calls since the last reset, used channels or -1 without a table, byte offset of spec, of the profile, bytes of the output)"""
+        n, k, a, b, c = ctypes.c_longlong(), ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong()
+        ffi.call("xengRmsynthGetInfo", ctypes.byref(n), ctypes.byref(k), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+        return n.value, k.value, a.value, b.value, c.value
+
     # ---- coherent dedispersion of the voltage beams (BeamCoherentDedisperse; include/xeng.h "Coherent dedispersion of the voltage
     # beams"): a context of its own, its kernels on the beamformer's stream
     def cdedisp_initialize(self, gpu, nchan, nbeam, ntime, pair0, npair, nfft, overlap):
@@ -1096,7 +1139,7 @@ class HipBackend:
         ffi.call("xengImsearchGetBaseline", *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for a in out])
         return tuple(out)
 
-    # ---- completion tickets and guard bands of the engines of ffi.ENGINES, ffi.MORE_ENGINES, ffi.NEWER_ENGINES, ffi.NEWEST_ENGINES, ffi.LATEST_ENGINES, ffi.FURTHER_ENGINES and ffi.CUTOUT_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
+    # ---- completion tickets and guard bands of the engines of ffi.ENGINES, ffi.MORE_ENGINES, ffi.NEWER_ENGINES, ffi.NEWEST_ENGINES, ffi.LATEST_ENGINES, ffi.FURTHER_ENGINES, ffi.CUTOUT_ENGINES and ffi.RMSYNTH_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
     # _guards_intact are made from these below the class
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
@@ -1152,7 +1195,7 @@ def _engine_methods(cname, prefix, guards):
     return {"%s_%s" % (prefix, k): f for k, f in fs.items()}
 
 
-for _row in ffi.ENGINES + ffi.MORE_ENGINES + ffi.NEWER_ENGINES + ffi.NEWEST_ENGINES + ffi.LATEST_ENGINES + ffi.FURTHER_ENGINES + ffi.CUTOUT_ENGINES:
+for _row in ffi.ENGINES + ffi.MORE_ENGINES + ffi.NEWER_ENGINES + ffi.NEWEST_ENGINES + ffi.LATEST_ENGINES + ffi.FURTHER_ENGINES + ffi.CUTOUT_ENGINES + ffi.RMSYNTH_ENGINES:
     for _name, _f in _engine_methods(*_row).items():
         _f.__name__ = _name
         _f.__qualname__ = "HipBackend." + _name

@@ -1420,6 +1420,73 @@ int xengCutoutTicketDone(unsigned long long ticket, int *done);
 int xengCutoutSync(void);
 int xengCutoutDestroy(void);
 
+/* ---------------------------------------------------------------- Faraday rotation-measure synthesis of folded profiles
+ * BeamRmSynth (no reference counterpart): the follow-up stage of the folded dual-pol cube xengFoldDump writes at nprod = 4.  Per
+ * beam pair: the Faraday spectrum over a grid of nphi depths, the depth of its peak, and the band-summed I, Q, U, V profile
+ * de-rotated at that depth.  The library takes numbers and knows nothing of Faraday rotation, wavelengths or depths: the host
+ * gives, per channel group g and depth k, the two words of a rotation (blocks/rm_synth.py rm_table).
+ * Everything is fp32; fl() is one rounding; no product is contracted into a sum except where fmaf is written.
+ *   in       X f32[npair][4][nchg][nbin], bin the fastest; 16-byte aligned, never written.
+ *   tables   SetTable: T f32[nchg][nphi][2] = (Tc, Ts), w f32[nchg] (NULL: all 1), use u8[nchg] (NULL: all 1); w finite, T finite
+ *            in the used channels.  A channel with use = 0 is never read, in X or in T: a NaN there is harmless.
+ *            SetMasks: off, on u8[npair][nbin], the off-pulse and on-pulse bins (NULL: every bin); n_off and n_on count them.
+ *            SetActive: u8[npair] (NULL: all).  The setters wait for the context's work in flight.
+ *   sizes    at Initialize: 1 <= npair <= 65535; 1 <= nchg <= 65536; 1 <= nbin <= 65536; 1 <= nphi <= 4096; nchg nphi 8 bytes
+ *            <= 1 GiB; feeds 0 (linear) or 1 (circular); the output and the run partials below 4 GiB each.
+ *   stokes   per (p, g, b), X0..X3 the four words:  linear   i = fl(X0+X1), q = fl(X0-X1), u = fl(X2+X2), v = fl(X3+X3)
+ *                                                   circular i = fl(X0+X1), q = fl(X2+X2), u = fl(X3+X3), v = fl(X0-X1)
+ *   baseline one value per (p, g) and word s of i, q, u, v: 64 partial chains from +0, chain j over the bins with b mod 64 = j and
+ *            off[p][b] != 0 in ascending b, plain adds; the 64 partials summed from +0 in ascending j; divided by (float)n_off,
+ *            correctly rounded; +0 if n_off = 0.  y_s = fl(s - base_s).
+ *   faraday  per (p, b, k): (re, im) from (+0, +0) over the used g in ascending order, four steps a channel in this order:
+ *            re = fmaf(y_q, Tc[g][k], re); re = fmaf(y_u, Ts[g][k], re); im = fmaf(y_u, Tc[g][k], im); im = fmaf(-y_q, Ts[g][k], im);
+ *            then pw = fmaf(im, im, fl(re re)).
+ *   spectrum per (p, k): per run r of 64 consecutive bins (b div 64 = r) a chain from +0 of plain adds of pw in ascending b over
+ *            on[p][b] != 0; spec[p][k] a chain from +0 of plain adds of the runs in ascending r.
+ *   record   per pair {i32 k, f32 peak, i32 n_on, i32 n_off}: k the depth of the largest spec[p][k], the smallest k among
+ *            equals (+0 and -0 are equal); a NaN is never chosen.  k = -1 and peak = +0 if n_on = 0 or no word is comparable.
+ *   profile  f32[npair][4][nbin]: words 0 and 3 chains from +0 of fmaf(w[g], y_i, .) and fmaf(w[g], y_v, .) over the used g in
+ *            ascending order; words 1 and 2 re and im of the Faraday word at the record's k, +0 if k = -1.
+ *   inactive nothing of X is read; the record is {-1, +0, 0, 0} and every word of spec and of the profile +0.
+ *   out      npair records of 16 bytes, then spec f32[npair][nphi] at byte 16 npair, then the profile at byte 16 npair +
+ *            4 npair nphi (xengRmsynthGetInfo gives both offsets and the size); nothing past it is written.
+ *   state    between two guard bands of 64 KiB: T, w, use, the list of used channels, the masks and their counts, the active
+ *            list, the baselines, the per-run partials, spec and the picked depths.
+ * Every output word is one chain in a fixed order: a call is a fixed function of X and the tables, bit-identical on a second call,
+ * after a Reset as in a fresh context, whatever the tile sizes and whatever else runs on the GPU; spec on a sub-list of the depths
+ * equals those words of the full spectrum bit for bit (a word of spec reads one column of T).  Which words are NaN is part of
+ * that; a NaN's sign and payload are not.  Exact on integer data while the sums stay below 2^24 (with a table of integers).
+ * xengRmsynthReset clears the call count; it launches and clears nothing.
+ * Rejected at Initialize, before any device is touched: every size outside the ranges above.  Rejected by Run without a launch: a
+ * NULL or misaligned input or output.  Every call without a context, and Run before SetTable: XENG_STATUS_INVALID_STATE.
+ * Not built: leakage and X-Y phase calibration, an ionospheric model, spectra summed over sub-integrations (additive: on the
+ * host), RM-CLEAN, a depth grid per pair, single-pulse RM from the cut-outs, a contraction on MFMAs. */
+#define XENG_RMSYNTH_MAX_NPHI 4096
+#define XENG_RMSYNTH_MAX_NBIN 65536
+#define XENG_RMSYNTH_MAX_NCHG 65536
+#define XENG_RMSYNTH_MAX_TABLE_BYTES (1LL << 30)
+int xengRmsynthInitialize(int gpu, int npair, int nchg, int nbin, int nphi, int feeds);
+/* host arrays f32[nchg][nphi][2], f32[nchg] or NULL, u8[nchg] or NULL.  Waits for the context's work in flight */
+int xengRmsynthSetTable(const float *T, const float *w, const unsigned char *use);
+/* host arrays u8[npair][nbin], either may be NULL (every bin).  Waits for the context's work in flight */
+int xengRmsynthSetMasks(const unsigned char *off, const unsigned char *on);
+/* host array u8[npair], or NULL for all.  Waits for the context's work in flight */
+int xengRmsynthSetActive(const unsigned char *active);
+/* enqueue only: four launches on the beamformer's stream */
+int xengRmsynthRun(const void *in_dev, void *out_dev);
+/* the host's call count only */
+int xengRmsynthReset(void);
+/* calls since the last reset, the used channels (-1 before SetTable), the byte offsets of spec and of the profile, the output's bytes */
+int xengRmsynthGetInfo(long long *ncalls_since_reset, int *nused, long long *spec_offset, long long *prof_offset, long long *out_bytes);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengRmsynthCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengRmsynthMark(unsigned long long *ticket);
+int xengRmsynthWait(unsigned long long ticket);
+int xengRmsynthTicketDone(unsigned long long ticket, int *done);
+int xengRmsynthSync(void);
+int xengRmsynthDestroy(void);
+
 /* ---------------------------------------------------------------- Coherent dedispersion of the voltage beams
  * BeamCoherentDedisperse (no reference counterpart): every (coarse channel, selected beam) row of the voltage beams is filtered by
  * overlap-save with a table given in the frequency domain, and comes out in the format it came in.  The library knows nothing of
