@@ -811,6 +811,63 @@ class HipBackend:
         ffi.call("xengRmsynthGetInfo", ctypes.byref(n), ctypes.byref(k), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
         return n.value, k.value, a.value, b.value, c.value
 
+    # ---- template-matched arrival phases of folded profiles (BeamToa; include/xeng.h "Template-matched arrival phases of folded
+    # profiles"): a context of its own, its kernels on the beamformer's stream
+    def toa_initialize(self, gpu, npair, nprod, nchg, nbin, nsub, nharm, nlag):
+        self._toa_nsub = int(nsub)
+        return self._lib.xengToaInitialize(int(gpu), int(npair), int(nprod), int(nchg), int(nbin), int(nsub), int(nharm), int(nlag))
+
+    def toa_set_bands(self, edges, w=None):
+        """edges: host int32 [nsub + 1], ascending group indices, C-contiguous; w: host float32 [nchg] or None (all 1); a group of
+        weight 0 is left out.  Waits for the context's work in flight."""
+        if edges.dtype != np.int32 or not edges.flags.c_contiguous:
+            raise ValueError("toa_set_bands: the edges must be C-contiguous int32")
+        return self._lib.xengToaSetBands(edges.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _host_floats(w))
+
+    def toa_set_tables(self, D, L):
+        """D: host float32 [nbin][nharm][2], L: host float32 [nharm][nlag][2] (blocks/toa.py toa_tables), C-contiguous.  Waits for
+        the context's work in flight."""
+        for t in (D, L):
+            if t.dtype != np.float32 or not t.flags.c_contiguous:
+                raise ValueError("toa_set_tables: a table must be C-contiguous float32")
+        pf = ctypes.POINTER(ctypes.c_float)
+        return self._lib.xengToaSetTables(D.ctypes.data_as(pf), L.ctypes.data_as(pf))
+
+    def toa_set_template(self, S):
+        """S: host float32 [npair][nsub + 1][nharm][2] (blocks/toa.py toa_template), C-contiguous.  Waits for the context's work in
+        flight."""
+        if S.dtype != np.float32 or not S.flags.c_contiguous:
+            raise ValueError("toa_set_template: the template must be C-contiguous float32")
+        return self._lib.xengToaSetTemplate(S.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+
+    def toa_set_mask(self, off=None):
+        """off: host uint8 [npair][nbin], C-contiguous, or None (every bin).  Waits for the context's work in flight."""
+        if off is not None and (off.dtype != np.uint8 or not off.flags.c_contiguous):
+            raise ValueError("toa_set_mask: the mask must be C-contiguous uint8")
+        return self._lib.xengToaSetMask(None if off is None else off.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
+
+    def toa_set_active(self, active=None):
+        """active: host uint8 [npair] or None (all).  Waits for the context's work in flight."""
+        if active is not None and (active.dtype != np.uint8 or not active.flags.c_contiguous):
+            raise ValueError("toa_set_active: the list must be C-contiguous uint8")
+        return self._lib.xengToaSetActive(None if active is None else active.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
+
+    def toa_run(self, in_arr, out_arr):
+        """Enqueue only: f32 [npair][nprod][nchg][nbin] in; records, P, PH and ccf out (toa_info's offsets); toa_mark / wait cover it."""
+        return self._enq.xengToaRun(in_arr.ptr, out_arr.ptr)
+
+    def toa_reset(self):
+        """The call count starts again (host state only: a call carries nothing over to the next)."""
+        ffi.check("xengToaReset", self._enq.xengToaReset())
+
+    def toa_info(self):
+        """(calls since the last reset, used groups per sub-band (-1 each before toa_set_bands), byte offset of P, of PH, of ccf,
+        bytes of the output)"""
+        n, a, b, c, d = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong()
+        used = (ctypes.c_int * self._toa_nsub)()
+        ffi.call("xengToaGetInfo", ctypes.byref(n), used, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d))
+        return n.value, list(used), a.value, b.value, c.value, d.value
+
     # ---- coherent dedispersion of the voltage beams (BeamCoherentDedisperse; include/xeng.h "Coherent dedispersion of the voltage
     # beams"): a context of its own, its kernels on the beamformer's stream
     def cdedisp_initialize(self, gpu, nchan, nbeam, ntime, pair0, npair, nfft, overlap):
@@ -1139,7 +1196,7 @@ class HipBackend:
         ffi.call("xengImsearchGetBaseline", *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for a in out])
         return tuple(out)
 
-    # ---- completion tickets and guard bands of the engines of ffi.ENGINES, ffi.MORE_ENGINES, ffi.NEWER_ENGINES, ffi.NEWEST_ENGINES, ffi.LATEST_ENGINES, ffi.FURTHER_ENGINES, ffi.CUTOUT_ENGINES and ffi.RMSYNTH_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
+    # ---- completion tickets and guard bands of the engines of ffi.ENGINES, ffi.MORE_ENGINES, ffi.NEWER_ENGINES, ffi.NEWEST_ENGINES, ffi.LATEST_ENGINES, ffi.FURTHER_ENGINES, ffi.CUTOUT_ENGINES, ffi.RMSYNTH_ENGINES and ffi.TOA_ENGINES: <prefix>_mark / _wait / _ticket_done / _sync /
     # _guards_intact are made from these below the class
     def _mark(self, mark):
         t = ctypes.c_ulonglong()
@@ -1195,7 +1252,7 @@ def _engine_methods(cname, prefix, guards):
     return {"%s_%s" % (prefix, k): f for k, f in fs.items()}
 
 
-for _row in ffi.ENGINES + ffi.MORE_ENGINES + ffi.NEWER_ENGINES + ffi.NEWEST_ENGINES + ffi.LATEST_ENGINES + ffi.FURTHER_ENGINES + ffi.CUTOUT_ENGINES + ffi.RMSYNTH_ENGINES:
+for _row in ffi.ENGINES + ffi.MORE_ENGINES + ffi.NEWER_ENGINES + ffi.NEWEST_ENGINES + ffi.LATEST_ENGINES + ffi.FURTHER_ENGINES + ffi.CUTOUT_ENGINES + ffi.RMSYNTH_ENGINES + ffi.TOA_ENGINES:
     for _name, _f in _engine_methods(*_row).items():
         _f.__name__ = _name
         _f.__qualname__ = "HipBackend." + _name

@@ -41,6 +41,9 @@ from .pulse_cutout import (CUTOUT_RECORD, CUTOUT_REQUEST, CutoutQueue, as_cutout
 from .beam_rm_synth_block import BeamRmSynth
 from .rm_synth import (RM_RECORD, as_rmsynth, pol_profile, rm_error, rm_lambda2, rm_offsets, rm_plan, rm_reference, rm_refine, rm_significance, rm_table,
                        rmsf)
+from .beam_toa_block import BeamToa
+from .toa import (TOA_RECORD, as_toa, subband_frequencies, toa_dm_fit, toa_epoch, toa_offsets, toa_reference, toa_refine, toa_subbands, toa_tables,
+                  toa_template)
 from .beam_fold_block import BeamFold
 from .fold import fold_phase, fold_rotations, fold_rotations_coherent, profile_snr
 from .beam_coherent_dedisperse_block import BeamCoherentDedisperse
@@ -61,5 +64,5 @@ from .flagging import flag_factors, flag_summary, flag_visibilities, stand_weigh
 from .calibration import apply_gains, direction_model_visibilities, inverse_gains, model_flux, model_visibilities, reference_phase
 from .spectral_kurtosis import incoherent_beam, sk_flags, sk_limits, spectral_kurtosis
 
-__all__ = ["Block", "Corr", "CorrAcc", "Beamform", "BeamformSumBeams", "Copy", "CorrSubsel", "CorrOutputFull", "Snap2Ingest", "BeamformOutput", "CorrOutputPart", "BeamformVlbiOutput", "UpchanBeamform", "TbfSource", "UpchanCorr", "UpchanSumBeams", "UpchanSpectra", "BeamDedisperse", "dm_delays", "BeamPulseSearch", "pulse_candidates", "BeamPeriodSearch", "BeamPeriodSearchLong", "period_bands", "period_candidates_long", "period_sift", "BeamAccelSearch", "ACCEL_RECORD", "accel_alpha", "accel_of", "accel_index", "accel_trials", "accel_candidates", "as_records_accel", "BeamFfaSearch", "period_candidates", "period_pfa", "ffa_candidates", "ffa_period", "ffa_plan", "ffa_rows", "BeamCandFold", "CANDFOLD_RECORD", "as_records_candfold", "candfold_candidates", "candfold_gains", "candfold_oscillators", "candfold_refined", "candfold_shifts", "candfold_sigma", "candfold_trials", "BeamRfiClean", "rfi_controls", "rfi_mad", "rfi_median", "rfi_occupancy", "rfi_tree_sum", "rfi_weights", "BeamDetrend", "detrend_k_mad", "detrend_plan", "detrend_reference", "detrend_startup", "BeamPulseCutout", "CUTOUT_RECORD", "CUTOUT_REQUEST", "CutoutQueue", "as_cutouts", "cutout_fine_dms", "cutout_k_mad", "cutout_offsets", "cutout_plan", "cutout_reference", "cutout_refined", "cutout_requests", "BeamRmSynth", "RM_RECORD", "as_rmsynth", "pol_profile", "rm_error", "rm_lambda2", "rm_offsets", "rm_plan", "rm_reference", "rm_refine", "rm_significance", "rm_table", "rmsf", "BeamFold", "fold_phase", "fold_rotations", "fold_rotations_coherent", "profile_snr", "BeamCoherentDedisperse", "BeamCoherentDedisperseLong", "chirp_table", "smear_samples", "cdedisp_plan", "cdedisp_plan_long", "UpchanImage", "pixel_grid", "patch", "steering_delays", "direction_list", "image_norm", "stokes_i", "UpchanClean", "psf", "clean_components", "clean_layout", "restore", "components_to_model", "UpchanGainCal", "UpchanCalApply", "UpchanPeel", "UpchanFlag", "UpchanPredict", "component_visibilities", "UpchanImageSearch", "IMSEARCH_RECORD", "group_frequencies", "image_dm_delays", "image_candidates", "flag_factors", "stand_weights", "flag_visibilities", "flag_summary", "model_visibilities", "direction_model_visibilities", "model_flux", "apply_gains", "inverse_gains", "reference_phase", "spectral_kurtosis", "sk_limits", "sk_flags", "incoherent_beam", "regtile_index", "tri_index",
+__all__ = ["Block", "Corr", "CorrAcc", "Beamform", "BeamformSumBeams", "Copy", "CorrSubsel", "CorrOutputFull", "Snap2Ingest", "BeamformOutput", "CorrOutputPart", "BeamformVlbiOutput", "UpchanBeamform", "TbfSource", "UpchanCorr", "UpchanSumBeams", "UpchanSpectra", "BeamDedisperse", "dm_delays", "BeamPulseSearch", "pulse_candidates", "BeamPeriodSearch", "BeamPeriodSearchLong", "period_bands", "period_candidates_long", "period_sift", "BeamAccelSearch", "ACCEL_RECORD", "accel_alpha", "accel_of", "accel_index", "accel_trials", "accel_candidates", "as_records_accel", "BeamFfaSearch", "period_candidates", "period_pfa", "ffa_candidates", "ffa_period", "ffa_plan", "ffa_rows", "BeamCandFold", "CANDFOLD_RECORD", "as_records_candfold", "candfold_candidates", "candfold_gains", "candfold_oscillators", "candfold_refined", "candfold_shifts", "candfold_sigma", "candfold_trials", "BeamRfiClean", "rfi_controls", "rfi_mad", "rfi_median", "rfi_occupancy", "rfi_tree_sum", "rfi_weights", "BeamDetrend", "detrend_k_mad", "detrend_plan", "detrend_reference", "detrend_startup", "BeamPulseCutout", "CUTOUT_RECORD", "CUTOUT_REQUEST", "CutoutQueue", "as_cutouts", "cutout_fine_dms", "cutout_k_mad", "cutout_offsets", "cutout_plan", "cutout_reference", "cutout_refined", "cutout_requests", "BeamRmSynth", "RM_RECORD", "as_rmsynth", "pol_profile", "rm_error", "rm_lambda2", "rm_offsets", "rm_plan", "rm_reference", "rm_refine", "rm_significance", "rm_table", "rmsf", "BeamToa", "TOA_RECORD", "as_toa", "subband_frequencies", "toa_dm_fit", "toa_epoch", "toa_offsets", "toa_reference", "toa_refine", "toa_subbands", "toa_tables", "toa_template", "BeamFold", "fold_phase", "fold_rotations", "fold_rotations_coherent", "profile_snr", "BeamCoherentDedisperse", "BeamCoherentDedisperseLong", "chirp_table", "smear_samples", "cdedisp_plan", "cdedisp_plan_long", "UpchanImage", "pixel_grid", "patch", "steering_delays", "direction_list", "image_norm", "stokes_i", "UpchanClean", "psf", "clean_components", "clean_layout", "restore", "components_to_model", "UpchanGainCal", "UpchanCalApply", "UpchanPeel", "UpchanFlag", "UpchanPredict", "component_visibilities", "UpchanImageSearch", "IMSEARCH_RECORD", "group_frequencies", "image_dm_delays", "image_candidates", "flag_factors", "stand_weights", "flag_visibilities", "flag_summary", "model_visibilities", "direction_model_visibilities", "model_flux", "apply_gains", "inverse_gains", "reference_phase", "spectral_kurtosis", "sk_limits", "sk_flags", "incoherent_beam", "regtile_index", "tri_index",
            "COMMAND_OK", "COMMAND_NOT_RECOGNIZED", "COMMAND_WRONG_TYPE", "COMMAND_INVALID"]

@@ -90,7 +90,7 @@ struct TicketRing {
 };
 // What every engine beside the beamformer on its stream has (Upchan, UpchanCorr, UpchanSumBeams, UpchanSpectra, Dedisp,
 // Pulse, Fold, Period, Ffa, Cdedisp, Cdlong, Image, Gaincal, Calapply, Peel, Clean, Flag, Predict, Imsearch; the table
-// ENGINES of ffi.py lists the same nineteen; Plong, Accel, Candfold, Rfi, Detrend, Cutout and Rmsynth in the lists behind it there): each derives its process-global context from this and keeps a mutex of its
+// ENGINES of ffi.py lists the same nineteen; Plong, Accel, Candfold, Rfi, Detrend, Cutout, Rmsynth and Toa in the lists behind it there): each derives its process-global context from this and keeps a mutex of its
 // own.  Its kernels run on STREAM_BEAM and tick that clock, so that rings declared 'beam' and their span stamps cover
 // them unchanged.
 struct BeamStreamContext {

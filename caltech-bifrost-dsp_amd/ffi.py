@@ -138,6 +138,10 @@ SYMBOLS = {
     "xengRmsynthInitialize": [_i, _i, _i, _i, _i, _i], "xengRmsynthSetTable": [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_ubyte)],
     "xengRmsynthSetMasks": [ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_ubyte)], "xengRmsynthSetActive": [ctypes.POINTER(ctypes.c_ubyte)],
     "xengRmsynthRun": [_vp, _vp], "xengRmsynthReset": [], "xengRmsynthGetInfo": [_pll, _pi, _pll, _pll, _pll],
+    "xengToaInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengToaSetBands": [_pi, ctypes.POINTER(ctypes.c_float)],
+    "xengToaSetTables": [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)], "xengToaSetTemplate": [ctypes.POINTER(ctypes.c_float)],
+    "xengToaSetMask": [ctypes.POINTER(ctypes.c_ubyte)], "xengToaSetActive": [ctypes.POINTER(ctypes.c_ubyte)],
+    "xengToaRun": [_vp, _vp], "xengToaReset": [], "xengToaGetInfo": [_pll, _pi, _pll, _pll, _pll, _pll],
     "xengCdedispInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdedispSetChirp": [ctypes.POINTER(ctypes.c_float)],
     "xengCdedispRun": [_vp, _vp, _pi], "xengCdedispReset": [], "xengCdedispGetInfo": [_pi, _pi, _pll, _pll],
     "xengCdlongInitialize": [_i, _i, _i, _i, _i, _i, _i, _i], "xengCdlongSetChirp": [_i, ctypes.POINTER(ctypes.c_float)],
@@ -199,7 +203,9 @@ FURTHER_ENGINES = [("Detrend", "detrend", True)]
 CUTOUT_ENGINES = [("Cutout", "cutout", True)]
 # ... and since tests/test_cutout_cpu.py pinned CUTOUT_ENGINES
 RMSYNTH_ENGINES = [("Rmsynth", "rmsynth", True)]
-for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES + FURTHER_ENGINES + CUTOUT_ENGINES + RMSYNTH_ENGINES:
+# ... and since tests/test_rmsynth_cpu.py pinned RMSYNTH_ENGINES
+TOA_ENGINES = [("Toa", "toa", True)]
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES + FURTHER_ENGINES + CUTOUT_ENGINES + RMSYNTH_ENGINES + TOA_ENGINES:
     SYMBOLS.update({"xeng%sMark" % _c: [ctypes.POINTER(ctypes.c_ulonglong)], "xeng%sWait" % _c: [ctypes.c_ulonglong],
                     "xeng%sTicketDone" % _c: [ctypes.c_ulonglong, _pi], "xeng%sSync" % _c: [], "xeng%sDestroy" % _c: []})
     if _guards:
@@ -245,7 +251,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengUpchanSpectraRun", "xengUpchanSpectraRunParts", "xengUpchanSpectraPrime", "xengUpchanSpectraPrimeParts", "xengUpchanSpectraReset",
                 "xengDedispRun", "xengDedispReset", "xengPulseRun", "xengPulseReset", "xengFoldRun", "xengFoldReset", "xengPeriodRun", "xengPeriodReset",
                 "xengPlongRun", "xengPlongReset", "xengAccelRun", "xengAccelReset",
-                "xengFfaRun", "xengFfaReset", "xengCandfoldRun", "xengCandfoldReset", "xengRfiRun", "xengRfiReset", "xengDetrendRun", "xengDetrendReset", "xengCutoutRun", "xengCutoutReset", "xengCutoutRequest", "xengRmsynthRun", "xengRmsynthReset", "xengCdedispRun", "xengCdedispReset", "xengCdlongRun", "xengCdlongReset",
+                "xengFfaRun", "xengFfaReset", "xengCandfoldRun", "xengCandfoldReset", "xengRfiRun", "xengRfiReset", "xengDetrendRun", "xengDetrendReset", "xengCutoutRun", "xengCutoutReset", "xengCutoutRequest", "xengRmsynthRun", "xengRmsynthReset", "xengToaRun", "xengToaReset", "xengCdedispRun", "xengCdedispReset", "xengCdlongRun", "xengCdlongReset",
                 "xengImageRun", "xengGaincalRun", "xengCalapplyRun", "xengPeelRun", "xengCleanRun", "xengFlagRun", "xengPredictRun",
                 "xengImsearchRun", "xengImsearchReset",
                 "xengMapAddI32", "xengMapSumI32", "xengXgpuDumpDone", "xengBeamformTicketDone", "bfBeamformIntegrate", "bfBeamformIntegrateSingleBeam",
@@ -254,7 +260,7 @@ ENQUEUE_ONLY = ["xengXgpuTryKernelAsyncAcc", "xengXgpuTryKernelAsyncSlab", "xeng
                 "xengRingCommitExternal", "xengRingNextSequence", "xengRingAcquire", "xengRingAcquireParts", "xengRingSpanRelease", "xengRingGetInfo",
                 "xengRingOpenReader", "xengRingCloseReader", "xengRingResize",
                 "xengStampNow", "xengStampNowFor", "xengStampDone", "xengGetDevice", "xengSetDevice"]
-for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES + FURTHER_ENGINES + CUTOUT_ENGINES + RMSYNTH_ENGINES:     # an event record and an event query: neither can wait
+for _c, _prefix, _guards in ENGINES + MORE_ENGINES + NEWER_ENGINES + NEWEST_ENGINES + LATEST_ENGINES + FURTHER_ENGINES + CUTOUT_ENGINES + RMSYNTH_ENGINES + TOA_ENGINES:     # an event record and an event query: neither can wait
     ENQUEUE_ONLY += ["xeng%sMark" % _c, "xeng%sTicketDone" % _c]
 _enq = None
 

@@ -1487,6 +1487,88 @@ int xengRmsynthTicketDone(unsigned long long ticket, int *done);
 int xengRmsynthSync(void);
 int xengRmsynthDestroy(void);
 
+/* ---------------------------------------------------------------- Template-matched arrival phases of folded profiles
+ * BeamToa (no reference counterpart): the stage between the folded cube xengFoldDump writes (nprod = 1 or 4) and a timing program.
+ * Per beam pair and per row -- the nsub sub-bands r = 0 .. nsub-1 and the whole band r = nsub -- the weighted profile, its baseline
+ * and noise over the off-pulse bins, its harmonics 1 .. nharm, and its correlation with a template on a grid of nlag lags with the
+ * lag of the peak.  The library takes numbers and knows nothing of frequencies, pulsars or time: the host gives every sine and
+ * cosine as a table (blocks/toa.py toa_tables) and the templates' harmonics (toa_template), and does the sub-lag refinement, the DM
+ * fit and the conversion to a time in float64 from this output (toa_refine, toa_dm_fit, toa_epoch).
+ * Everything is fp32; fl() is one rounding; no product is contracted into a sum except where fmaf is written.  k = 1 .. nharm
+ * throughout; a table's index [k] is k - 1.
+ *   in       X f32[npair][nprod][nchg][nbin], bin the fastest; 16-byte aligned, never written.
+ *   tables   SetBands: edges i32[nsub+1], 0 <= edges[0] <= ... <= edges[nsub] <= nchg, sub-band r is the groups [edges[r], edges[r+1]);
+ *            w f32[nchg] (NULL: all 1), finite.  A group is used if it lies in a sub-band and w[g] != 0; a group that is not used is
+ *            never read: a NaN there is harmless.
+ *            SetTables: D f32[nbin][nharm][2] = (cos, -sin)(2 pi k b / nbin), L f32[nharm][nlag][2] = (cos, -sin)(2 pi k l / nlag).
+ *            SetTemplate: S f32[npair][nsub+1][nharm][2] = (sr, si).  D, L and S finite.
+ *            SetMask: off u8[npair][nbin], the off-pulse bins (NULL: every bin); n_off counts them.
+ *            SetActive: u8[npair] (NULL: all).  The setters wait for the context's work in flight.
+ *   sizes    at Initialize: 1 <= npair <= 65535; nprod 1 or 4; 1 <= nchg <= 65536; 1 <= nbin <= 16384; 1 <= nsub <= 256;
+ *            1 <= nharm <= min(4096, (nbin-1)/2); 1 <= nlag <= 65536; each of D, L, S at most 1 GiB; the output below 4 GiB.
+ *   x        per (p, g, b): X[p][0][g][b] at nprod = 1; fl(X[p][0][g][b] + X[p][1][g][b]) at nprod = 4.
+ *   P        P[p][r][b], r < nsub: a chain from +0 of acc = fmaf(w[g], x, acc) over the used groups of sub-band r in ascending g
+ *            (+0 if it has none).  P[p][nsub][b]: a chain from +0 of plain adds of P[p][r][b] over r = 0 .. nsub-1 ascending.
+ *   base     per (p, r): 64 partial chains from +0, chain j over the bins with b mod 64 = j and off[p][b] != 0 in ascending b, plain
+ *            adds of P; the 64 partials summed from +0 in ascending j; divided by (float)n_off, correctly rounded; +0 if n_off = 0.
+ *   var      the same scheme over fl(d d), d = fl(P - base); +0 if n_off = 0.
+ *   PH       PH[p][r][k] = (re, im): chains from +0 over all b ascending, re = fmaf(d_b, D[b][k][0], re), im = fmaf(d_b, D[b][k][1], im).
+ *   cross    cr = fmaf(re, sr, fl(im si)); ci = fmaf(im, sr, -fl(re si)), (sr, si) = S[p][r][k].
+ *   ccf      ccf[p][r][l]: a chain from +0 over k ascending, two steps a harmonic in this order:
+ *            acc = fmaf(cr, L[k][l][0], acc); acc = fmaf(ci, L[k][l][1], acc).  It peaks where l / nlag is the profile's delay behind
+ *            the template in turns.
+ *   record   per (p, r) {i32 l, f32 peak, f32 base, f32 var}: l the lag of the largest ccf[p][r][l], the smallest l among equals
+ *            (+0 and -0 are equal); a NaN is never chosen.  l = -1 and peak = +0 if no word is comparable or the row has no used
+ *            group (the band row: no sub-band has one); base and var are the words above either way.
+ *   inactive nothing of X is read; every record is {-1, +0, +0, +0} and every word of P, PH and ccf +0.
+ *   out      records [npair][nsub+1] of 16 bytes, then P f32[npair][nsub+1][nbin], then PH f32[npair][nsub+1][nharm][2], then
+ *            ccf f32[npair][nsub+1][nlag], with no gaps (xengToaGetInfo gives the three offsets and the size); nothing past it is
+ *            written.
+ *   state    between two guard bands of 64 KiB: D, L, S, w, the lists of used groups, the mask and its counts, the active list,
+ *            base and var.
+ * Every output word is one chain in a fixed order: a call is a fixed function of X and the tables, bit-identical on a second call,
+ * after a Reset as in a fresh context, whatever the tile sizes and whatever else runs on the GPU.  Which words are NaN is part of
+ * that; a NaN's sign and payload are not.  P is exact on integer data while the sums stay below 2^24.
+ * xengToaReset clears the call count; it launches and clears nothing.
+ * Rejected at Initialize, before any device is touched: every size outside the ranges above.  Rejected by the setters: a NULL or
+ * misaligned table, edges that descend or leave the groups, a word that is not finite.  Rejected by Run without a launch: a NULL or
+ * misaligned input or output.  Every call without a context, and Run before SetBands, SetTables and SetTemplate:
+ * XENG_STATUS_INVALID_STATE.
+ * Not built: barycentring, a par-file or polyco reader, a .tim or archive writer, template generation from data,
+ * profile-evolution (2-D template) fits, scattering fits. */
+#define XENG_TOA_MAX_NBIN 16384
+#define XENG_TOA_MAX_NHARM 4096
+#define XENG_TOA_MAX_NLAG 65536
+#define XENG_TOA_MAX_NSUB 256
+#define XENG_TOA_MAX_NCHG 65536
+#define XENG_TOA_MAX_TABLE_BYTES (1LL << 30)
+int xengToaInitialize(int gpu, int npair, int nprod, int nchg, int nbin, int nsub, int nharm, int nlag);
+/* host arrays i32[nsub+1] and f32[nchg] or NULL.  Waits for the context's work in flight */
+int xengToaSetBands(const int *edges, const float *w);
+/* host arrays f32[nbin][nharm][2] and f32[nharm][nlag][2].  Waits for the context's work in flight */
+int xengToaSetTables(const float *D, const float *L);
+/* host array f32[npair][nsub+1][nharm][2].  Waits for the context's work in flight */
+int xengToaSetTemplate(const float *S);
+/* host array u8[npair][nbin], or NULL for every bin.  Waits for the context's work in flight */
+int xengToaSetMask(const unsigned char *off);
+/* host array u8[npair], or NULL for all.  Waits for the context's work in flight */
+int xengToaSetActive(const unsigned char *active);
+/* enqueue only: six launches on the beamformer's stream */
+int xengToaRun(const void *in_dev, void *out_dev);
+/* the host's call count only */
+int xengToaReset(void);
+/* calls since the last reset, the used groups of each sub-band (i32[nsub], -1 before SetBands), the byte offsets of P, PH and ccf,
+ * the output's bytes */
+int xengToaGetInfo(long long *ncalls_since_reset, int *nused, long long *prof_offset, long long *harm_offset, long long *ccf_offset, long long *out_bytes);
+/* The state is allocated between two guard bands of 64 KiB: as xengDedispCheckGuards */
+int xengToaCheckGuards(int *intact);
+/* completion tickets for everything enqueued on the beamformer's stream so far, as xengUpchanMark / Wait / TicketDone */
+int xengToaMark(unsigned long long *ticket);
+int xengToaWait(unsigned long long ticket);
+int xengToaTicketDone(unsigned long long ticket, int *done);
+int xengToaSync(void);
+int xengToaDestroy(void);
+
 /* ---------------------------------------------------------------- Coherent dedispersion of the voltage beams
  * BeamCoherentDedisperse (no reference counterpart): every (coarse channel, selected beam) row of the voltage beams is filtered by
  * overlap-save with a table given in the frequency domain, and comes out in the format it came in.  The library knows nothing of
